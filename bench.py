@@ -139,6 +139,22 @@ def reference_compiled_check(name, pairs, tested):
     return bool(hashlib.sha256(keys.tobytes()).hexdigest() == str(ref[name + "_pairs_sha"]) and int(tested) == int(ref[name + "_tested"]))
 
 
+def dump_outputs(out_dir, pairs, tested, max_rows=1 << 21):
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST timed step, as float64 .npy files -- pairs.npy, the pair list in
+    canonical order (rows sorted lexicographically: the device's output order is an atomicAdd race, collision.cuh:40), n_pairs.npy and
+    pairs_tested.npy.  A list of more than max_rows pairs (32 MB as float64) is replaced by a fixed, seeded sample of max_rows of its sorted rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    p = np.asarray(pairs, dtype=np.uint64).reshape(-1, 2)
+    p = p[np.lexsort((p[:, 1], p[:, 0]))]
+    n = p.shape[0]
+    if n > max_rows:
+        p = p[np.sort(np.random.Generator(np.random.PCG64(20261015)).choice(n, max_rows, replace=False))]
+    out = {"pairs": p.astype(np.float64), "n_pairs": np.array([n], dtype=np.float64), "pairs_tested": np.array([int(tested)], dtype=np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": os.path.abspath(out_dir), "files": sorted(name + ".npy" for name in out), "pairs_sampled": bool(n > max_rows)}
+
+
 def secondary_measurement(torch, which, steps=60, warmup=10):
     """Secondary workloads beside the headline, same call and options, the last step's pair set and pairs_tested against the oracle and
     against the reference-compiled end result.  N = 1 only.
@@ -484,6 +500,8 @@ def main():
     ap.add_argument("--qpw", type=int, default=None, help="CD_OPT_QUERIES_PER_WAVE override")
     ap.add_argument("--no-order-hint", action="store_true", help="CD_OPT_ORDER_HINT 0 for the whole run: the timed region steps in the plain order (what a mesh that moves between "
                                                                   "steps gets); by default the line carries that measurement beside the headline (order_hint.ms_per_step_without)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (its pair list in canonical order, n_pairs, pairs_tested) "
+                                                                        "as DIR/<name>.npy in float64, rank 0 only: two builds compared output for output")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -937,6 +955,8 @@ def main():
                                      "pack / counts / exchange / cross run on a second stream beside tree / local (allgather counts from the step's start, "
                                      "cross from the end of the exchange to the end of the pass over the received queries)")
     if rank == 0:
+        if args.dump_outputs:
+            line["dumped_outputs"] = dump_outputs(args.dump_outputs, last_pairs, last_tested)
         print(json.dumps(line))
     if ms is not None:
         ms.close()
