@@ -175,6 +175,93 @@ __device__ __forceinline__ bool tri_contact_fast(const d3 P1, const d3 P2, const
     return c;
 }
 
+// ---------------------------------------------------------------- triangle-triangle distance (cd_find_proximity; not reference behaviour)
+// tri_distance(A, B) = 0 when the pair is IN CONTACT as the collision path decides it -- the FP64 boxes overlap strictly (box.cuh:40-43,
+// box_overlap) and tri_contact(A, B) holds -- else sqrt of the minimum squared distance over the feature pairs: every vertex against
+// the other triangle's face interior (pt_face2) and its three edges (pt_seg2), and every edge pair's interior critical point (seg_seg2).
+// Each term is |P - Q|^2 for two points P, Q that lie on the two triangles up to the rounding of forming them (a clamped or range-checked
+// parameter, never an extrapolation), so the result is never below the true distance by more than a few ulps of the coordinates
+// (DESIGN.md section 10).  A face whose barycentric denominator is not > 0 (zero area, collinear, a point) and an edge pair that is parallel
+// contribute nothing of their own: their edges' and vertices' terms remain, and those cover every pair of points of a segment or a point,
+// so a degenerate triangle gets the distance of the point set it is.  The one exception is a pair the collision path calls in contact:
+// the 17-axis test has only zero axes between two degenerate triangles (and no in-plane normal of a segment lying in a triangle's plane),
+// so such a pair can be apart and still reported by cd_find_collisions -- here it is at 0, as every pair in contact is.  Without the box
+// condition the test's verdict alone would put two points 5 apart at 0 although their boxes are disjoint.
+// The coordinates are translated to A's first vertex and scaled by a power of two (exact) so that products of squares neither overflow
+// nor underflow for |coordinates| anywhere in 1e-300 .. 1e300.  Fixed operation order, -ffp-contract=off, IEEE divide and sqrt: the
+// numpy restatement (tests/proximity_ref.py) reproduces it bit for bit.  Non-finite vertices: undefined.
+__device__ __forceinline__ double dmin2(double a, double b) { return b < a ? b : a; }
+__device__ __forceinline__ d3 dscale(const d3 a, double s) { return d3{a.x * s, a.y * s, a.z * s}; }
+// squared distance from p to the segment [a, b]
+__device__ __forceinline__ double pt_seg2(const d3 p, const d3 a, const d3 b)
+{
+    const d3 ab = sub(b, a), ap = sub(p, a);
+    const double den = dot(ab, ab);
+    double t = 0.0;
+    if (den > 0.0) { t = dot(ap, ab) / den; t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t); }
+    const d3 q = d3{a.x + t * ab.x, a.y + t * ab.y, a.z + t * ab.z};
+    const d3 d = sub(p, q);
+    return dot(d, d);
+}
+// squared distance from p to its projection onto the plane of (a, b, c) when that projection lies in the triangle, else +inf
+__device__ __forceinline__ double pt_face2(const d3 p, const d3 a, const d3 b, const d3 c)
+{
+    const d3 ab = sub(b, a), ac = sub(c, a), ap = sub(p, a);
+    const double d00 = dot(ab, ab), d01 = dot(ab, ac), d11 = dot(ac, ac), d20 = dot(ap, ab), d21 = dot(ap, ac);
+    const double den = d00 * d11 - d01 * d01;
+    if (!(den > 0.0)) return __builtin_inf();
+    const double v = (d11 * d20 - d01 * d21) / den, w = (d00 * d21 - d01 * d20) / den;
+    if (!(v >= 0.0 && w >= 0.0 && v + w <= 1.0)) return __builtin_inf();
+    const d3 q = d3{(a.x + v * ab.x) + w * ac.x, (a.y + v * ab.y) + w * ac.y, (a.z + v * ab.z) + w * ac.z};
+    const d3 d = sub(p, q);
+    return dot(d, d);
+}
+// squared distance between the segments [p1, q1], [p2, q2] at their interior critical point when it lies on both, else +inf
+// (the endpoints' terms are pt_seg2's)
+__device__ __forceinline__ double seg_seg2(const d3 p1, const d3 q1, const d3 p2, const d3 q2)
+{
+    const d3 d1 = sub(q1, p1), d2 = sub(q2, p2), r = sub(p1, p2);
+    const double a = dot(d1, d1), e = dot(d2, d2), b = dot(d1, d2), c = dot(d1, r), f = dot(d2, r);
+    const double den = a * e - b * b;
+    if (!(den > 0.0)) return __builtin_inf();
+    const double s = (b * f - c * e) / den, t = (a * f - b * c) / den;
+    if (!(s >= 0.0 && s <= 1.0 && t >= 0.0 && t <= 1.0)) return __builtin_inf();
+    const d3 P = d3{p1.x + s * d1.x, p1.y + s * d1.y, p1.z + s * d1.z}, Q = d3{p2.x + t * d2.x, p2.y + t * d2.y, p2.z + t * d2.z};
+    const d3 d = sub(P, Q);
+    return dot(d, d);
+}
+constexpr int TRI_DIST_EXP_MAX = 1000;                  // |scale exponent| clamp: 2^+-1000 are normal numbers
+__device__ __forceinline__ double dabs(double x) { return x < 0.0 ? -x : x; }
+__device__ __forceinline__ double dmax_abs3(double m, const d3 v) { m = fmax2(m, dabs(v.x)); m = fmax2(m, dabs(v.y)); return fmax2(m, dabs(v.z)); }
+__device__ __forceinline__ double pow2(int e) { return __longlong_as_double((long long)(1023 + e) << 52); }
+__device__ inline double tri_distance(const d3 P1, const d3 P2, const d3 P3, const d3 Q1, const d3 Q2, const d3 Q3)
+{
+    if (box_overlap(box_set(P1, P2, P3), box_set(Q1, Q2, Q3)) && tri_contact_fast(P1, P2, P3, Q1, Q2, Q3)) return 0.0;   // in contact (collision.cuh:31-39)
+    d3 p2 = sub(P2, P1), p3 = sub(P3, P1), q1 = sub(Q1, P1), q2 = sub(Q2, P1), q3 = sub(Q3, P1);
+    double m = 0.0;
+    m = dmax_abs3(m, p2); m = dmax_abs3(m, p3); m = dmax_abs3(m, q1); m = dmax_abs3(m, q2); m = dmax_abs3(m, q3);
+    if (!(m > 0.0)) return 0.0;                                           // (six coincident points: tri_contact holds already)
+    int ex = (int)((__double_as_longlong(m) >> 52) & 0x7ff) - 1022;     // m = f 2^ex, f in [0.5, 1) (frexp; a subnormal m is clamped below)
+    ex = ex < -TRI_DIST_EXP_MAX ? -TRI_DIST_EXP_MAX : (ex > TRI_DIST_EXP_MAX ? TRI_DIST_EXP_MAX : ex);
+    const double sc = pow2(-ex);
+    const d3 p1 = d3{0.0, 0.0, 0.0};
+    p2 = dscale(p2, sc); p3 = dscale(p3, sc); q1 = dscale(q1, sc); q2 = dscale(q2, sc); q3 = dscale(q3, sc);
+    // the 33 terms, a vertex / edge index of each triangle at a time (a rolled loop: unrolled, the compiler keeps every term's operands
+    // live at once: 250 VGPRs against 188); the minimum of exact values does not depend on the order they are taken in
+    double best = __builtin_inf();
+#pragma unroll 1
+    for (int i = 0; i < 3; ++i) {
+        const d3 pi = i == 0 ? p1 : (i == 1 ? p2 : p3), pn = i == 0 ? p2 : (i == 1 ? p3 : p1);     // vertex i of A, edge (i, i+1) of A
+        const d3 qi = i == 0 ? q1 : (i == 1 ? q2 : q3);
+        best = dmin2(best, pt_face2(pi, q1, q2, q3));
+        best = dmin2(best, pt_face2(qi, p1, p2, p3));
+        best = dmin2(best, pt_seg2(pi, q1, q2)); best = dmin2(best, pt_seg2(pi, q2, q3)); best = dmin2(best, pt_seg2(pi, q3, q1));
+        best = dmin2(best, pt_seg2(qi, p1, p2)); best = dmin2(best, pt_seg2(qi, p2, p3)); best = dmin2(best, pt_seg2(qi, p3, p1));
+        best = dmin2(best, seg_seg2(pi, pn, q1, q2)); best = dmin2(best, seg_seg2(pi, pn, q2, q3)); best = dmin2(best, seg_seg2(pi, pn, q3, q1));
+    }
+    return __builtin_sqrt(best) * pow2(ex);
+}
+
 __device__ __forceinline__ d3 load_vertex(const double *__restrict__ verts, uint32_t i)
 {
     const double *p = verts + 3 * (size_t)i;

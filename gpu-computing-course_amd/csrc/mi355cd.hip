@@ -7,6 +7,7 @@
 #include "cd_build.h"
 #include "cd_traverse.h"
 #include "cd_post.h"
+#include "cd_proximity.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -153,6 +154,10 @@ struct cd_ctx {
     int wall_clock_khz = 0;                 // hipDeviceAttributeWallClockRate: ticks of s_memrealtime per millisecond
     double root_box_host[6] = {};           // AABB of the whole tree, fetched together with other read-backs
     bool root_box_valid = false;
+    // self-proximity (cd_find_proximity, cd_proximity.h): buffers of its own -- nothing the collision path keeps is touched
+    ProxState *d_px_state = nullptr; ProxState *h_px_state = nullptr;
+    uint2 *d_px_cand = nullptr; uint64_t px_shard_cap = 0;
+    uint32_t *d_px_pairs = nullptr; double *d_px_dists = nullptr; uint64_t px_pairs_cap = 0;
 };
 
 namespace {
@@ -179,6 +184,8 @@ void free_all(cd_ctx *c)
     }
     for (int i = 0; i < 2; ++i) { hipFree(c->pp_keys[i]); hipFree(c->pp_vals[i]); }
     hipFree(c->pp_flags); hipFree(c->pp_os);
+    hipFree(c->d_px_state); hipFree(c->d_px_cand); hipFree(c->d_px_pairs); hipFree(c->d_px_dists);
+    if (c->h_px_state) hipHostFree(c->h_px_state);
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -1729,6 +1736,8 @@ int cd_debug_option(cd_ctx *c, int key, int64_t value, int64_t *out)
     case CD_DBG_GET_POLLED_STEPS:   if (!out) return CD_ERR_ARG; *out = c->polled_steps; return CD_OK;
     case CD_DBG_GET_POLL_FB_WHY:    if (!out) return CD_ERR_ARG; *out = (int64_t)c->poll_fb_busy | ((int64_t)c->poll_fb_late_word << 16) | ((int64_t)c->poll_fb_lost << 32); return CD_OK;
     case CD_DBG_GET_POLL_MAX_WAIT_US: if (!out) return CD_ERR_ARG; *out = c->poll_max_wait_us; return CD_OK;
+    case CD_DBG_GET_GRAPH_CAPTURES: if (!out) return CD_ERR_ARG; *out = (int64_t)c->graph_captures; return CD_OK;
+    case CD_DBG_GET_GRAPH_REPLAYS:  if (!out) return CD_ERR_ARG; *out = (int64_t)c->graph_replays; return CD_OK;
     case CD_DBG_GET_TREE_WAS_FUSED: if (!out) return CD_ERR_ARG; *out = c->last_tree_fused ? 1 : 0; return CD_OK;
     case CD_DBG_GET_SORT_FORM:   if (out) *out = c->sort_mode; return CD_OK;
     case CD_DBG_GET_ORDER_STATE: {          // the order hint as it stands: 0 none built, 1 a permutation of the groups that differs from the plain order, 2 the plain order itself, -1 NOT a permutation (a bug)
@@ -1793,6 +1802,144 @@ int cd_find_collisions_queries(cd_ctx *c, const void *d_queries, uint64_t nq, ui
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if (nq == 0) { if (n_pairs) *n_pairs = 0; return CD_OK; }
     return run_traversal(c, c->tb[0], d_queries, nq, pairs, cap_pairs, n_pairs);
+}
+
+// ---- self-proximity (cd_proximity.h) ------------------------------------------------------------------------------------------------
+// Own buffers (state, candidates, pairs, distances): the collision path's counters, pair list, statistics and captured step stay as they were.
+static bool prox_dist_ok(double dist) { return dist >= 0.0 && dist <= 1.7976931348623157e308; }      // (NaN fails both)
+static int prox_buffers(cd_ctx *c, uint64_t cap_pairs)
+{
+    if (!c->d_px_state) {
+        HIPCHK(hipMalloc(&c->d_px_state, sizeof(ProxState)));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_px_state), sizeof(ProxState), hipHostMallocDefault));
+    }
+    if (!c->d_px_cand) {                                                    // 16 candidates a triangle to start with; grown on overflow
+        const uint64_t per = std::max<uint64_t>(4096, (16ull * c->nt + NSHARD - 1) / NSHARD);
+        HIPCHK(hipMalloc(&c->d_px_cand, sizeof(uint2) * per * NSHARD));
+        c->px_shard_cap = per;
+    }
+    const uint64_t want = cap_pairs > 0 ? cap_pairs : 1;
+    if (want > c->px_pairs_cap) {
+        hipFree(c->d_px_pairs); hipFree(c->d_px_dists); c->d_px_pairs = nullptr; c->d_px_dists = nullptr; c->px_pairs_cap = 0;
+        HIPCHK(hipMalloc(&c->d_px_pairs, sizeof(uint32_t) * 2 * want));
+        HIPCHK(hipMalloc(&c->d_px_dists, sizeof(double) * want));
+        c->px_pairs_cap = want;
+    }
+    return CD_OK;
+}
+// the two kernels of one pass and the read-back of the counters (no synchronisation)
+static int prox_enqueue(cd_ctx *c, double dist, uint64_t cap_pairs)
+{
+    hipStream_t s = c->stream;
+    const uint32_t n = c->nt;
+    HIPCHK(hipMemsetAsync(c->d_px_state, 0, sizeof(ProxState), s));
+    k_prox_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(c->d_recs32, c->d_leaf, c->d_verts, c->d_boxes, (int)n, dist,
+                                                                             c->d_os_ticket + 8, c->d_px_state, c->d_px_cand, c->px_shard_cap);
+    const uint32_t xb = std::max<uint32_t>(1u, std::min<uint32_t>(64u, cdiv(n, 4096)));   // workgroups per shard
+    k_prox_exact<<<dim3(xb, NSHARD), PROX_EXACT_THREADS, 0, s>>>(c->d_px_cand, c->px_shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, dist,
+                                                                 c->d_px_state, c->d_px_pairs, c->d_px_dists, cap_pairs);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_px_state, c->d_px_state, sizeof(ProxState), hipMemcpyDeviceToHost, s));
+    return CD_OK;
+}
+// after the synchronisation: 1 = a shard overflowed (the buffer has been grown: enqueue again), 0 = done
+static int prox_overflowed(cd_ctx *c, int &rc)
+{
+    uint64_t mx = 0;
+    for (int i = 0; i < NSHARD; ++i) mx = std::max<uint64_t>(mx, c->h_px_state->shard[i * PROX_SHARD_STRIDE]);
+    rc = CD_OK;
+    if (mx <= c->px_shard_cap) return 0;
+    hipFree(c->d_px_cand); c->d_px_cand = nullptr;
+    const uint64_t per = mx + mx / 4 + 1024;
+    const hipError_t e = hipMalloc(&c->d_px_cand, sizeof(uint2) * per * NSHARD);
+    if (e != hipSuccess) { c->px_shard_cap = 0; rc = -(int)e; return 0; }
+    c->px_shard_cap = per;
+    return 1;
+}
+static int prox_results(cd_ctx *c, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
+{
+    const uint64_t np = c->h_px_state->n_pairs, take = std::min(np, cap_pairs);
+    if (take) {
+        HIPCHK(hipMemcpy(pairs, c->d_px_pairs, sizeof(uint32_t) * 2 * take, hipMemcpyDeviceToHost));
+        if (dists) HIPCHK(hipMemcpy(dists, c->d_px_dists, sizeof(double) * take, hipMemcpyDeviceToHost));
+    }
+    if (n_pairs) *n_pairs = np;
+    if (n_tested) *n_tested = c->h_px_state->n_tested;
+    return np > cap_pairs ? CD_OVERFLOW : CD_OK;
+}
+static int prox_pass(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
+{
+    for (;;) {
+        int rc = prox_enqueue(c, dist, cap_pairs);
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (!prox_overflowed(c, rc)) { if (rc) return rc; break; }
+    }
+    return prox_results(c, pairs, dists, cap_pairs, n_pairs, n_tested);
+}
+static int prox_args(cd_ctx *c, double dist, uint32_t *pairs, uint64_t cap_pairs)
+{
+    if (!c || !prox_dist_ok(dist) || (cap_pairs && !pairs)) return CD_ERR_ARG;
+    return CD_OK;
+}
+int cd_find_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
+{
+    int rc = prox_args(c, dist, pairs, cap_pairs);
+    if (rc) return rc;
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if ((rc = prox_buffers(c, cap_pairs))) return rc;
+    return prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
+}
+static int self_proximity_impl(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested, int redo)
+{
+    int rc;
+    {
+        Prezeroed fused(c);                                                // cd_build_tree's pipeline, then the proximity pass behind it: one synchronisation
+        rc = enqueue_morton_sort(c, !fused_build_next(c));
+        if (!rc) rc = enqueue_tree(c);
+        if (!rc) rc = prox_enqueue(c, dist, cap_pairs);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(c->sort_flags, c->d_os_ticket + 8, sizeof c->sort_flags, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->root_box_host, c->d_boxes, sizeof(double) * 6, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    rc = judge_sort_flags(c);
+    if (rc == SORT_REDO) return redo < SORT_REDO_MAX ? self_proximity_impl(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested, redo + 1) : CD_ERR_SORT;
+    if (rc) return rc;
+    c->root_box_valid = true;
+    c->stage = ST_REFIT;
+    if (prox_overflowed(c, rc)) return prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
+    if (rc) return rc;
+    return prox_results(c, pairs, dists, cap_pairs, n_pairs, n_tested);
+}
+int cd_self_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
+{
+    int rc = prox_args(c, dist, pairs, cap_pairs);
+    if (rc) return rc;
+    if ((rc = prox_buffers(c, cap_pairs))) return rc;
+    sort_retry_tick(c);
+    const cd_stats keep = c->stats;                                        // (the build inside does not count as a stage of the collision path)
+    rc = self_proximity_impl(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested, 0);
+    c->stats = keep;
+    return rc;
+}
+int cd_tri_distance_points(const double *tri, uint64_t n, double *dist)
+{
+    if (!tri || !dist) return CD_ERR_ARG;
+    if (n == 0) return CD_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
+    double *d_t = nullptr, *d_o = nullptr;
+    hipError_t e = hipMalloc(&d_t, sizeof(double) * 18 * n);
+    if (e == hipSuccess) e = hipMalloc(&d_o, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMemcpy(d_t, tri, sizeof(double) * 18 * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        k_tri_distance_points<<<cdiv(n, 256) < 4096u ? cdiv(n, 256) : 4096u, 256>>>(d_t, n, d_o);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(dist, d_o, sizeof(double) * n, hipMemcpyDeviceToHost);
+    }
+    hipFree(d_t); hipFree(d_o);
+    return e == hipSuccess ? CD_OK : -(int)e;
 }
 
 }  // extern "C"

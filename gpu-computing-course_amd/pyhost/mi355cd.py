@@ -29,6 +29,7 @@ CD_DBG_GET_POLL_FB_WHY, CD_DBG_GET_POLL_MAX_WAIT_US = 16, 17
 CD_DBG_REPORT_COPIES = 6
 CD_DBG_STORE_QBOX = 9
 CD_DBG_BIG_OFFSETS = 18
+CD_DBG_GET_GRAPH_CAPTURES, CD_DBG_GET_GRAPH_REPLAYS = 19, 20
 
 QUERY_DTYPE = np.dtype([("v", "<f8", (9,)), ("id", "<u4"), ("vidx", "<u4", (3,))])
 assert QUERY_DTYPE.itemsize == 88
@@ -66,6 +67,7 @@ EXPORTS = [
     "cd_set_option", "cd_set_vertex_id_base", "cd_root_box", "cd_pack_queries", "cd_find_collisions_queries", "cd_version",
     "cd_debug_option", "cd_debug_hint", "cd_debug_hint_set", "cd_morton3d_points", "cd_morton3d_points_layout", "cd_expand64_values", "cd_box_pairs", "cd_tri_contact_points", "cd_alloc_host_pairs", "cd_free_host_pairs",
     "cd_multi_unique_id", "cd_multi_create", "cd_multi_create_from_comm", "cd_multi_destroy", "cd_multi_set_flags", "cd_multi_step",
+    "cd_find_proximity", "cd_self_proximity", "cd_tri_distance_points",
 ]
 
 _lib = None
@@ -134,6 +136,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_debug_option.argtypes = [vp, C.c_int, C.c_int64, C.POINTER(C.c_int64)]
     lib.cd_box_pairs.argtypes = [vp, vp, C.c_uint64, vp, vp]
     lib.cd_tri_contact_points.argtypes = [vp, C.c_uint64, vp]
+    lib.cd_find_proximity.argtypes = [vp, C.c_double, vp, vp, C.c_uint64, u64p, u64p]
+    lib.cd_self_proximity.argtypes = [vp, C.c_double, vp, vp, C.c_uint64, u64p, u64p]
+    lib.cd_tri_distance_points.argtypes = [vp, C.c_uint64, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -280,6 +285,25 @@ class CollisionDetector:
         if buf is None:
             return np.zeros((0, 2), dtype=np.uint32), n.value, rc
         return (buf[:got].copy() if copy else buf[:got]), n.value, rc
+
+    def _proximity_call(self, fn, name, dist, cap):
+        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        dists = np.empty(max(cap, 1), dtype=np.float64)
+        n, tested = C.c_uint64(0), C.c_uint64(0)
+        rc = fn(self._ctx, float(dist), _ptr(pairs) if cap else None, _ptr(dists), cap, C.byref(n), C.byref(tested))
+        self._chk(name, rc, allow=(CD_OK, CD_OVERFLOW))
+        self.proximity_tested = tested.value
+        got = min(n.value, cap)
+        return pairs[:got].copy(), dists[:got].copy(), n.value, rc
+
+    def find_proximity(self, dist: float, cap: int = 1 << 20):
+        """cd_find_proximity on the tree that is there: (pairs[n, 2] (smaller ID, larger ID), dists[n], n, rc); n may exceed cap
+        (rc = CD_OVERFLOW, the first cap pairs are returned).  self.proximity_tested: exact distance evaluations made."""
+        return self._proximity_call(self.lib.cd_find_proximity, "cd_find_proximity", dist, cap)
+
+    def self_proximity(self, dist: float, cap: int = 1 << 20):
+        """cd_self_proximity: build the tree, then find_proximity, with one host synchronisation."""
+        return self._proximity_call(self.lib.cd_self_proximity, "cd_self_proximity", dist, cap)
 
     def find_collisions(self, cap: int = 1 << 20):
         return self._pairs_call(self.lib.cd_find_collisions, "cd_find_collisions", cap)
@@ -484,6 +508,17 @@ def tri_contact_points(tri) -> np.ndarray:
     rc = load_library().cd_tri_contact_points(_ptr(t), t.shape[0], _ptr(out))
     if rc != CD_OK:
         raise CdError("cd_tri_contact_points", rc)
+    return out
+
+
+def tri_distance_points(tri) -> np.ndarray:
+    """tri_distance (0 for a pair in contact, else the minimum over the 15 feature pairs) on explicit vertex positions [n, 6, 3],
+    on the device (cd_tri_distance_points)."""
+    t = np.ascontiguousarray(tri, dtype=np.float64).reshape(-1, 18)
+    out = np.zeros(t.shape[0], dtype=np.float64)
+    rc = load_library().cd_tri_distance_points(_ptr(t), t.shape[0], _ptr(out))
+    if rc != CD_OK:
+        raise CdError("cd_tri_distance_points", rc)
     return out
 
 

@@ -266,6 +266,8 @@ enum {
                                      /* the word came with the synchronise (late in flight), 32..47 the word was not there after the drain (LOST: must stay 0)                          */
     CD_DBG_GET_POLL_MAX_WAIT_US = 17, /* ... the longest polled wait that ended in the word (sampled every 16th step), microseconds                                                   */
     CD_DBG_BIG_OFFSETS        = 18,  /* 1: the half traversal runs the instance that forms 64-bit record addresses (what trees of more than 2^27 leaves get) on a tree of any size (tests)  */
+    CD_DBG_GET_GRAPH_CAPTURES = 19,  /* ... CD_OPT_GRAPH: steps captured as a graph on this context so far (a captured step kept across other calls: no new capture)    */
+    CD_DBG_GET_GRAPH_REPLAYS  = 20,  /* ... CD_OPT_GRAPH: graph launches of captured steps so far                                              */
     CD_DBG_GET_TREE_WAS_FUSED = 14,  /* 1: the tree that is there was made by the one-pass build                                              */
     CD_DBG_GET_ORDER_STATE    = 15   /* the order hint (CD_OPT_ORDER_HINT) as it stands: 0 none built yet; 1 a permutation of the groups of 64 leaves that differs from the plain order;    */
                                      /* 2 the plain order itself; -1 not a permutation (must never be)                                                                                        */
@@ -379,6 +381,33 @@ int cd_multi_set_flags(cd_multi *m, int flags);
 /* One step.  pairs: local pairs first, then the cross pairs this rank owns (output format of cd_find_collisions);
  * returns CD_OVERFLOW when they do not fit cap_pairs (*n_pairs holds the true count).  info may be NULL. */
 int cd_multi_step(cd_multi *m, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, cd_multi_info *info);
+
+/* ---- self-proximity (not reference behaviour) ----
+ * tri_distance(A, B): 0 when the pair is in contact as cd_find_collisions decides it -- the FP64 boxes overlap strictly (box.cuh:40-43)
+ * and tri_contact(A, B) holds (the 17-axis test of cd_tri_contact_points) -- so a pair the library calls in contact is always at
+ * distance 0; otherwise the square root of the minimum squared distance over the 15 feature pairs (6 vertex-triangle, 9 edge-edge),
+ * evaluated in FP64 with a fixed operation order (csrc/cd_math.h).  A degenerate triangle (zero area, collinear, a single point) has
+ * the distance of the point set it is, except in a pair the library calls in contact: between two degenerate triangles (or a segment
+ * lying in a triangle's plane) the 17-axis test can say "contact" for triangles apart, and when their boxes also overlap strictly
+ * cd_find_collisions reports them -- such a pair is at 0.  Finite inputs never give NaN.  Non-finite vertices: the result is undefined.
+ *
+ * Every unordered pair of triangles (a, b) of this context with no shared vertex index (neighborCount < 1, as collision.cuh:38) and
+ * tri_distance(a, b) <= dist.  pairs: interleaved (smaller ID, larger ID), unordered, as cd_find_collisions; tri_distance is evaluated
+ * with the smaller ID's triangle as A (equal IDs: the smaller face index).  dists (may be NULL): dists[k] = tri_distance of pairs[k].
+ * n_tested (may be NULL): exact distance evaluations made.  Needs a tree built from the current vertices (CD_ERR_ORDER otherwise,
+ * including after cd_update_vertices without a rebuild).  dist must be finite and >= 0 (CD_ERR_ARG otherwise).  Returns CD_OVERFLOW
+ * with the true *n_pairs when it exceeds cap_pairs; nothing is written past cap_pairs (pairs may be NULL with cap_pairs 0).
+ * The result depends on the mesh and dist only: not on the Morton frame, CD_OPT_TRAVERSAL, CD_OPT_CELL_TABLE or how the tree was
+ * built.  These calls leave cd_stats, the last collision pair list (cd_sorted_pairs, cd_collision_triangles) and a captured
+ * CD_OPT_GRAPH step as they were; they keep device buffers of their own. */
+int cd_find_proximity(cd_ctx *ctx, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs,
+                      uint64_t *n_pairs, uint64_t *n_tested);
+/* cd_build_tree + cd_find_proximity, queued back to back, one host synchronisation. */
+int cd_self_proximity(cd_ctx *ctx, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs,
+                      uint64_t *n_pairs, uint64_t *n_tested);
+/* tri_distance on explicit positions (host pointers; no context): tri is n x 6 x 3 doubles (A's three vertices, then B's), as
+ * cd_tri_contact_points.  The pin of the device function. */
+int cd_tri_distance_points(const double *tri, uint64_t n, double *dist);
 
 /* Library / build identification: "mi355cd <version> gfx950". */
 const char *cd_version(void);
