@@ -8,6 +8,7 @@
 #include "cd_traverse.h"
 #include "cd_post.h"
 #include "cd_proximity.h"
+#include "cd_ccd.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -158,6 +159,11 @@ struct cd_ctx {
     ProxState *d_px_state = nullptr; ProxState *h_px_state = nullptr;
     uint2 *d_px_cand = nullptr; uint64_t px_shard_cap = 0;
     uint32_t *d_px_pairs = nullptr; double *d_px_dists = nullptr; uint64_t px_pairs_cap = 0;
+    // continuous collision queries (cd_find_ccd, cd_ccd.h): buffers of their own, allocated on first use
+    CcdState *d_cc_state = nullptr; CcdState *h_cc_state = nullptr;
+    uint2 *d_cc_cand = nullptr; uint64_t cc_shard_cap = 0;
+    uint32_t *d_cc_pairs = nullptr; double *d_cc_toi = nullptr, *d_cc_dists = nullptr; uint64_t cc_pairs_cap = 0;
+    double *d_cc_x1 = nullptr; NodeRec32 *d_cc_recs = nullptr; int32_t *d_cc_up = nullptr; uint32_t *d_cc_arrive = nullptr;
 };
 
 namespace {
@@ -186,6 +192,9 @@ void free_all(cd_ctx *c)
     hipFree(c->pp_flags); hipFree(c->pp_os);
     hipFree(c->d_px_state); hipFree(c->d_px_cand); hipFree(c->d_px_pairs); hipFree(c->d_px_dists);
     if (c->h_px_state) hipHostFree(c->h_px_state);
+    hipFree(c->d_cc_state); hipFree(c->d_cc_cand); hipFree(c->d_cc_pairs); hipFree(c->d_cc_toi); hipFree(c->d_cc_dists);
+    hipFree(c->d_cc_x1); hipFree(c->d_cc_recs); hipFree(c->d_cc_up); hipFree(c->d_cc_arrive);
+    if (c->h_cc_state) hipHostFree(c->h_cc_state);
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -1942,6 +1951,174 @@ int cd_tri_distance_points(const double *tri, uint64_t n, double *dist)
     return e == hipSuccess ? CD_OK : -(int)e;
 }
 
+
+// ---- continuous collision queries (cd_ccd.h) ------------------------------------------------------------------------------------
+// Own buffers (x1, swept records, parent links, arrival counters, state, candidates, pairs, times, distances): the context's vertices,
+// the collision path's counters, pair list, statistics and captured step, and the proximity buffers stay as they were.
+static bool ccd_dist_ok(double dist) { return dist > 0.0 && dist <= 1.7976931348623157e308; }       // (NaN fails both)
+static int ccd_buffers(cd_ctx *c, uint64_t cap_pairs)
+{
+    if (!c->d_cc_state) {
+        HIPCHK(hipMalloc(&c->d_cc_state, sizeof(CcdState)));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_cc_state), sizeof(CcdState), hipHostMallocDefault));
+    }
+    if (!c->d_cc_x1) {
+        HIPCHK(hipMalloc(&c->d_cc_x1, sizeof(double) * 3 * (size_t)std::max<uint32_t>(c->nv, 1u)));
+        HIPCHK(hipMalloc(&c->d_cc_recs, sizeof(NodeRec32) * (size_t)std::max<uint32_t>(c->nt, 1u)));
+        HIPCHK(hipMalloc(&c->d_cc_up, sizeof(int32_t) * 2 * (size_t)std::max<uint32_t>(c->nt, 1u)));
+        HIPCHK(hipMalloc(&c->d_cc_arrive, sizeof(uint32_t) * (size_t)std::max<uint32_t>(c->nt, 1u)));
+    }
+    if (!c->d_cc_cand) {                                                    // 16 candidates a triangle to start with; grown on overflow
+        const uint64_t per = std::max<uint64_t>(4096, (16ull * c->nt + NSHARD - 1) / NSHARD);
+        HIPCHK(hipMalloc(&c->d_cc_cand, sizeof(uint2) * per * NSHARD));
+        c->cc_shard_cap = per;
+    }
+    const uint64_t want = cap_pairs > 0 ? cap_pairs : 1;
+    if (want > c->cc_pairs_cap) {
+        hipFree(c->d_cc_pairs); hipFree(c->d_cc_toi); hipFree(c->d_cc_dists);
+        c->d_cc_pairs = nullptr; c->d_cc_toi = nullptr; c->d_cc_dists = nullptr; c->cc_pairs_cap = 0;
+        HIPCHK(hipMalloc(&c->d_cc_pairs, sizeof(uint32_t) * 2 * want));
+        HIPCHK(hipMalloc(&c->d_cc_toi, sizeof(double) * want));
+        HIPCHK(hipMalloc(&c->d_cc_dists, sizeof(double) * want));
+        c->cc_pairs_cap = want;
+    }
+    return CD_OK;
+}
+// x1 upload, swept refit (links, then the climb), descent, exact pass and the read-back of the counters (no synchronisation)
+static int ccd_enqueue(cd_ctx *c, const double *verts_end /* NULL: a redo, x1 is there */, double dist, uint64_t cap_pairs)
+{
+    hipStream_t s = c->stream;
+    const uint32_t n = c->nt;
+    if (verts_end) HIPCHK(hipMemcpyAsync(c->d_cc_x1, verts_end, sizeof(double) * 3 * (size_t)c->nv, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(c->d_cc_state, 0, sizeof(CcdState), s));
+    if (n >= 2) {
+        HIPCHK(hipMemsetAsync(c->d_cc_up, 0xff, sizeof(int32_t) * 2 * (size_t)n, s));   // -1: no parent (the root; and any link a broken tree lacks)
+        k_ccd_links<<<cdiv(n - 1, CCD_THREADS), CCD_THREADS, 0, s>>>(c->d_recs32, (int)n, c->d_os_ticket + 8, c->d_cc_recs, c->d_cc_up, c->d_cc_arrive);
+        k_ccd_refit<<<cdiv(n, CCD_THREADS), CCD_THREADS, 0, s>>>(c->d_leaf, c->d_verts, c->d_cc_x1, (int)n, c->d_os_ticket + 8, c->d_cc_up, c->d_cc_arrive,
+                                                                 c->d_cc_recs, c->d_cc_state);
+        k_ccd_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(c->d_cc_recs, c->d_leaf, c->d_verts, c->d_cc_x1, (int)n, dist,
+                                                                               c->d_os_ticket + 8, c->d_cc_state, c->d_cc_cand, c->cc_shard_cap);
+        const uint32_t xb = std::max<uint32_t>(1u, std::min<uint32_t>(64u, cdiv(n, 4096)));   // workgroups per shard
+        k_ccd_exact<<<dim3(xb, NSHARD), PROX_EXACT_THREADS, 0, s>>>(c->d_cc_cand, c->cc_shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, c->d_cc_x1, dist,
+                                                                    c->d_cc_state, c->d_cc_pairs, c->d_cc_toi, c->d_cc_dists, cap_pairs);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_cc_state, c->d_cc_state, sizeof(CcdState), hipMemcpyDeviceToHost, s));
+    return CD_OK;
+}
+// after the synchronisation: 1 = a shard overflowed (the buffer has been grown: enqueue again), 0 = done
+static int ccd_overflowed(cd_ctx *c, int &rc)
+{
+    uint64_t mx = 0;
+    for (int i = 0; i < NSHARD; ++i) mx = std::max<uint64_t>(mx, c->h_cc_state->shard[i * PROX_SHARD_STRIDE]);
+    rc = CD_OK;
+    if (mx <= c->cc_shard_cap) return 0;
+    hipFree(c->d_cc_cand); c->d_cc_cand = nullptr;
+    const uint64_t per = mx + mx / 4 + 1024;
+    const hipError_t e = hipMalloc(&c->d_cc_cand, sizeof(uint2) * per * NSHARD);
+    if (e != hipSuccess) { c->cc_shard_cap = 0; rc = -(int)e; return 0; }
+    c->cc_shard_cap = per;
+    return 1;
+}
+static int ccd_results(cd_ctx *c, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info)
+{
+    const CcdState *h = c->h_cc_state;
+    const uint64_t np = h->n_pairs, take = std::min(np, cap_pairs);
+    if (take) {
+        HIPCHK(hipMemcpy(pairs, c->d_cc_pairs, sizeof(uint32_t) * 2 * take, hipMemcpyDeviceToHost));
+        if (toi) HIPCHK(hipMemcpy(toi, c->d_cc_toi, sizeof(double) * take, hipMemcpyDeviceToHost));
+        if (dists) HIPCHK(hipMemcpy(dists, c->d_cc_dists, sizeof(double) * take, hipMemcpyDeviceToHost));
+    }
+    if (n_pairs) *n_pairs = np;
+    if (info) {
+        uint64_t cand = 0;
+        for (int i = 0; i < NSHARD; ++i) cand += h->shard[i * PROX_SHARD_STRIDE];
+        info->n_candidates = cand; info->n_tested = h->n_tested; info->n_evals = h->n_evals; info->n_unresolved = h->n_unresolved;
+    }
+    return np > cap_pairs ? CD_OVERFLOW : CD_OK;
+}
+// after a pass that is already enqueued and synchronised: redo it while a shard overflows, then the results
+static int ccd_finish(cd_ctx *c, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info)
+{
+    int rc;
+    while (ccd_overflowed(c, rc)) {
+        if ((rc = ccd_enqueue(c, nullptr, dist, cap_pairs))) return rc;
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    if (rc) return rc;
+    return ccd_results(c, pairs, toi, dists, cap_pairs, n_pairs, info);
+}
+static int ccd_args(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, uint64_t cap_pairs)
+{
+    if (!c || !verts_end || !ccd_dist_ok(dist) || (cap_pairs && !pairs)) return CD_ERR_ARG;
+    return CD_OK;
+}
+int cd_find_ccd(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
+                cd_ccd_info *info)
+{
+    int rc = ccd_args(c, verts_end, dist, pairs, cap_pairs);
+    if (rc) return rc;
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if ((rc = ccd_buffers(c, cap_pairs))) return rc;
+    if ((rc = ccd_enqueue(c, verts_end, dist, cap_pairs))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ccd_finish(c, dist, pairs, toi, dists, cap_pairs, n_pairs, info);
+}
+static int self_ccd_impl(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
+                         cd_ccd_info *info, int redo)
+{
+    int rc;
+    {
+        Prezeroed fused(c);                                                // cd_build_tree's pipeline, then the CCD pass behind it: one synchronisation
+        rc = enqueue_morton_sort(c, !fused_build_next(c));
+        if (!rc) rc = enqueue_tree(c);
+        if (!rc) rc = ccd_enqueue(c, verts_end, dist, cap_pairs);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(c->sort_flags, c->d_os_ticket + 8, sizeof c->sort_flags, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->root_box_host, c->d_boxes, sizeof(double) * 6, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    rc = judge_sort_flags(c);
+    if (rc == SORT_REDO) return redo < SORT_REDO_MAX ? self_ccd_impl(c, verts_end, dist, pairs, toi, dists, cap_pairs, n_pairs, info, redo + 1) : CD_ERR_SORT;
+    if (rc) return rc;
+    c->root_box_valid = true;
+    c->stage = ST_REFIT;
+    return ccd_finish(c, dist, pairs, toi, dists, cap_pairs, n_pairs, info);
+}
+int cd_self_ccd(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
+                cd_ccd_info *info)
+{
+    int rc = ccd_args(c, verts_end, dist, pairs, cap_pairs);
+    if (rc) return rc;
+    if ((rc = ccd_buffers(c, cap_pairs))) return rc;
+    sort_retry_tick(c);
+    const cd_stats keep = c->stats;                                        // (the build inside does not count as a stage of the collision path)
+    rc = self_ccd_impl(c, verts_end, dist, pairs, toi, dists, cap_pairs, n_pairs, info, 0);
+    c->stats = keep;
+    return rc;
+}
+int cd_ccd_points(const double *tri, uint64_t n, double dist, double *toi, double *dists, uint32_t *evals)
+{
+    if (!tri || !toi || !dists || !evals || !ccd_dist_ok(dist)) return CD_ERR_ARG;
+    if (n == 0) return CD_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
+    double *d_t = nullptr, *d_toi = nullptr, *d_d = nullptr; uint32_t *d_e = nullptr;
+    hipError_t e = hipMalloc(&d_t, sizeof(double) * 36 * n);
+    if (e == hipSuccess) e = hipMalloc(&d_toi, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMalloc(&d_d, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMalloc(&d_e, sizeof(uint32_t) * n);
+    if (e == hipSuccess) e = hipMemcpy(d_t, tri, sizeof(double) * 36 * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        k_ccd_points<<<cdiv(n, CCD_THREADS) < 4096u ? cdiv(n, CCD_THREADS) : 4096u, CCD_THREADS>>>(d_t, n, dist, d_toi, d_d, d_e);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(toi, d_toi, sizeof(double) * n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(dists, d_d, sizeof(double) * n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(evals, d_e, sizeof(uint32_t) * n, hipMemcpyDeviceToHost);
+    }
+    hipFree(d_t); hipFree(d_toi); hipFree(d_d); hipFree(d_e);
+    return e == hipSuccess ? CD_OK : -(int)e;
+}
 }  // extern "C"
 
 #include "cd_multi.h"

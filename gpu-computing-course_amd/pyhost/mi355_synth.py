@@ -154,6 +154,23 @@ def cloth_pair(quads: int = 500, x_offset: float = 0.0, round_f32: bool = True):
     return verts, np.ascontiguousarray(vidx)
 
 
+def cloth_motion(verts: np.ndarray, approach: float = 0.5, wave: float = 0.5, throw: bool = False, quads: int = 500, seed: int = 7):
+    """End positions x1 for cloth_pair(quads)'s vertices `verts` (continuous collision queries): the two sheets approach each other
+    in y by `approach` quad edges each, plus a smooth wave of amplitude `wave` quad edges in y; throw=True also sends one vertex of
+    sheet A across the whole mesh.  approach = wave = 0 gives x1 == x0.  Returns f64[V, 3]."""
+    v = np.asarray(verts, dtype=np.float64)
+    edge = 2.88 / quads
+    half = v.shape[0] // 2                                               # sheet A's vertices, then sheet B's
+    x1 = v.copy()
+    sign = np.where(np.arange(v.shape[0]) < half, 1.0, -1.0)
+    x1[:, 1] += sign * approach * edge
+    x1[:, 1] += wave * edge * np.sin(4.0 * v[:, 0] + 1.0) * np.cos(3.0 * v[:, 2])
+    if throw:
+        k = int(np.random.default_rng(seed).integers(0, half))
+        x1[k] = v[k] + np.array([-2.5, 0.3, 2.0]) * np.sign(1.5 - v[k, 0])
+    return x1
+
+
 def cloth_shard(rank: int, quads: int = 500, overlap: float = 0.10):
     """BASELINE config 4: rank r owns a copy of the config-3 geometry shifted along x so that
     neighbouring copies overlap by `overlap` of their width.  Vertex indices and triangle IDs are

@@ -51,6 +51,10 @@ CD_MULTI_INJECT_ALLOC_FAILURE = 64
 CD_ERR_RCCL, CD_ERR_PEER, CD_ERR_INJECTED = -1008, -1009, -1010
 
 
+class CdCcdInfo(C.Structure):
+    _fields_ = [("n_candidates", C.c_uint64), ("n_tested", C.c_uint64), ("n_evals", C.c_uint64), ("n_unresolved", C.c_uint64)]
+
+
 class CdMultiInfo(C.Structure):
     _fields_ = [("world", C.c_uint32), ("rank", C.c_uint32), ("n_peers", C.c_uint32), ("host_syncs", C.c_uint32), ("attempts", C.c_uint32),
                 ("failed_rank_plus1", C.c_uint32), ("sent_queries", C.c_uint64), ("recv_queries", C.c_uint64), ("local_pairs", C.c_uint64),
@@ -68,6 +72,7 @@ EXPORTS = [
     "cd_debug_option", "cd_debug_hint", "cd_debug_hint_set", "cd_morton3d_points", "cd_morton3d_points_layout", "cd_expand64_values", "cd_box_pairs", "cd_tri_contact_points", "cd_alloc_host_pairs", "cd_free_host_pairs",
     "cd_multi_unique_id", "cd_multi_create", "cd_multi_create_from_comm", "cd_multi_destroy", "cd_multi_set_flags", "cd_multi_step",
     "cd_find_proximity", "cd_self_proximity", "cd_tri_distance_points",
+    "cd_find_ccd", "cd_self_ccd", "cd_ccd_points",
 ]
 
 _lib = None
@@ -139,6 +144,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_find_proximity.argtypes = [vp, C.c_double, vp, vp, C.c_uint64, u64p, u64p]
     lib.cd_self_proximity.argtypes = [vp, C.c_double, vp, vp, C.c_uint64, u64p, u64p]
     lib.cd_tri_distance_points.argtypes = [vp, C.c_uint64, vp]
+    lib.cd_find_ccd.argtypes = [vp, vp, C.c_double, vp, vp, vp, C.c_uint64, u64p, vp]
+    lib.cd_self_ccd.argtypes = [vp, vp, C.c_double, vp, vp, vp, C.c_uint64, u64p, vp]
+    lib.cd_ccd_points.argtypes = [vp, C.c_uint64, C.c_double, vp, vp, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -304,6 +312,30 @@ class CollisionDetector:
     def self_proximity(self, dist: float, cap: int = 1 << 20):
         """cd_self_proximity: build the tree, then find_proximity, with one host synchronisation."""
         return self._proximity_call(self.lib.cd_self_proximity, "cd_self_proximity", dist, cap)
+
+    def _ccd_call(self, fn, name, verts_end, dist, cap):
+        v = np.ascontiguousarray(verts_end, dtype=np.float64)
+        if v.shape != (self.nv, 3):
+            raise ValueError(f"verts_end must be [{self.nv}, 3], got {v.shape}")
+        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        toi = np.empty(max(cap, 1), dtype=np.float64)
+        dists = np.empty(max(cap, 1), dtype=np.float64)
+        n, info = C.c_uint64(0), CdCcdInfo()
+        rc = fn(self._ctx, _ptr(v), float(dist), _ptr(pairs) if cap else None, _ptr(toi), _ptr(dists), cap, C.byref(n), C.byref(info))
+        self._chk(name, rc, allow=(CD_OK, CD_OVERFLOW))
+        self.ccd_info = info
+        got = min(n.value, cap)
+        return pairs[:got].copy(), toi[:got].copy(), dists[:got].copy(), n.value, rc
+
+    def find_ccd(self, verts_end, dist: float, cap: int = 1 << 20):
+        """cd_find_ccd on the tree that is there, the vertices moving linearly to verts_end: (pairs[n, 2] (smaller ID, larger ID),
+        toi[n], dists[n], n, rc); n may exceed cap (rc = CD_OVERFLOW, the first cap pairs are returned).  A returned distance > dist
+        marks a pair left unresolved.  self.ccd_info: candidates, pairs through the gate, evaluations, unresolved pairs."""
+        return self._ccd_call(self.lib.cd_find_ccd, "cd_find_ccd", verts_end, dist, cap)
+
+    def self_ccd(self, verts_end, dist: float, cap: int = 1 << 20):
+        """cd_self_ccd: build the tree on the current vertices, then find_ccd, with one host synchronisation."""
+        return self._ccd_call(self.lib.cd_self_ccd, "cd_self_ccd", verts_end, dist, cap)
 
     def find_collisions(self, cap: int = 1 << 20):
         return self._pairs_call(self.lib.cd_find_collisions, "cd_find_collisions", cap)
@@ -520,6 +552,19 @@ def tri_distance_points(tri) -> np.ndarray:
     if rc != CD_OK:
         raise CdError("cd_tri_distance_points", rc)
     return out
+
+
+def ccd_points(tri, dist: float):
+    """The per-pair continuous advancement (cd_ccd_points) on explicit positions [n, 12, 3] (A's and B's vertices at x0, then at x1):
+    (toi[n] (+inf: not reported), dists[n], evals[n])."""
+    t = np.ascontiguousarray(tri, dtype=np.float64).reshape(-1, 36)
+    toi = np.zeros(t.shape[0], dtype=np.float64)
+    d = np.zeros(t.shape[0], dtype=np.float64)
+    ev = np.zeros(t.shape[0], dtype=np.uint32)
+    rc = load_library().cd_ccd_points(_ptr(t), t.shape[0], float(dist), _ptr(toi), _ptr(d), _ptr(ev))
+    if rc != CD_OK:
+        raise CdError("cd_ccd_points", rc)
+    return toi, d, ev
 
 
 def version() -> str:

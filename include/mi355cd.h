@@ -409,6 +409,36 @@ int cd_self_proximity(cd_ctx *ctx, double dist, uint32_t *pairs, double *dists, 
  * cd_tri_contact_points.  The pin of the device function. */
 int cd_tri_distance_points(const double *tri, uint64_t n, double *dist);
 
+/* ---- continuous collision queries (not reference behaviour) ----
+ * Vertices move linearly from x0 (this context's vertices, the tree's) to x1 = verts_end (host pointer, nv x 3 doubles, the layout of
+ * cd_create's; uploaded by the call, never installed into the context): p(t) = p0 + t * (p1 - p0) per coordinate, t in [0, 1].
+ * Every unordered pair (A, B) with no shared vertex index (as proximity), A the smaller ID (equal IDs: the smaller face index), whose
+ * FP64 swept boxes (the box of each triangle's six points, x0 and x1) widened by dist (lo - dist, hi + dist) overlap (closed), is run
+ * through conservative advancement with report threshold dist and target h = dist / 2:
+ *   L = (max_i |dA_i - g| + max_j |dB_j - g|) (1 + 2^-20), d = p1 - p0 per vertex, g the mean of the six d;
+ *   t = 0, d = tri_distance on x0 itself; then: d <= dist -> reported (t, d); L == 0 -> not reported; CCD_MAX_EVALS (1024)
+ *   evaluations made -> reported UNRESOLVED (t, d) with d > dist; t' = t + (d - h) / L >= 1 -> one evaluation on x1 itself,
+ *   reported (1, d1) when d1 <= dist, else not; otherwise t = t', d = tri_distance at p(t), again.
+ * Guarantee: a pair whose exact linearly moving triangles come closer than h - delta (delta ~ 2^-38 of the pair's largest |coordinate|)
+ * at some t* is reported with toi <= t*, and stays at least h - delta apart before toi.  The pairs with toi == 0 are cd_find_proximity's
+ * on x0 with the same distances (for dist >= 2^-30 of the largest |coordinate|); every pair of cd_find_proximity on x1 is reported.
+ * pairs: interleaved (smaller ID, larger ID), unordered; toi[k], dists[k] (either may be NULL): its time and distance.
+ * info (may be NULL): candidates of the broad phase, pairs through the gate, tri_distance evaluations, unresolved pairs reported.
+ * Needs a tree built from the current vertices (CD_ERR_ORDER otherwise).  dist must be finite and > 0, verts_end not NULL (CD_ERR_ARG
+ * otherwise).  Returns CD_OVERFLOW with the true *n_pairs when it exceeds cap_pairs; nothing is written past cap_pairs.  These calls
+ * leave the context's vertices, cd_stats, the last collision pair list, a captured CD_OPT_GRAPH step and the proximity buffers as they
+ * were; they keep device buffers of their own. */
+typedef struct cd_ccd_info { uint64_t n_candidates, n_tested, n_evals, n_unresolved; } cd_ccd_info;
+int cd_find_ccd(cd_ctx *ctx, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists,
+                uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info);
+/* cd_build_tree on x0 + cd_find_ccd, queued back to back, one host synchronisation. */
+int cd_self_ccd(cd_ctx *ctx, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists,
+                uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info);
+/* The per-pair advancement on explicit positions (host pointers; no context; no gate): tri is n x 36 doubles, A's three vertices then
+ * B's at x0, then the same at x1.  toi[k] = +inf: not reported (dists[k] = the last distance evaluated); evals[k]: tri_distance
+ * evaluations.  The pin of the device function. */
+int cd_ccd_points(const double *tri, uint64_t n, double dist, double *toi, double *dists, uint32_t *evals);
+
 /* Library / build identification: "mi355cd <version> gfx950". */
 const char *cd_version(void);
 
