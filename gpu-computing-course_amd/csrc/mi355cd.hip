@@ -1187,6 +1187,7 @@ static int install_frame(cd_ctx *c, int mode, const double off[3], const double 
     HIPCHK(hipStreamSynchronize(c->stream));                                // (nothing of an earlier call may still read the old frame)
     HIPCHK(hipMemcpy(c->d_frame, c->frame_host, sizeof(double) * FRAME_WORDS, hipMemcpyHostToDevice));
     c->stage = ST_CREATED;
+    graph_drop(c);                                                          // (a captured step has k_morton's instance baked in: <true> for a layout word, <false> without)
     return CD_OK;
 }
 int cd_set_morton_frame(cd_ctx *c, int mode, const double offset[3], const double span[3])
