@@ -398,7 +398,9 @@ int cd_multi_step(cd_multi *m, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_
  * including after cd_update_vertices without a rebuild).  dist must be finite and >= 0 (CD_ERR_ARG otherwise).  Returns CD_OVERFLOW
  * with the true *n_pairs when it exceeds cap_pairs; nothing is written past cap_pairs (pairs may be NULL with cap_pairs 0).
  * The result depends on the mesh and dist only: not on the Morton frame, CD_OPT_TRAVERSAL, CD_OPT_CELL_TABLE or how the tree was
- * built.  These calls leave cd_stats, the last collision pair list (cd_sorted_pairs, cd_collision_triangles) and a captured
+ * built.  Scaling the mesh and dist by a power of two scales the distances and nothing else while the largest |coordinate| lies within
+ * about 2^-320 .. 2^260 (fp32 overflow and subnormals included); beyond, the contact predicate that puts a pair
+ * at 0 overflows or underflows as the reference's does, and the results follow it.  These calls leave cd_stats, the last collision pair list (cd_sorted_pairs, cd_collision_triangles) and a captured
  * CD_OPT_GRAPH step as they were; they keep device buffers of their own. */
 int cd_find_proximity(cd_ctx *ctx, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs,
                       uint64_t *n_pairs, uint64_t *n_tested);
@@ -422,6 +424,8 @@ int cd_tri_distance_points(const double *tri, uint64_t n, double *dist);
  * Guarantee: a pair whose exact linearly moving triangles come closer than h - delta (delta ~ 2^-38 of the pair's largest |coordinate|)
  * at some t* is reported with toi <= t*, and stays at least h - delta apart before toi.  The pairs with toi == 0 are cd_find_proximity's
  * on x0 with the same distances (for dist >= 2^-30 of the largest |coordinate|); every pair of cd_find_proximity on x1 is reported.
+ * Scaling x0, x1 and dist by a power of two keeps the pairs and toi and scales the distances within cd_find_proximity's band of
+ * coordinate magnitudes.
  * pairs: interleaved (smaller ID, larger ID), unordered; toi[k], dists[k] (either may be NULL): its time and distance.
  * info (may be NULL): candidates of the broad phase, pairs through the gate, tri_distance evaluations, unresolved pairs reported.
  * Needs a tree built from the current vertices (CD_ERR_ORDER otherwise).  dist must be finite and > 0, verts_end not NULL (CD_ERR_ARG

@@ -15,6 +15,7 @@ import pytest
 import ccd_ref as cr
 import mi355cd
 import mi355_synth as synth
+import scale_inputs as si
 
 DELTA_REL = 2.0 ** -38
 
@@ -176,3 +177,21 @@ def test_argument_errors_without_a_device():
     n = C.c_uint64(0)
     assert lib.cd_find_ccd(None, tri.ctypes.data, 0.1, None, None, None, 0, C.byref(n), None) == mi355cd.CD_ERR_ARG
     assert lib.cd_self_ccd(None, tri.ctypes.data, 0.1, None, None, None, 0, C.byref(n), None) == mi355cd.CD_ERR_ARG
+
+
+@pytest.mark.parametrize("name", list(si.meshes()))
+def test_restatement_is_equivariant_under_powers_of_two(name):
+    """x0, x1 and dist scaled by 2^k over scale_inputs.SCALES (past both ends of the fp32 range): the same pairs, the same toi bits,
+    distances times 2^k exactly, and the same gate and evaluation counts -- what tests/test_query_scales_gpu.py compares the device
+    with at every scale."""
+    v, vidx, edge = si.meshes()[name]
+    x1 = si.motion(v, edge)
+    dist = edge / 4
+    (p0, t0, d0), counts0 = cr.ccd_pairs(v, x1, vidx, None, dist, brute=False, counts=True)
+    assert p0.shape[0] > vidx.shape[0] and np.all(d0 <= dist)                       # many pairs, none unresolved
+    assert len(np.unique(t0)) > 100
+    for k in si.SCALES:
+        (pk, tk, dk), countsk = cr.ccd_pairs(si.scaled(v, k), si.scaled(x1, k), vidx, None, np.ldexp(dist, k), brute=False, counts=True)
+        assert np.array_equal(pk, p0) and countsk == counts0, (k, pk.shape, p0.shape, countsk, counts0)
+        assert np.array_equal(tk.view(np.uint64), t0.view(np.uint64)), k
+        assert np.array_equal(dk.view(np.uint64), np.ldexp(d0, k).view(np.uint64)), k

@@ -16,6 +16,7 @@ import pytest
 
 import mi355cd
 import proximity_ref as pr
+import scale_inputs as si
 
 TOL_REL = 2.0 ** -40
 
@@ -128,3 +129,32 @@ def test_proximity_entry_points_reject_bad_arguments():
             # a non-null context pointer that is never dereferenced: the distance is checked first
             assert fn(C.c_void_p(8), bad, None, None, 0, C.byref(n), None) == mi355cd.CD_ERR_ARG
     assert lib.cd_tri_distance_points(None, 1, None) == mi355cd.CD_ERR_ARG
+
+
+@pytest.mark.parametrize("name", list(si.meshes()))
+def test_restatement_is_equivariant_under_powers_of_two(name):
+    """Scaling a mesh by 2^k over scale_inputs.SCALES (past both ends of the fp32 range) scales every distance by 2^k exactly and
+    changes neither the pairs in contact nor the oracle's collision pairs: the fact the device's range tests
+    (tests/test_query_scales_gpu.py) compare against."""
+    v, vidx, edge = si.meshes()[name]
+    n = vidx.shape[0]
+    tv = v[vidx.astype(np.int64)]
+    c = pr._candidates(tv.min(axis=1) - edge / 2, tv.max(axis=1) + edge / 2)      # every pair whose boxes are at most `edge` apart
+    i, j = c[:, 0], c[:, 1]
+    keep = ~(vidx[i][:, :, None] == vidx[j][:, None, :]).any(axis=(1, 2))
+    pairs = np.concatenate([tv[i[keep]], tv[j[keep]]], axis=1)
+    assert pairs.shape[0] > 5 * n
+    d0 = pr.tri_distance_np(pairs)
+    z0 = pr.in_contact(pairs)
+    coll0 = pr.oracle.pair_set(pr.oracle.brute_force(v, vidx)[0])
+    dist = edge / 4
+    p0, pd0 = pr.proximity_pairs(v, vidx, None, dist, brute=False)
+    assert z0.sum() >= 50 and coll0.size == z0.sum() and p0.shape[0] > z0.sum()
+    for k in si.SCALES:
+        dk = pr.tri_distance_np(si.scaled(pairs, k))
+        bad = np.nonzero(dk.view(np.uint64) != np.ldexp(d0, k).view(np.uint64))[0]
+        assert bad.size == 0, (k, bad.size, bad[:3])
+        assert np.array_equal(pr.in_contact(si.scaled(pairs, k)), z0), k
+        assert np.array_equal(pr.oracle.pair_set(pr.oracle.brute_force(si.scaled(v, k), vidx)[0]), coll0), k
+        pk, pdk = pr.proximity_pairs(si.scaled(v, k), vidx, None, np.ldexp(dist, k), brute=False)
+        assert np.array_equal(pk, p0) and np.array_equal(pdk.view(np.uint64), np.ldexp(pd0, k).view(np.uint64)), k
