@@ -7,7 +7,7 @@
 //   k_ccd_refit    : one lane per leaf: the FP64 box of the leaf's six points (x0 and x1) rounded outward to fp32 is written into
 //       its parent's record half; the lane climbs while it is the second to arrive at a record (per-split arrival counter) and
 //       writes the union of that record's two halves into ITS parent's half.  fp32 unions of outward-rounded boxes are true bounds.
-//   k_ccd_descend  : k_prox_descend's stackless pre-order walk over the swept records; the query box is the leaf's swept box
+//   k_ccd_descend  : k_prox_descend's stackless pre-order walk (prox_walk) over the swept records; the query box is the leaf's swept box
 //       widened by ccd_pad with directed rounding; candidates go through the same LDS queue to the same shards.
 //   k_ccd_exact    : neighbour filter, FP64 swept-box gate, ccd_advance, append (IDs, toi, d) with one atomic per workgroup and round.
 //   k_ccd_points   : ccd_advance on explicit positions (cd_ccd_points): the pin of the device code.
@@ -94,7 +94,7 @@ template <class S> __device__ inline void ccd_advance(const S &src, double dist,
 }
 
 // The FP64 swept-box gate: the boxes of each triangle's six points, widened by dist (lo - dist, hi + dist), overlap (closed).
-__device__ __forceinline__ Box swept_box(const CcdMeshSrc &s, int k0)
+template <class S> __device__ __forceinline__ Box swept_box(const S &s, int k0)
 {
     Box b = box_set(s.p0(k0), s.p0(k0 + 1), s.p0(k0 + 2));
     const Box e = box_set(s.p1(k0), s.p1(k0 + 1), s.p1(k0 + 2));
@@ -102,7 +102,7 @@ __device__ __forceinline__ Box swept_box(const CcdMeshSrc &s, int k0)
     b.x2 = fmax2(b.x2, e.x2); b.y2 = fmax2(b.y2, e.y2); b.z2 = fmax2(b.z2, e.z2);
     return b;
 }
-__device__ __forceinline__ bool ccd_gate(const CcdMeshSrc &s, double dist)
+template <class S> __device__ __forceinline__ bool ccd_gate(const S &s, double dist)
 {
     const Box a = swept_box(s, 0), b = swept_box(s, 3);
     return (a.x1 - dist) <= (b.x2 + dist) && (b.x1 - dist) <= (a.x2 + dist) && (a.y1 - dist) <= (b.y2 + dist) &&
@@ -202,9 +202,7 @@ __global__ __launch_bounds__(PROX_DESC_THREADS) void k_ccd_descend(const NodeRec
                                                                    uint2 *__restrict__ cand, unsigned long long shard_cap)
 {
     if (sort_failed(sort_flags)) return;                                 // the records are not a tree (the host redoes the build)
-    __shared__ uint2 queue[PROX_QCAP];
-    const uint32_t lane = threadIdx.x, j = blockIdx.x * PROX_DESC_THREADS + lane;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    const uint32_t j = blockIdx.x * PROX_DESC_THREADS + threadIdx.x;
     unsigned long long *ctr = &st->shard[(blockIdx.x & (NSHARD - 1)) * PROX_SHARD_STRIDE];
     uint2 *shard = cand + (size_t)(blockIdx.x & (NSHARD - 1)) * shard_cap;
     const float pad = ccd_pad(st, dist);
@@ -221,47 +219,7 @@ __global__ __launch_bounds__(PROX_DESC_THREADS) void k_ccd_descend(const NodeRec
         h0 = r[0]; h1 = r[1];
         end = __float_as_uint(h1.w) & REC_LAST_MASK;
     }
-    uint32_t qn = 0;                                                     // (wave-uniform)
-    uint32_t steps = 0;
-    while (__ballot(active) != 0ull) {
-        bool hit = false; uint32_t k = 0;
-        if (active) {
-            const bool ov = qlx <= h0.w && h0.x <= qhx && qly <= h1.x && h0.y <= qhy && qlz <= h1.y && h0.z <= qhz;   // closed overlap
-            const int32_t link = (int32_t)__float_as_uint(h1.z);
-            if (ov && link >= 0) {                                       // an internal node: on to its left child, which ends at its split
-                const float4 *l = rec_left(recs, n, (uint32_t)link);
-                h0 = l[0]; h1 = l[1];
-                end = (uint32_t)link;
-            } else {
-                if (ov) { hit = true; k = ~(uint32_t)link; }
-                if (end >= (uint32_t)(n - 1) || ++steps > 2u * (uint32_t)n) active = false;   // (the bound only guards against a broken tree)
-                else {                                                   // the next subtree in pre-order: the right child of the split at `end`
-                    const float4 *r = rec_right(recs, n, end);
-                    h0 = r[0]; h1 = r[1];
-                    end = __float_as_uint(h1.w) & REC_LAST_MASK;
-                }
-            }
-        }
-        const unsigned long long bal = __ballot(hit);
-        if (hit) queue[qn + __popcll(bal & lt_mask)] = make_uint2(j, k);
-        qn += (uint32_t)__popcll(bal);
-        __syncthreads();
-        const bool last = __ballot(active) == 0ull;
-        while (qn >= 64u || (qn > 0u && last)) {                         // full batches, and at the end whatever is left
-            const uint32_t m = qn < 64u ? qn : 64u;
-            unsigned long long base = 0;
-            if (lane == 0) base = atomicAdd(ctr, (unsigned long long)m);
-            base = __shfl(base, 0);
-            if (lane < m && base + lane < shard_cap) shard[base + lane] = queue[lane];
-            uint2 rest = make_uint2(0u, 0u);
-            const bool moved = lane + 64u < qn;
-            if (moved) rest = queue[lane + 64u];
-            __syncthreads();
-            if (moved) queue[lane] = rest;
-            __syncthreads();
-            qn -= m;
-        }
-    }
+    prox_walk<HiTrue>(recs, n, j, active, h0, h1, end, qlx, qly, qlz, qhx, qhy, qhz, ctr, shard, shard_cap);
 }
 
 __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_ccd_exact(const uint2 *__restrict__ cand, unsigned long long shard_cap, const LeafTri *__restrict__ leaf,

@@ -1,7 +1,8 @@
 // cd_proximity.h -- self-proximity: every pair of triangles of the mesh with no shared vertex index and tri_distance <= dist
 // (cd_math.h), over the tree the collision path builds.  Not reference behaviour.
 //   k_prox_descend : fp32 filter.  One lane per query leaf j (sorted order), no stack: the leaves (j, n-1] are walked in
-//       pre-order through the split-named records (cd_bvh.h), starting at the right child of recs[j].  A subtree that
+//       pre-order through the split-named records (cd_bvh.h), starting at the right child of recs[j] (prox_walk, shared with the
+//       CCD and between-mesh descents).  A subtree that
 //       ends at leaf e and is done (missed, or a leaf) is followed by the right child of recs[e] -- the next subtree in
 //       pre-order -- until e == n-1.  Nothing is pushed, so no depth can overflow anything.  Every stored box is taken as
 //       [lo, f32_next_up(hi)] (the records keep hi ROUNDED DOWN unless its cell is ambiguous: an upper bound only after the
@@ -49,40 +50,31 @@ __device__ __forceinline__ float prox_pad(const double *__restrict__ root_box, d
     return __double2float_ru(dist + dist * PROX_SLACK + m * PROX_SLACK);
 }
 
-__global__ __launch_bounds__(PROX_DESC_THREADS) void k_prox_descend(const NodeRec32 *__restrict__ recs, const LeafTri *__restrict__ leaf,
-                                                                    const double *__restrict__ verts, const double *__restrict__ root_box, int n, double dist,
-                                                                    const uint32_t *__restrict__ sort_flags /* 9 words */, ProxState *__restrict__ st,
-                                                                    uint2 *__restrict__ cand, unsigned long long shard_cap)
+// How a walk reads a stored hi: the static records' as an upper bound (prox_hi), the swept records' as they are (true bounds).
+struct HiNextUp { __device__ static __forceinline__ float hi(float h) { return prox_hi(h); } };
+struct HiTrue { __device__ static __forceinline__ float hi(float h) { return h; } };
+
+// The stackless pre-order walk and its candidate queue, written once (k_prox_descend, k_ccd_descend, k_between_descend).  A lane starts
+// at the subtree (h0, h1) -- a record half -- whose last leaf is `end`, and walks every subtree after it in pre-order up to leaf n-1: an
+// internal node that overlaps goes on to its left child (which ends at its split); a subtree that is done (missed, or a leaf) is
+// followed by the right child of the split at `end`, until end == n-1.  The query box (ql*, qh*) meets [lo, Hi::hi(hi)] closed.
+// Leaf hits (j, k) go through a wave-shared LDS queue to `shard`, 64 at a time (nothing is written past shard_cap; *ctr counts all).
+// One wave per workgroup; every lane of it calls this (inactive lanes with active = false).
+template <class Hi>
+__device__ __forceinline__ void prox_walk(const NodeRec32 *__restrict__ recs, int n, uint32_t j, bool active, float4 h0, float4 h1, uint32_t end,
+                                          float qlx, float qly, float qlz, float qhx, float qhy, float qhz,
+                                          unsigned long long *__restrict__ ctr, uint2 *__restrict__ shard, unsigned long long shard_cap)
 {
-    uint32_t bad = 0;
-    for (int i = 0; i < 9; ++i) bad |= sort_flags[i];
-    if (bad) return;                                                     // the sort failed: the records are not a tree (the host redoes the build)
     __shared__ uint2 queue[PROX_QCAP];
-    const uint32_t lane = threadIdx.x, j = blockIdx.x * PROX_DESC_THREADS + lane;
+    const uint32_t lane = threadIdx.x;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    unsigned long long *ctr = &st->shard[(blockIdx.x & (NSHARD - 1)) * PROX_SHARD_STRIDE];
-    uint2 *shard = cand + (size_t)(blockIdx.x & (NSHARD - 1)) * shard_cap;
-    const float pad = prox_pad(root_box, dist);
-    bool active = (int)j < n - 1;
-    float qlx = 0.f, qly = 0.f, qlz = 0.f, qhx = 0.f, qhy = 0.f, qhz = 0.f;
-    float4 h0 = make_float4(0.f, 0.f, 0.f, 0.f), h1 = h0;                // the subtree at hand: its box and link, as a record half holds them
-    uint32_t end = 0;                                                    // its last leaf
-    if (active) {
-        const LeafTri lt = leaf[j];
-        const Box b = box_set(load_vertex(verts, lt.v0), load_vertex(verts, lt.v1), load_vertex(verts, lt.v2));
-        qlx = __ocml_sub_rtn_f32(__double2float_rd(b.x1), pad); qly = __ocml_sub_rtn_f32(__double2float_rd(b.y1), pad); qlz = __ocml_sub_rtn_f32(__double2float_rd(b.z1), pad);
-        qhx = __ocml_add_rtp_f32(__double2float_ru(b.x2), pad); qhy = __ocml_add_rtp_f32(__double2float_ru(b.y2), pad); qhz = __ocml_add_rtp_f32(__double2float_ru(b.z2), pad);
-        const float4 *r = rec_right(recs, n, j);
-        h0 = r[0]; h1 = r[1];
-        end = __float_as_uint(h1.w) & REC_LAST_MASK;
-    }
     uint32_t qn = 0;                                                     // (wave-uniform)
     uint32_t steps = 0;
     while (__ballot(active) != 0ull) {
         bool hit = false; uint32_t k = 0;
         if (active) {
-            // closed overlap of the widened query box with [lo, next_up(hi)]
-            const bool ov = qlx <= prox_hi(h0.w) && h0.x <= qhx && qly <= prox_hi(h1.x) && h0.y <= qhy && qlz <= prox_hi(h1.y) && h0.z <= qhz;
+            // closed overlap of the widened query box with [lo, Hi::hi(hi)]
+            const bool ov = qlx <= Hi::hi(h0.w) && h0.x <= qhx && qly <= Hi::hi(h1.x) && h0.y <= qhy && qlz <= Hi::hi(h1.y) && h0.z <= qhz;
             const int32_t link = (int32_t)__float_as_uint(h1.z);
             if (ov && link >= 0) {                                       // an internal node: on to its left child, which ends at its split
                 const float4 *l = rec_left(recs, n, (uint32_t)link);
@@ -118,6 +110,34 @@ __global__ __launch_bounds__(PROX_DESC_THREADS) void k_prox_descend(const NodeRe
             qn -= m;
         }
     }
+}
+
+__global__ __launch_bounds__(PROX_DESC_THREADS) void k_prox_descend(const NodeRec32 *__restrict__ recs, const LeafTri *__restrict__ leaf,
+                                                                    const double *__restrict__ verts, const double *__restrict__ root_box, int n, double dist,
+                                                                    const uint32_t *__restrict__ sort_flags /* 9 words */, ProxState *__restrict__ st,
+                                                                    uint2 *__restrict__ cand, unsigned long long shard_cap)
+{
+    uint32_t bad = 0;
+    for (int i = 0; i < 9; ++i) bad |= sort_flags[i];
+    if (bad) return;                                                     // the sort failed: the records are not a tree (the host redoes the build)
+    const uint32_t j = blockIdx.x * PROX_DESC_THREADS + threadIdx.x;
+    unsigned long long *ctr = &st->shard[(blockIdx.x & (NSHARD - 1)) * PROX_SHARD_STRIDE];
+    uint2 *shard = cand + (size_t)(blockIdx.x & (NSHARD - 1)) * shard_cap;
+    const float pad = prox_pad(root_box, dist);
+    bool active = (int)j < n - 1;
+    float qlx = 0.f, qly = 0.f, qlz = 0.f, qhx = 0.f, qhy = 0.f, qhz = 0.f;
+    float4 h0 = make_float4(0.f, 0.f, 0.f, 0.f), h1 = h0;                // the subtree at hand: its box and link, as a record half holds them
+    uint32_t end = 0;                                                    // its last leaf
+    if (active) {
+        const LeafTri lt = leaf[j];
+        const Box b = box_set(load_vertex(verts, lt.v0), load_vertex(verts, lt.v1), load_vertex(verts, lt.v2));
+        qlx = __ocml_sub_rtn_f32(__double2float_rd(b.x1), pad); qly = __ocml_sub_rtn_f32(__double2float_rd(b.y1), pad); qlz = __ocml_sub_rtn_f32(__double2float_rd(b.z1), pad);
+        qhx = __ocml_add_rtp_f32(__double2float_ru(b.x2), pad); qhy = __ocml_add_rtp_f32(__double2float_ru(b.y2), pad); qhz = __ocml_add_rtp_f32(__double2float_ru(b.z2), pad);
+        const float4 *r = rec_right(recs, n, j);                         // the walk starts at the right child of recs[j]
+        h0 = r[0]; h1 = r[1];
+        end = __float_as_uint(h1.w) & REC_LAST_MASK;
+    }
+    prox_walk<HiNextUp>(recs, n, j, active, h0, h1, end, qlx, qly, qlz, qhx, qhy, qhz, ctr, shard, shard_cap);
 }
 
 __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_prox_exact(const uint2 *__restrict__ cand, unsigned long long shard_cap, const LeafTri *__restrict__ leaf,

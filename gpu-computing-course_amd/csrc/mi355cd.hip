@@ -9,6 +9,7 @@
 #include "cd_post.h"
 #include "cd_proximity.h"
 #include "cd_ccd.h"
+#include "cd_between.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -164,6 +165,14 @@ struct cd_ctx {
     uint2 *d_cc_cand = nullptr; uint64_t cc_shard_cap = 0;
     uint32_t *d_cc_pairs = nullptr; double *d_cc_toi = nullptr, *d_cc_dists = nullptr; uint64_t cc_pairs_cap = 0;
     double *d_cc_x1 = nullptr; NodeRec32 *d_cc_recs = nullptr; int32_t *d_cc_up = nullptr; uint32_t *d_cc_arrive = nullptr;
+    // queries between two meshes (cd_find_*_between, cd_between.h) with this context as a: buffers of their own, allocated on first use and
+    // grown to the other context's sizes (x1 of b, b's swept records, parent links, arrival counters)
+    CcdState *d_bw_state = nullptr; CcdState *h_bw_state = nullptr;
+    uint2 *d_bw_cand = nullptr; uint64_t bw_shard_cap = 0;
+    uint32_t *d_bw_pairs = nullptr; double *d_bw_toi = nullptr, *d_bw_dists = nullptr; uint64_t bw_pairs_cap = 0;
+    double *d_bw_x1a = nullptr; double *d_bw_x1b = nullptr; uint64_t bw_x1b_cap = 0;
+    NodeRec32 *d_bw_recs = nullptr; int32_t *d_bw_up = nullptr; uint32_t *d_bw_arrive = nullptr; uint64_t bw_rec_cap = 0;
+    int device = 0;                         // the HIP device ordinal current at cd_create (the between queries need both contexts on one device)
 };
 
 namespace {
@@ -195,6 +204,9 @@ void free_all(cd_ctx *c)
     hipFree(c->d_cc_state); hipFree(c->d_cc_cand); hipFree(c->d_cc_pairs); hipFree(c->d_cc_toi); hipFree(c->d_cc_dists);
     hipFree(c->d_cc_x1); hipFree(c->d_cc_recs); hipFree(c->d_cc_up); hipFree(c->d_cc_arrive);
     if (c->h_cc_state) hipHostFree(c->h_cc_state);
+    hipFree(c->d_bw_state); hipFree(c->d_bw_cand); hipFree(c->d_bw_pairs); hipFree(c->d_bw_toi); hipFree(c->d_bw_dists);
+    hipFree(c->d_bw_x1a); hipFree(c->d_bw_x1b); hipFree(c->d_bw_recs); hipFree(c->d_bw_up); hipFree(c->d_bw_arrive);
+    if (c->h_bw_state) hipHostFree(c->h_bw_state);
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -1090,7 +1102,7 @@ int cd_create(cd_ctx **out, const double *verts_xyz, uint32_t nv, const uint32_t
     c->nv = nv; c->nt = nt;
     c->all_verts_referenced = all_ref;
     c->ntiles = cdiv(nt, SORT_TILE);
-    { int dev = 0, khz = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess) c->wall_clock_khz = khz; (void)hipGetLastError(); }
+    { int dev = 0, khz = 0; if (hipGetDevice(&dev) == hipSuccess) { c->device = dev; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess) c->wall_clock_khz = khz; } (void)hipGetLastError(); }
     const size_t n = nt;
 #define ALLOC(p, bytes) do { hipError_t e_ = hipMalloc((void **)&(p), (bytes)); if (e_ != hipSuccess) { free_all(c); delete c; return -(int)e_; } } while (0)
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -2119,6 +2131,163 @@ int cd_ccd_points(const double *tri, uint64_t n, double dist, double *toi, doubl
     }
     hipFree(d_t); hipFree(d_toi); hipFree(d_d); hipFree(d_e);
     return e == hipSuccess ? CD_OK : -(int)e;
+}
+
+// ---- queries between two meshes (cd_between.h) ------------------------------------------------------------------------------------
+// Everything runs on a's stream, in buffers a owns (state, candidates, pairs, times, distances, x1 of both meshes, b's swept records):
+// neither context's vertices, counters, statistics, pair list, captured step, proximity or CCD buffers are touched.  Both trees are
+// finished (every call of the library blocks); b's stream is drained all the same before its records are read on a's.
+static int bw_args(cd_ctx *a, cd_ctx *b, uint32_t *pairs, uint64_t cap_pairs)
+{
+    if (!a || !b || a == b || a->device != b->device || (cap_pairs && !pairs)) return CD_ERR_ARG;
+    return CD_OK;
+}
+static int bw_buffers(cd_ctx *a, const cd_ctx *b, uint64_t cap_pairs, bool ccd)
+{
+    if (!a->d_bw_state) {
+        HIPCHK(hipMalloc(&a->d_bw_state, sizeof(CcdState)));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&a->h_bw_state), sizeof(CcdState), hipHostMallocDefault));
+    }
+    if (!a->d_bw_cand) {                                                    // 16 candidates a triangle of a to start with; grown on overflow
+        const uint64_t per = std::max<uint64_t>(4096, (16ull * a->nt + NSHARD - 1) / NSHARD);
+        HIPCHK(hipMalloc(&a->d_bw_cand, sizeof(uint2) * per * NSHARD));
+        a->bw_shard_cap = per;
+    }
+    const uint64_t want = cap_pairs > 0 ? cap_pairs : 1;
+    if (want > a->bw_pairs_cap) {
+        hipFree(a->d_bw_pairs); hipFree(a->d_bw_toi); hipFree(a->d_bw_dists);
+        a->d_bw_pairs = nullptr; a->d_bw_toi = nullptr; a->d_bw_dists = nullptr; a->bw_pairs_cap = 0;
+        HIPCHK(hipMalloc(&a->d_bw_pairs, sizeof(uint32_t) * 2 * want));
+        HIPCHK(hipMalloc(&a->d_bw_toi, sizeof(double) * want));
+        HIPCHK(hipMalloc(&a->d_bw_dists, sizeof(double) * want));
+        a->bw_pairs_cap = want;
+    }
+    if (ccd) {
+        if (!a->d_bw_x1a) HIPCHK(hipMalloc(&a->d_bw_x1a, sizeof(double) * 3 * (size_t)a->nv));
+        if (b->nv > a->bw_x1b_cap) {
+            hipFree(a->d_bw_x1b); a->d_bw_x1b = nullptr; a->bw_x1b_cap = 0;
+            HIPCHK(hipMalloc(&a->d_bw_x1b, sizeof(double) * 3 * (size_t)b->nv));
+            a->bw_x1b_cap = b->nv;
+        }
+        if (b->nt > a->bw_rec_cap) {
+            hipFree(a->d_bw_recs); hipFree(a->d_bw_up); hipFree(a->d_bw_arrive);
+            a->d_bw_recs = nullptr; a->d_bw_up = nullptr; a->d_bw_arrive = nullptr; a->bw_rec_cap = 0;
+            HIPCHK(hipMalloc(&a->d_bw_recs, sizeof(NodeRec32) * (size_t)b->nt));
+            HIPCHK(hipMalloc(&a->d_bw_up, sizeof(int32_t) * 2 * (size_t)b->nt));
+            HIPCHK(hipMalloc(&a->d_bw_arrive, sizeof(uint32_t) * (size_t)b->nt));
+            a->bw_rec_cap = b->nt;
+        }
+    }
+    return CD_OK;
+}
+// one pass (CCD: a's M, b's swept refit; descent; exact stage) and the read-back of the counters (no synchronisation).  ax1 / bx1: device
+// pointers to the end positions (CCD only).
+static int bw_enqueue(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_pairs, const double *ax1, const double *bx1)
+{
+    hipStream_t s = a->stream;
+    const uint32_t na = a->nt, nb = b->nt;
+    const uint32_t *fa = a->d_os_ticket + 8, *fb = b->d_os_ticket + 8;
+    HIPCHK(hipMemsetAsync(a->d_bw_state, 0, sizeof(CcdState), s));
+    if (kind == BW_CCD) {
+        k_between_mbits<<<cdiv(na, CCD_THREADS), CCD_THREADS, 0, s>>>(a->d_leaf, a->d_verts, ax1, (int)na, a->d_bw_state);
+        if (nb >= 2) {
+            HIPCHK(hipMemsetAsync(a->d_bw_up, 0xff, sizeof(int32_t) * 2 * (size_t)nb, s));   // -1: no parent (the root)
+            k_ccd_links<<<cdiv(nb - 1, CCD_THREADS), CCD_THREADS, 0, s>>>(b->d_recs32, (int)nb, fb, a->d_bw_recs, a->d_bw_up, a->d_bw_arrive);
+            k_ccd_refit<<<cdiv(nb, CCD_THREADS), CCD_THREADS, 0, s>>>(b->d_leaf, b->d_verts, bx1, (int)nb, fb, a->d_bw_up, a->d_bw_arrive, a->d_bw_recs, a->d_bw_state);
+        }
+        k_between_descend<true><<<cdiv(na, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(a->d_bw_recs, b->d_root, (int)nb, a->d_leaf, a->d_verts, ax1, (int)na,
+                                                                                         a->d_boxes, b->d_boxes, dist, fa, fb, a->d_bw_state, a->d_bw_cand, a->bw_shard_cap);
+    } else {
+        k_between_descend<false><<<cdiv(na, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(b->d_recs32, b->d_root, (int)nb, a->d_leaf, a->d_verts, nullptr, (int)na,
+                                                                                          a->d_boxes, b->d_boxes, dist, fa, fb, a->d_bw_state, a->d_bw_cand, a->bw_shard_cap);
+    }
+    const uint32_t xb = std::max<uint32_t>(1u, std::min<uint32_t>(64u, cdiv(na, 4096)));   // workgroups per shard
+    const dim3 grid(xb, NSHARD);
+    if (kind == BW_CONTACT)
+        k_between_exact<BW_CONTACT><<<grid, PROX_EXACT_THREADS, 0, s>>>(a->d_bw_cand, a->bw_shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
+                                                                        dist, a->d_bw_state, a->d_bw_pairs, a->d_bw_toi, a->d_bw_dists, cap_pairs);
+    else if (kind == BW_PROXIMITY)
+        k_between_exact<BW_PROXIMITY><<<grid, PROX_EXACT_THREADS, 0, s>>>(a->d_bw_cand, a->bw_shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
+                                                                          dist, a->d_bw_state, a->d_bw_pairs, a->d_bw_toi, a->d_bw_dists, cap_pairs);
+    else
+        k_between_exact<BW_CCD><<<grid, PROX_EXACT_THREADS, 0, s>>>(a->d_bw_cand, a->bw_shard_cap, a->d_leaf, a->d_verts, ax1, b->d_leaf, b->d_verts, bx1,
+                                                                    dist, a->d_bw_state, a->d_bw_pairs, a->d_bw_toi, a->d_bw_dists, cap_pairs);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(a->h_bw_state, a->d_bw_state, sizeof(CcdState), hipMemcpyDeviceToHost, s));
+    return CD_OK;
+}
+// enqueue, synchronise, and again with a grown candidate buffer while a shard overflowed
+static int bw_pass(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_pairs, const double *ax1, const double *bx1)
+{
+    for (;;) {
+        int rc = bw_enqueue(a, b, kind, dist, cap_pairs, ax1, bx1);
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(a->stream));
+        uint64_t mx = 0;
+        for (int i = 0; i < NSHARD; ++i) mx = std::max<uint64_t>(mx, a->h_bw_state->shard[i * PROX_SHARD_STRIDE]);
+        if (mx <= a->bw_shard_cap) return CD_OK;
+        hipFree(a->d_bw_cand); a->d_bw_cand = nullptr;
+        const uint64_t per = mx + mx / 4 + 1024;
+        const hipError_t e = hipMalloc(&a->d_bw_cand, sizeof(uint2) * per * NSHARD);
+        if (e != hipSuccess) { a->bw_shard_cap = 0; return -(int)e; }
+        a->bw_shard_cap = per;
+    }
+}
+static int bw_results(cd_ctx *a, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs)
+{
+    const uint64_t np = a->h_bw_state->n_pairs, take = std::min(np, cap_pairs);
+    if (take) {
+        HIPCHK(hipMemcpy(pairs, a->d_bw_pairs, sizeof(uint32_t) * 2 * take, hipMemcpyDeviceToHost));
+        if (toi) HIPCHK(hipMemcpy(toi, a->d_bw_toi, sizeof(double) * take, hipMemcpyDeviceToHost));
+        if (dists) HIPCHK(hipMemcpy(dists, a->d_bw_dists, sizeof(double) * take, hipMemcpyDeviceToHost));
+    }
+    if (n_pairs) *n_pairs = np;
+    return np > cap_pairs ? CD_OVERFLOW : CD_OK;
+}
+static int bw_start(cd_ctx *a, cd_ctx *b, uint64_t cap_pairs, bool ccd)
+{
+    if (a->stage < ST_REFIT || b->stage < ST_REFIT) return CD_ERR_ORDER;
+    int rc = bw_buffers(a, b, cap_pairs, ccd);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return CD_OK;
+}
+int cd_find_collisions_between(cd_ctx *a, cd_ctx *b, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
+{
+    int rc = bw_args(a, b, pairs, cap_pairs);
+    if (rc || (rc = bw_start(a, b, cap_pairs, false))) return rc;
+    if ((rc = bw_pass(a, b, BW_CONTACT, 0.0, cap_pairs, nullptr, nullptr))) return rc;
+    if (n_tested) *n_tested = a->h_bw_state->n_tested;
+    return bw_results(a, pairs, nullptr, nullptr, cap_pairs, n_pairs);
+}
+int cd_find_proximity_between(cd_ctx *a, cd_ctx *b, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
+{
+    int rc = bw_args(a, b, pairs, cap_pairs);
+    if (rc) return rc;
+    if (!prox_dist_ok(dist)) return CD_ERR_ARG;
+    if ((rc = bw_start(a, b, cap_pairs, false))) return rc;
+    if ((rc = bw_pass(a, b, BW_PROXIMITY, dist, cap_pairs, nullptr, nullptr))) return rc;
+    if (n_tested) *n_tested = a->h_bw_state->n_tested;
+    return bw_results(a, pairs, nullptr, dists, cap_pairs, n_pairs);
+}
+int cd_find_ccd_between(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const double *verts_end_b, double dist, uint32_t *pairs, double *toi, double *dists,
+                        uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info)
+{
+    int rc = bw_args(a, b, pairs, cap_pairs);
+    if (rc) return rc;
+    if (!ccd_dist_ok(dist)) return CD_ERR_ARG;
+    if ((rc = bw_start(a, b, cap_pairs, true))) return rc;
+    const double *ax1 = a->d_verts, *bx1 = b->d_verts;                     // NULL: that mesh does not move (x1 = x0)
+    if (verts_end_a) { HIPCHK(hipMemcpyAsync(a->d_bw_x1a, verts_end_a, sizeof(double) * 3 * (size_t)a->nv, hipMemcpyHostToDevice, a->stream)); ax1 = a->d_bw_x1a; }
+    if (verts_end_b) { HIPCHK(hipMemcpyAsync(a->d_bw_x1b, verts_end_b, sizeof(double) * 3 * (size_t)b->nv, hipMemcpyHostToDevice, a->stream)); bx1 = a->d_bw_x1b; }
+    if ((rc = bw_pass(a, b, BW_CCD, dist, cap_pairs, ax1, bx1))) return rc;
+    if (info) {
+        const CcdState *h = a->h_bw_state;
+        uint64_t cand = 0;
+        for (int i = 0; i < NSHARD; ++i) cand += h->shard[i * PROX_SHARD_STRIDE];
+        info->n_candidates = cand; info->n_tested = h->n_tested; info->n_evals = h->n_evals; info->n_unresolved = h->n_unresolved;
+    }
+    return bw_results(a, pairs, toi, dists, cap_pairs, n_pairs);
 }
 }  // extern "C"
 

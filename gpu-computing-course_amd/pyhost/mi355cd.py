@@ -73,6 +73,7 @@ EXPORTS = [
     "cd_multi_unique_id", "cd_multi_create", "cd_multi_create_from_comm", "cd_multi_destroy", "cd_multi_set_flags", "cd_multi_step",
     "cd_find_proximity", "cd_self_proximity", "cd_tri_distance_points",
     "cd_find_ccd", "cd_self_ccd", "cd_ccd_points",
+    "cd_find_collisions_between", "cd_find_proximity_between", "cd_find_ccd_between",
 ]
 
 _lib = None
@@ -147,6 +148,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_find_ccd.argtypes = [vp, vp, C.c_double, vp, vp, vp, C.c_uint64, u64p, vp]
     lib.cd_self_ccd.argtypes = [vp, vp, C.c_double, vp, vp, vp, C.c_uint64, u64p, vp]
     lib.cd_ccd_points.argtypes = [vp, C.c_uint64, C.c_double, vp, vp, vp]
+    lib.cd_find_collisions_between.argtypes = [vp, vp, vp, C.c_uint64, u64p, u64p]
+    lib.cd_find_proximity_between.argtypes = [vp, vp, C.c_double, vp, vp, C.c_uint64, u64p, u64p]
+    lib.cd_find_ccd_between.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp, C.c_uint64, u64p, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -336,6 +340,54 @@ class CollisionDetector:
     def self_ccd(self, verts_end, dist: float, cap: int = 1 << 20):
         """cd_self_ccd: build the tree on the current vertices, then find_ccd, with one host synchronisation."""
         return self._ccd_call(self.lib.cd_self_ccd, "cd_self_ccd", verts_end, dist, cap)
+
+    # ---- queries between this mesh (a) and another context's (b): pairs (ID in self, ID in other), self's triangle first
+    def find_collisions_between(self, other, cap: int = 1 << 20):
+        """cd_find_collisions_between(self, other): (pairs[n, 2] (ID in self, ID in other), n, rc); n may exceed cap (rc = CD_OVERFLOW,
+        the first cap pairs are returned).  self.between_tested: pairs whose FP64 boxes overlap strictly.  Both trees must be built."""
+        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        n, tested = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.cd_find_collisions_between(self._ctx, other._ctx, _ptr(pairs) if cap else None, cap, C.byref(n), C.byref(tested))
+        self._chk("cd_find_collisions_between", rc, allow=(CD_OK, CD_OVERFLOW))
+        self.between_tested = tested.value
+        got = min(n.value, cap)
+        return pairs[:got].copy(), n.value, rc
+
+    def find_proximity_between(self, other, dist: float, cap: int = 1 << 20):
+        """cd_find_proximity_between(self, other, dist): (pairs[n, 2] (ID in self, ID in other), dists[n], n, rc).
+        self.between_tested: exact distance evaluations made."""
+        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        dists = np.empty(max(cap, 1), dtype=np.float64)
+        n, tested = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.cd_find_proximity_between(self._ctx, other._ctx, float(dist), _ptr(pairs) if cap else None, _ptr(dists), cap,
+                                                C.byref(n), C.byref(tested))
+        self._chk("cd_find_proximity_between", rc, allow=(CD_OK, CD_OVERFLOW))
+        self.between_tested = tested.value
+        got = min(n.value, cap)
+        return pairs[:got].copy(), dists[:got].copy(), n.value, rc
+
+    def find_ccd_between(self, other, dist: float, verts_end=None, other_verts_end=None, cap: int = 1 << 20):
+        """cd_find_ccd_between: self's vertices move to verts_end, other's to other_verts_end (None: that mesh does not move):
+        (pairs[n, 2] (ID in self, ID in other), toi[n], dists[n], n, rc).  self.ccd_info: as find_ccd's."""
+        def end(v, nv, what):
+            if v is None:
+                return None
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            if v.shape != (nv, 3):
+                raise ValueError(f"{what} must be [{nv}, 3], got {v.shape}")
+            return v
+        va = end(verts_end, self.nv, "verts_end")
+        vb = end(other_verts_end, other.nv, "other_verts_end")
+        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        toi = np.empty(max(cap, 1), dtype=np.float64)
+        dists = np.empty(max(cap, 1), dtype=np.float64)
+        n, info = C.c_uint64(0), CdCcdInfo()
+        rc = self.lib.cd_find_ccd_between(self._ctx, _ptr(va), other._ctx, _ptr(vb), float(dist), _ptr(pairs) if cap else None,
+                                          _ptr(toi), _ptr(dists), cap, C.byref(n), C.byref(info))
+        self._chk("cd_find_ccd_between", rc, allow=(CD_OK, CD_OVERFLOW))
+        self.ccd_info = info
+        got = min(n.value, cap)
+        return pairs[:got].copy(), toi[:got].copy(), dists[:got].copy(), n.value, rc
 
     def find_collisions(self, cap: int = 1 << 20):
         return self._pairs_call(self.lib.cd_find_collisions, "cd_find_collisions", cap)

@@ -443,6 +443,38 @@ int cd_self_ccd(cd_ctx *ctx, const double *verts_end, double dist, uint32_t *pai
  * evaluations.  The pin of the device function. */
 int cd_ccd_points(const double *tri, uint64_t n, double dist, double *toi, double *dists, uint32_t *evals);
 
+/* ---- queries between two meshes (not reference behaviour) ----
+ * The three questions above, asked of the triangles of context a against those of context b (two objects: a cloth and a body, an
+ * obstacle, another garment).  A pair is (a's triangle, b's triangle), written (ID in a, ID in b) with each context's own IDs from
+ * cd_create -- NOT reordered by ID; rows unordered, as cd_find_collisions.  The two contexts have separate vertex arrays, so there is
+ * no neighbour filter, and cd_set_vertex_id_base plays no part.  Every per-pair predicate takes a's triangle as its first argument
+ * (P / A); the self queries put the smaller ID there instead.  So between(a, b) is exactly the set of cross pairs of the self query on
+ * the merged mesh whose triangles are a's first, with the smaller IDs, and whose vertices are a's, then b's offset by a's nv.
+ *   contact   : the FP64 boxes overlap strictly (box.cuh:40-43) and tri_contact(a, b) holds.  n_tested (may be NULL): the (a, b) pairs
+ *               whose FP64 boxes overlap strictly -- a number of the meshes alone.
+ *   proximity : tri_distance(a, b) <= dist, tri_distance as cd_find_proximity defines it (a pair in contact, as the contact query
+ *               decides it, is at 0).  dists (may be NULL).  n_tested (may be NULL): exact distance evaluations made.
+ *   CCD       : cd_find_ccd's definition -- the FP64 swept-box gate widened by dist, conservative advancement with h = dist / 2,
+ *               CCD_MAX_EVALS, unresolved pairs reported with d > dist -- with x0 each context's current vertices and x1 verts_end_a /
+ *               verts_end_b (host pointers, the layout of cd_create's).  NULL: that mesh does not move (x1 = x0; a static obstacle);
+ *               both may be NULL.  toi, dists, info (each may be NULL) mean what they mean for cd_find_ccd.
+ * Errors: CD_ERR_ARG when a context is NULL, a == b (self queries have their own calls), the two contexts were created on different
+ * HIP devices, or dist fails the rule of the self call (proximity: finite and >= 0; CCD: finite and > 0).  CD_ERR_ORDER unless BOTH
+ * contexts have a tree built from their current vertices (cd_update_vertices without a rebuild counts as not built).  CD_OVERFLOW with
+ * the true *n_pairs when the pairs do not fit cap_pairs; nothing is written past cap_pairs (pairs may be NULL with cap_pairs 0).
+ * Guarantee: the result depends on the two meshes and dist only -- not on either context's Morton frame, CD_OPT_TRAVERSAL,
+ * CD_OPT_CELL_TABLE or build variant, nor on which context's tree is walked.  The calls leave both contexts' state as it was: cd_stats,
+ * the last pair list (cd_sorted_pairs, cd_collision_triangles), a captured CD_OPT_GRAPH step, the proximity and CCD buffers.  Their
+ * device buffers belong to context a (grown on demand; cd_destroy frees them) and they run on a's stream.  Neither context may be used
+ * by another thread during the call. */
+int cd_find_collisions_between(cd_ctx *a, cd_ctx *b, uint32_t *pairs, uint64_t cap_pairs,
+                               uint64_t *n_pairs, uint64_t *n_tested);
+int cd_find_proximity_between(cd_ctx *a, cd_ctx *b, double dist, uint32_t *pairs, double *dists,
+                              uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested);
+int cd_find_ccd_between(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const double *verts_end_b, double dist,
+                        uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
+                        cd_ccd_info *info);
+
 /* Library / build identification: "mi355cd <version> gfx950". */
 const char *cd_version(void);
 
