@@ -388,7 +388,7 @@ int cd_multi_step(cd_multi *m, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_
     if (!local_err && (m->flags & CD_MULTI_INJECT_FAILURE)) local_err = CD_ERR_INJECTED;   // test hook: this rank's next step fails locally
     m->flags &= ~CD_MULTI_INJECT_FAILURE;
     if (!local_err && m->slab_cap < m->qcap) { const int rc = multi_slabs(m); if (rc) local_err = rc; }   // a growth of an earlier step whose allocation failed here: again, before anything is packed
-    auto late = [&](int rc) { m->sticky_err = rc; c->scratch_clean = false; hipStreamSynchronize(s); hipStreamSynchronize(m->xstream); return rc; };   // an error AFTER the decision: returned, and published by the next step
+    auto late = [&](int rc) { m->sticky_err = rc; c->left.scratch_clean = false; hipStreamSynchronize(s); hipStreamSynchronize(m->xstream); return rc; };   // an error AFTER the decision: returned, and published by the next step
 #define LATE_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return late(-(int)e_); } while (0)
 #define SOFT_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess && !local_err) local_err = -(int)e_; } while (0)
 
@@ -435,7 +435,7 @@ int cd_multi_step(cd_multi *m, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_
             QuerySrc src{c->d_leaf, c->d_boxes, c->d_qbox, c->d_root, nullptr, nullptr, c->d_os_ticket + 8};
             // (the fused build has just zeroed the traversal counters itself -- ZeroPlan, cd_build.h -- unless the sort took a form that
             //  goes without; a memset here sits between the tree and the traversal: 12 us of the step)
-            if (!c->scratch_clean) HIPCHK(hipMemsetAsync(t0.d_state, 0, sizeof(TravState), s));
+            if (!c->left.scratch_clean) HIPCHK(hipMemsetAsync(t0.d_state, 0, sizeof(TravState), s));
             launch_pass<false, false>(c, t0, src, c->nt, cap);
             rc = enqueue_report(c, t0, pairs != nullptr, spec0);
             if (rc) return rc;
@@ -507,7 +507,7 @@ int cd_multi_step(cd_multi *m, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_
         // step starts from scratch.
         hipStreamSynchronize(s); hipStreamSynchronize(xs);
         (void)hipGetLastError();
-        c->scratch_clean = false; c->prezeroed = false;
+        c->left.scratch_clean = false; c->prezeroed = false;
         if (info) { info->world = (uint32_t)W; info->rank = (uint32_t)me; info->host_syncs = syncs; info->attempts = attempts + 1; info->query_cap = m->qcap;
                     info->failed_rank_plus1 = failed_rank >= 0 && failed_rank < W ? (uint32_t)failed_rank + 1u : 0u; }
         if (n_pairs) *n_pairs = 0;

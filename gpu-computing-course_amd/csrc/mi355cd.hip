@@ -87,7 +87,6 @@ struct cd_ctx {
     LeafTri *d_leaf = nullptr; NodeMeta *d_meta = nullptr; int32_t *d_parent = nullptr; double *d_seg = nullptr; float *d_seg32 = nullptr; uint32_t nbp2 = 1; int32_t *d_cross = nullptr; uint32_t cross_cap = 0;   // segment tree over leaf boxes: nbp2*512 heap nodes
     double *d_boxes = nullptr; uint32_t *d_bounded = nullptr; NodeRec32 *d_recs32 = nullptr; LeafBox32 *d_qbox = nullptr;
     unsigned long long *d_leaf_side = nullptr;   // fused build: one bit a leaf -- its box is in the left half of recs[j] (else the right half of recs[j - 1]); what k_cross_fused reads instead of qbox[]
-    bool qbox_valid = false;                // d_qbox holds THIS tree's query boxes (the fused build stores them only when somebody is known to read them: qbox_wanted / ensure_qbox)
     uint32_t dbg_big_offsets = 0;           // CD_DBG_BIG_OFFSETS: k_descend_half's 64-bit-address instance whatever n is (tests)
     uint32_t dbg_store_qbox = 0;            // CD_DBG_STORE_QBOX: the fused build always stores qbox[] (A/B, tests)
     // the cell table of the current vertices (cd_bvh.h AmbTable; amb_refresh): keys == nullptr while every coordinate is an fp32 value
@@ -96,11 +95,7 @@ struct cd_ctx {
     bool cell_table_opt = true;             // CD_OPT_CELL_TABLE
     uint8_t *d_vamb = nullptr, *vamb = nullptr;   // per vertex: which of its three coordinates lie in ambiguous cells (vamb: d_vamb, or nullptr while there is no table)
     int32_t *d_root = nullptr;              // name (split) of the root record, one word inside d_small
-    bool leaf_records_filled = false;       // leaf[] holds the sorted triangles (leaves_filled: and parent[] / bounded[] are reset)
-    bool internal_boxes_valid = false;      // the FP64 boxes of the internal nodes were written by the last refit (fused calls skip them)
     int32_t *d_split_of = nullptr;          // fused build: split of every internal node (child links of the records)
-    bool hierarchy_valid = false;           // meta[] / parent[] hold the tree of the current keys (fused calls build the records without them)
-    bool last_tree_fused = false;           // the last fused call built hierarchy + refit in one pass (ms_hierarchy is then part of ms_refit)
     uint32_t stamp_mask = 15;               // CD_OPT_KERNEL_STAMPS: with stage timing off, which time stamps a fused call still takes (1 block build, 2 descent, 4 exact, 8 pipeline start): ~5 us of idle GPU each
     uint32_t dbg_sort_windows = 0;          // CD_DBG_SORT_WINDOWS: 0 the form the size asks for, 1 always the large window form of k_local_sort, 2 always the small one (A/B, tests)
     bool left_frame = false; uint32_t steps_in_mode1 = 0;    // the sort went from its first form to its second because keys lay beyond bit 59 (not for a long run); sorts since then
@@ -115,12 +110,25 @@ struct cd_ctx {
     uint64_t *pp_keys[2] = {nullptr, nullptr}; uint32_t *pp_vals[2] = {nullptr, nullptr}; uint32_t *pp_flags = nullptr;
     void *pp_os = nullptr; size_t pp_os_bytes = 0; uint32_t pp_cap = 0;
     uint64_t last_pairs_on_device = 0;      // pairs of the last traversal that are resident in d_pairs
+    // What the enqueuers of a step leave behind ON THE HOST for whoever comes next.  A replayed graph runs no enqueuer, so graph_step puts this record (and stats.sort_passes) back as
+    // its capture left it: a flag an enqueuer sets for later readers belongs HERE, or a replay differs from the stream path.  Written while enqueueing too, and deliberately outside:
+    // order_ready and local_small_ok are part of the graph's KEY (a change captures again; local_small_active follows local_small_ok and CD_DBG_SORT_WINDOWS, both in the key),
+    // order_pending is set and taken inside one enqueue_refit, top_seq and report_seq are counters a kernel compares against (never set back), last_pairs_on_device is
+    // written by graph_step itself.
+    struct StepLeft {
+        bool leaves_filled = false;         // the sort's fix-up hop already wrote leaf[], parent = -1, bounded = 0
+        bool leaf_records_filled = false;   // leaf[] holds the sorted triangles (leaves_filled: and parent[] / bounded[] are reset)
+        bool hierarchy_valid = false;       // meta[] / parent[] hold the tree of the current keys (fused calls build the records without them)
+        bool internal_boxes_valid = false;  // the FP64 boxes of the internal nodes were written by the last refit (fused calls skip them)
+        bool last_tree_fused = false;       // the last fused call built hierarchy + refit in one pass (ms_hierarchy is then part of ms_refit)
+        bool events_ride = false;           // the last pass recorded EV_TRAV0 / EV_DESC1 / EV_TRAV1 through its kernels' dispatch packets
+        bool scratch_clean = false;         // the kernels of the last fused step left the scratch block zeroed (ZeroPlan, cd_build.h): the next one needs no memset at all
+        bool qbox_valid = false;            // d_qbox holds THIS tree's query boxes (the fused build stores them only when somebody is known to read them: qbox_wanted / ensure_qbox)
+    } left;
     // host mirrors
     cd_stats stats = {};
     uint32_t sort_flags[9] = {};            // [0..7] look-back time-out words of the last sort, [8] half-key fix-up overflow; refreshed by read_state()
     bool stage_events = true;               // CD_OPT_STAGE_TIMING
-    bool leaves_filled = false;             // the sort's fix-up hop already wrote leaf[], parent = -1, bounded = 0
-    bool events_ride = false;               // the last pass recorded EV_TRAV0 / EV_DESC1 / EV_TRAV1 through its kernels' dispatch packets
     uint32_t dbg_report_copies = 0;        // CD_DBG_REPORT_COPIES: the report kernel copies the first pairs to the host (32 workgroups) instead of the exact kernel posting them (A/B)
     bool order_hint_large = false;          // CD_OPT_ORDER_HINT 2: also for trees of more than 1 M leaves (sorted chunk by chunk; measured slower there)
     bool order_hint = true;                 // CD_OPT_ORDER_HINT: the half traversal takes its groups of 64 leaves longest-first, by the previous step's times (cd_bvh.h, build_half_order)
@@ -130,7 +138,6 @@ struct cd_ctx {
     uint8_t *d_tri_cost = nullptr;          // per triangle (original index): the time class its wave left in the last half traversal
     bool prezeroed = false;                 // fused path: the scratch block was zeroed by one memset at pipeline start
     hipEvent_t tree_done_event = nullptr;   // set by the multi-GPU step: taken (and cleared) by the launch that completes the tree, if it can carry it
-    bool scratch_clean = false;             // ... or by the kernels of the previous fused step (ZeroPlan, cd_build.h): no memset at all
     bool quiet_pass = false;                // launch_pass records no events (a pass on another stream, beside the one whose times are reported)
     int sort_mode = 0;                      // 0 hybrid on key bits 44..59 (every in-frame Morton key is below 2^60), 1 hybrid on bits 48..63 (2 global passes + in-LDS sort of the windows + fix-up), 2 half-key (4 passes + fix-up),
                                             // 2 full (8 passes); forced by CD_OPT_SORT_FULL, or escalated after an overflow on this context
@@ -150,7 +157,7 @@ struct cd_ctx {
     uint32_t poll_stale = 0;
     hipGraph_t graph = nullptr; hipGraphExec_t graph_exec = nullptr;
     struct GraphKey { uint64_t cap, spec_n; int sort_mode, variant, frame_mode; uint32_t nt, exact_blocks, dbg; const void *p_pairs, *p_cand, *p_defer, *p_report; uint64_t cand_cap; uint32_t defer_cap, pad; } graph_key = {};   // (no padding bytes: compared with memcmp)
-    struct GraphPost { bool leaves_filled, leaf_records_filled, hierarchy_valid, internal_boxes_valid, last_tree_fused, events_ride, scratch_clean, qbox_valid; uint32_t sort_passes; } graph_post = {};
+    struct GraphPost { StepLeft left; uint32_t sort_passes; } graph_post = {};   // what the captured step's enqueuers left on the host: a replay runs none of them
     uint64_t graph_replays = 0, graph_captures = 0;
     bool all_verts_referenced = false;      // every vertex belongs to a triangle (checked at cd_create; the topology never changes afterwards)
     int wall_clock_khz = 0;                 // hipDeviceAttributeWallClockRate: ticks of s_memrealtime per millisecond
@@ -348,7 +355,6 @@ inline hipError_t evrec(cd_ctx *c, int idx)
 struct Prezeroed {                          // scope of a fused call: stage memsets are replaced by the one in enqueue_morton_sort
     cd_ctx *c;
     explicit Prezeroed(cd_ctx *c_) : c(c_) { c->prezeroed = true; }
-    void done() { c->prezeroed = false; }
     ~Prezeroed() { c->prezeroed = false; }
 };
 
@@ -372,8 +378,8 @@ int enqueue_morton_sort(cd_ctx *c, bool links_too = true, bool frame_ready = fal
     // ... unless the previous fused step's own kernels have left the sort scratch zeroed and this step's kernels zero
     // the rest (k_local_sort: the small counters, k_build_block: the traversal counters; ZeroPlan, cd_build.h)
     const bool self_cleaning = c->prezeroed && c->sort_mode <= 1 && fused_build_next(c);
-    const bool skip_memset = self_cleaning && c->scratch_clean;
-    c->scratch_clean = false;
+    const bool skip_memset = self_cleaning && c->left.scratch_clean;
+    c->left.scratch_clean = false;
     if (!skip_memset) HIPCHK(hipMemsetAsync(c->d_os, 0, c->sort_mode <= 1 ? (c->prezeroed ? c->zero_bytes : c->sort_hi_bytes) : c->os_bytes, s));
     // Three forms of the same stable 64-bit sort (cd_sort.h): hybrid = 2 global passes on the top 16 bits + an in-LDS
     // sort of run-aligned windows + the fix-up hop; half-key = 4 global passes on the high 32 bits + the fix-up hop;
@@ -407,7 +413,7 @@ int enqueue_morton_sort(cd_ctx *c, bool links_too = true, bool frame_ready = fal
                                                     pass == first_digit && chunked ? c->d_chunk_tot : nullptr);
         cur ^= 1;
     }
-    c->leaves_filled = false; c->leaf_records_filled = false;
+    c->left.leaves_filled = false; c->left.leaf_records_filled = false;
     if (hybrid) {                               // data is in buffer 1 again; windows go 1 -> 0, fix-up hop and leaf fill in the kernel's epilogue
         const LeafFill fill{c->d_vidx, c->d_ids, n, c->d_leaf, links_too ? c->d_parent : nullptr, links_too ? c->d_bounded : nullptr};
         // one workgroup per CU is all this kernel's LDS allows: the windows are n / 256 keys when that is less than their nominal
@@ -427,13 +433,13 @@ int enqueue_morton_sort(cd_ctx *c, bool links_too = true, bool frame_ready = fal
             k_local_sort<LeafFill, LocalLarge><<<cdiv(n, win), LocalLarge::THREADS, 0, s>>>(c->d_keys[1], c->d_perm[1], c->d_keys[0], c->d_perm[0], n, 48 - down, c->d_os_ticket + 16, fill,
                                                                                             self_cleaning ? c->d_small : nullptr, self_cleaning ? 128u : 0u, win);
         }
-        c->leaves_filled = links_too;
-        c->leaf_records_filled = true;
+        c->left.leaves_filled = links_too;
+        c->left.leaf_records_filled = true;
     } else if (mode != 3) {
         k_sort_fixup_fill<<<cdiv(n, 256), 256, 0, s>>>(c->d_keys[1], c->d_perm[1], c->d_keys[0], c->d_perm[0], n, c->d_os_ticket + 16,
                                                        c->d_vidx, c->d_ids, c->d_leaf, links_too ? c->d_parent : nullptr, links_too ? c->d_bounded : nullptr);
-        c->leaves_filled = links_too;           // by the fix-up hop; enqueue_hierarchy runs k_fill_leaves otherwise
-        c->leaf_records_filled = true;
+        c->left.leaves_filled = links_too;           // by the fix-up hop; enqueue_hierarchy runs k_fill_leaves otherwise
+        c->left.leaf_records_filled = true;
     }
     c->stats.sort_passes = hybrid ? 2 : (mode == 2 ? 4 : 8);
     HIPCHK(evrec(c, EV_SORT1));
@@ -448,12 +454,12 @@ int enqueue_hierarchy(cd_ctx *c, bool poison_boxes)
     HIPCHK(evrec(c, EV_HIER0));
     if (!c->prezeroed) HIPCHK(hipMemsetAsync(c->d_small, 0, 16 * sizeof(uint32_t), s));
     // (a repeated cd_build_hierarchy needs the parent links reset again: the flag is good for one use)
-    if (!c->leaves_filled || poison_boxes)
+    if (!c->left.leaves_filled || poison_boxes)
         k_fill_leaves<<<cdiv(n, 256), 256, 0, s>>>(c->d_perm[0], c->d_vidx, c->d_ids, n, c->d_leaf, c->d_parent, c->d_bounded, poison_boxes ? c->d_boxes : nullptr);
-    c->leaves_filled = false;
+    c->left.leaves_filled = false;
     if (n > 1)
         k_hierarchy<<<cdiv(n - 1, 256), 256, 0, s>>>(c->d_keys[0], (int)n, c->d_meta, c->d_parent, c->d_small);
-    c->hierarchy_valid = true;
+    c->left.hierarchy_valid = true;
     HIPCHK(evrec(c, EV_HIER1));
     HIPCHK(hipGetLastError());
     return 0;
@@ -470,10 +476,10 @@ static bool qbox_wanted(const cd_ctx *c)
 }
 int ensure_qbox(cd_ctx *c)
 {
-    if (c->qbox_valid) return 0;
+    if (c->left.qbox_valid) return 0;
     k_fill_qbox<<<cdiv(c->nt, 256), 256, 0, c->stream>>>(c->d_verts, c->d_leaf, (int)c->nt, c->d_qbox, c->amb, (const uint8_t *)c->vamb);
     HIPCHK(hipGetLastError());
-    c->qbox_valid = true;
+    c->left.qbox_valid = true;
     return 0;
 }
 int enqueue_refit(cd_ctx *c, bool write_internal, bool fused = false)
@@ -487,10 +493,10 @@ int enqueue_refit(cd_ctx *c, bool write_internal, bool fused = false)
     uint32_t *cross_count = c->d_small + 16;
     if (!c->prezeroed) HIPCHK(hipMemsetAsync(cross_count, 0, 64 * sizeof(uint32_t), s));
     if (fused) {
-        if (!c->leaf_records_filled)                 // (the 8-pass sort does not fill the leaves; enqueue_hierarchy would have)
+        if (!c->left.leaf_records_filled)                 // (the 8-pass sort does not fill the leaves; enqueue_hierarchy would have)
             k_fill_leaves<<<cdiv(n, 256), 256, 0, s>>>(c->d_perm[0], c->d_vidx, c->d_ids, n, c->d_leaf, c->d_parent, c->d_bounded, nullptr);
-        c->leaves_filled = false; c->leaf_records_filled = true;
-        c->hierarchy_valid = false;
+        c->left.leaves_filled = false; c->left.leaf_records_filled = true;
+        c->left.hierarchy_valid = false;
         // (its time stamps ride on its own dispatch packet: this is the largest kernel of the step, bench.py prices it)
         const bool stamp = (c->stamp_mask & 1u) != 0;
         const bool self_cleaning = c->prezeroed && c->sort_mode <= 1;
@@ -508,7 +514,7 @@ int enqueue_refit(cd_ctx *c, bool write_internal, bool fused = false)
         const bool hint = c->order_hint && c->trav_variant >= 3 && n > 64u && c->nbp2 > 1 && !c->dbg_split_cross && (c->nbp2 <= (uint32_t)TOP_IN_BLOCK || c->order_hint_large);
         const uint32_t *hp = hint ? c->d_perm[0] : nullptr; const uint8_t *ht = hint ? c->d_tri_cost : nullptr; uint32_t *hc = hint ? c->d_cost : nullptr;
         const int store_q = qbox_wanted(c) ? 1 : 0;
-        c->qbox_valid = store_q != 0;
+        c->left.qbox_valid = store_q != 0;
         if (stamp)
             hipExtLaunchKernelGGL(k_build_block, dim3(nblocks), dim3(REFIT_BLK), 0u, s, c->ev[EV_BLK0], c->ev[EV_BLK1], 0u,
                                   (const double *)c->d_verts, (const LeafTri *)c->d_leaf, (int)n, (const uint64_t *)c->d_keys[0], c->d_split_of,
@@ -519,9 +525,9 @@ int enqueue_refit(cd_ctx *c, bool write_internal, bool fused = false)
                                                         c->d_seg, c->d_seg32, (int)c->nbp2, cross_list, cross_count, c->cross_cap, zp, seg_min, c->amb, (const uint8_t *)c->vamb,
                                                         hp, ht, hc, c->d_leaf_side, store_q);
         c->order_pending = hint;
-        c->scratch_clean = self_cleaning;       // (judge_sort_flags takes it back when the sort has raised a flag)
+        c->left.scratch_clean = self_cleaning;       // (judge_sort_flags takes it back when the sort has raised a flag)
     } else {
-        c->qbox_valid = true;
+        c->left.qbox_valid = true;
         k_refit_seg_local<<<nblocks, REFIT_BLK, 0, s>>>(c->d_verts, c->d_leaf, (int)n, c->d_meta, c->d_boxes, c->d_bounded,
                                                        c->d_recs32, c->d_qbox, c->d_root, write_internal ? 1 : 0, c->d_seg, (int)c->nbp2,
                                                        cross_list, cross_count, c->cross_cap, c->amb, (const uint8_t *)c->vamb);
@@ -555,7 +561,7 @@ int enqueue_refit(cd_ctx *c, bool write_internal, bool fused = false)
                                                             c->d_recs32, c->d_split_of, c->d_root, c->d_cross, cross_count, c->cross_cap, c->d_top_pub, top_flag, c->top_seq,
                                                             nord, ogroups, c->d_cost, c->d_order);
         if (nord) c->order_ready = true;
-        c->internal_boxes_valid = write_internal;
+        c->left.internal_boxes_valid = write_internal;
         HIPCHK(evrec(c, EV_REFIT1));
         HIPCHK(hipGetLastError());
         return 0;
@@ -585,7 +591,7 @@ int enqueue_refit(cd_ctx *c, bool write_internal, bool fused = false)
     } else if (n > 1)
         k_refit_seg_cross<<<xblocks, 256, 0, s>>>((int)n, c->d_meta, c->d_seg, (int)c->nbp2, c->d_boxes, c->d_bounded, c->d_recs32,
                                                   c->d_root, write_internal ? 1 : 0, c->d_cross, cross_count, c->cross_cap, c->amb);
-    c->internal_boxes_valid = write_internal;
+    c->left.internal_boxes_valid = write_internal;
     HIPCHK(evrec(c, EV_REFIT1));
     HIPCHK(hipGetLastError());
     return 0;
@@ -596,13 +602,13 @@ int enqueue_refit(cd_ctx *c, bool write_internal, bool fused = false)
 static bool fused_build_next(const cd_ctx *c) { return !(c->trav_variant == 0 || c->dbg_no_fused_build); }
 int enqueue_tree(cd_ctx *c)
 {
-    c->last_tree_fused = false;
+    c->left.last_tree_fused = false;
     if (!fused_build_next(c)) {
         int rc = enqueue_hierarchy(c, false);
         if (!rc) rc = enqueue_refit(c, c->trav_variant == 0, false);
         return rc;
     }
-    c->last_tree_fused = true;
+    c->left.last_tree_fused = true;
     return enqueue_refit(c, false, true);
 }
 
@@ -668,7 +674,7 @@ void launch_pass(cd_ctx *c, TravBuf &tb, const QuerySrc &src, uint32_t items, ui
             hipExtLaunchKernelGGL((k_exact<EXTERNAL>), dim3(c->exact_blocks), dim3(EXACT_THREADS), 0u, s, nullptr, e2, 0u,
                                   src, n, (const LeafTri *)c->d_leaf, (const double *)c->d_boxes, (const double *)c->d_verts, vb, (const Candidates *)tb.d_cand,
                                   (unsigned long long)shard_cap, tb.d_pairs, (unsigned long long)cap_pairs, tb.d_state, half, post, post_n);
-        c->events_ride = ride;
+        c->left.events_ride = ride;
     }
 }
 
@@ -826,8 +832,8 @@ int run_traversal(cd_ctx *c, TravBuf &tb, const void *d_ext, uint64_t nq_ext, ui
     int rc = ensure_pairs(c, tb, cap_pairs > 0 ? cap_pairs : 1);
     if (rc) return rc;
     const int per_pass = c->trav_variant == 0 ? 1 : 2;             // descent + exact kernel
-    if (c->trav_variant == 0 && !(c->internal_boxes_valid && c->hierarchy_valid)) {   // variant 0 walks meta[] and the FP64 boxes of the internal nodes
-        if (!c->hierarchy_valid && (rc = enqueue_hierarchy(c, false))) return rc;
+    if (c->trav_variant == 0 && !(c->left.internal_boxes_valid && c->left.hierarchy_valid)) {   // variant 0 walks meta[] and the FP64 boxes of the internal nodes
+        if (!c->left.hierarchy_valid && (rc = enqueue_hierarchy(c, false))) return rc;
         if ((rc = enqueue_refit(c, true, false))) return rc;
     }
     // (the from-the-root descent reads its query boxes from qbox[], k_exact the leaf boxes of candidates that are not certain -- external queries against a tree whose
@@ -843,7 +849,7 @@ int run_traversal(cd_ctx *c, TravBuf &tb, const void *d_ext, uint64_t nq_ext, ui
         launches = 0; deep_ms = 0.f;
         QuerySrc src{c->d_leaf, c->d_boxes, c->d_qbox, c->d_root, d_ext, nullptr, c->d_os_ticket + 8};
         const bool will_ride = !c->stage_events && (c->trav_variant == 1 || c->trav_variant >= 3) && nq > 0;   // see launch_pass: events on the dispatch packets
-        c->events_ride = false;
+        c->left.events_ride = false;
         if (!will_ride) HIPCHK(evrec(c, EV_TRAV0));
         if (!(c->prezeroed && attempt == 0 && &tb == &c->tb[0])) HIPCHK(hipMemsetAsync(tb.d_state, 0, sizeof(TravState), s));
         const uint64_t spec_n = pairs ? (cap_pairs < SPEC_PAIRS ? cap_pairs : SPEC_PAIRS) : 0;
@@ -853,7 +859,7 @@ int run_traversal(cd_ctx *c, TravBuf &tb, const void *d_ext, uint64_t nq_ext, ui
             if (external) launch_pass<true, false>(c, tb, src, nq, cap_pairs); else launch_pass<false, false>(c, tb, src, nq, cap_pairs);
             launches += per_pass;
         }
-        if (!c->events_ride) HIPCHK(evrec(c, EV_TRAV1));      // device time of the kernels only: recorded before the read-back
+        if (!c->left.events_ride) HIPCHK(evrec(c, EV_TRAV1));      // device time of the kernels only: recorded before the read-back
         if ((rc = read_state(c, tb, h, pairs, spec_n, pinned_pairs_id(pairs, cap_pairs)))) return rc;
         spec_valid = spec_n;
         if (shards_overflowed(tb, h)) { if ((rc = grow_shards(c, tb, h))) return rc; continue; }
@@ -900,7 +906,7 @@ int run_traversal(cd_ctx *c, TravBuf &tb, const void *d_ext, uint64_t nq_ext, ui
         HIPCHK(hipStreamSynchronize(s));
     }
     // (a time stamp that was not taken in this call must not be read: the event holds an earlier call's)
-    const bool have_d = !c->events_ride || (c->stamp_mask & 2u), have_x = !c->events_ride || (c->stamp_mask & 4u);
+    const bool have_d = !c->left.events_ride || (c->stamp_mask & 2u), have_x = !c->left.events_ride || (c->stamp_mask & 4u);
     c->stats.ms_traverse = (have_d && have_x) ? elapsed(c, EV_TRAV0, EV_TRAV1) + deep_ms : 0.f;
     c->stats.ms_descend = (c->trav_variant != 0 && nq > 0 && have_d) ? elapsed(c, EV_TRAV0, EV_DESC1) : 0.f;
     c->stats.ms_exact = (c->trav_variant != 0 && nq > 0 && have_d && have_x) ? elapsed(c, EV_DESC1, EV_TRAV1) : 0.f;
@@ -1006,7 +1012,7 @@ int amb_refresh(cd_ctx *c)
 bool graph_eligible(const cd_ctx *c)
 {
     return c->graph_opt && !c->stage_events && c->stamp_mask == 0 && c->sort_mode <= 1 && fused_build_next(c) && c->trav_variant == 3 &&
-           c->scratch_clean && !c->dbg_diag && !c->dbg_lds_pad && c->nt > 1 && c->tree_done_event == nullptr;
+           c->left.scratch_clean && !c->dbg_diag && !c->dbg_lds_pad && c->nt > 1 && c->tree_done_event == nullptr;
 }
 int graph_step(cd_ctx *c, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, bool &handled)
 {
@@ -1035,20 +1041,16 @@ int graph_step(cd_ctx *c, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs
         c->prezeroed = false;
         hipGraph_t g = nullptr;
         const hipError_t ee = hipStreamEndCapture(s, &g);
-        if (rc || ee != hipSuccess || !g) { if (g) hipGraphDestroy(g); (void)hipGetLastError(); c->scratch_clean = false; return CD_OK; }   // (not handled: the stream path runs, with its memset)
+        if (rc || ee != hipSuccess || !g) { if (g) hipGraphDestroy(g); (void)hipGetLastError(); c->left.scratch_clean = false; return CD_OK; }   // (not handled: the stream path runs, with its memset)
         c->graph = g;
-        if (hipGraphInstantiate(&c->graph_exec, g, nullptr, nullptr, 0) != hipSuccess) { graph_drop(c); (void)hipGetLastError(); c->scratch_clean = false; return CD_OK; }
+        if (hipGraphInstantiate(&c->graph_exec, g, nullptr, nullptr, 0) != hipSuccess) { graph_drop(c); (void)hipGetLastError(); c->left.scratch_clean = false; return CD_OK; }
         std::memset(&c->graph_key, 0, sizeof c->graph_key);
         c->graph_key = key;
-        c->graph_post = cd_ctx::GraphPost{c->leaves_filled, c->leaf_records_filled, c->hierarchy_valid, c->internal_boxes_valid, c->last_tree_fused, c->events_ride, c->scratch_clean, c->qbox_valid,
-                                          c->stats.sort_passes};
+        c->graph_post = {c->left, c->stats.sort_passes};
         ++c->graph_captures;
     }
     // what the enqueue functions leave behind on the host side, as the capture left it
-    const cd_ctx::GraphPost &gp = c->graph_post;
-    c->leaves_filled = gp.leaves_filled; c->leaf_records_filled = gp.leaf_records_filled; c->hierarchy_valid = gp.hierarchy_valid;
-    c->internal_boxes_valid = gp.internal_boxes_valid; c->last_tree_fused = gp.last_tree_fused; c->events_ride = gp.events_ride; c->scratch_clean = gp.scratch_clean; c->qbox_valid = gp.qbox_valid;
-    c->stats.sort_passes = gp.sort_passes;
+    c->left = c->graph_post.left; c->stats.sort_passes = c->graph_post.sort_passes;
     HIPCHK(hipGraphLaunch(c->graph_exec, s));
     HIPCHK(hipStreamSynchronize(s));
     ++c->graph_replays;
@@ -1058,7 +1060,7 @@ int graph_step(cd_ctx *c, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs
     { const int js = judge_sort_flags(c); if (js != CD_OK) return CD_OK; }                 // (not handled: the stream path redoes the step in the sort's next form)
     if (shards_overflowed(tb, h) || h.n_deferred > 0) {             // the tree is fine: the traversal again, with the stream path's retries / deep pass
         handled = true;
-        c->scratch_clean = false;
+        c->left.scratch_clean = false;
         return run_traversal(c, tb, nullptr, 0, pairs, cap_pairs, n_pairs);
     }
     handled = true;
@@ -1242,7 +1244,7 @@ constexpr int SORT_REDO = 77;                   // internal: this form of the so
 constexpr int SORT_REDO_MAX = 4;                // redos one call can need: small windows -> large windows -> half-key -> full is three (judge_sort_flags); one to spare
 namespace { int judge_sort_flags(cd_ctx *c)
 {
-    for (int i = 0; i < 9; ++i) if (c->sort_flags[i]) c->scratch_clean = false;     // the flag words are cleared by the memset only
+    for (int i = 0; i < 9; ++i) if (c->sort_flags[i]) c->left.scratch_clean = false;     // the flag words are cleared by the memset only
     for (int i = 0; i < 8; ++i) if (c->sort_flags[i]) return CD_ERR_SORT;
     const uint32_t f = c->sort_flags[8];
     if (!f) return CD_OK;
@@ -1266,22 +1268,63 @@ static void sort_retry_tick(cd_ctx *c)
 {
     if (c->sort_mode == 1 && c->left_frame && ++c->steps_in_mode1 >= SORT_RETRY_STEPS) { c->sort_mode = 0; c->steps_in_mode1 = 0; c->local_small_ok = true; graph_drop(c); }   // (the second form's runs are 16 x longer: the small windows get their chance again too)
 }
-static int check_sort_flags(cd_ctx *c)
+extern "C++" {                                  // (templates: the enqueued sequence is a parameter)
+// The sort's redo policy, in ONE place.  `attempt` enqueues one try of whatever contains the sort and ends in a synchronise that has brought the sort's flag words to the host
+// (c->sort_flags); negative is an error, anything else the attempt's own result, which the caller gets back once the flags are clean.  A raised flag: judge_sort_flags has
+// changed the form, the attempt runs again.
+template <class Attempt> static int with_sort_redo(cd_ctx *c, Attempt attempt)
+{
+    for (int redo = 0;; ++redo) {
+        const int rc = attempt();
+        if (rc < 0) return rc;
+        const int js = judge_sort_flags(c);
+        if (js != SORT_REDO) return js ? js : rc;
+        if (redo == SORT_REDO_MAX) return CD_ERR_SORT;
+    }
+}
+// The read-back a fused step ends in when nothing else brings them: the sort's flag words (d_os_ticket[8..16]) and the root box, then the synchronise.
+static int sync_with_flags(cd_ctx *c)
 {
     HIPCHK(hipMemcpyAsync(c->sort_flags, c->d_os_ticket + 8, sizeof c->sort_flags, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->root_box_host, c->d_boxes, sizeof(double) * 6, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    return judge_sort_flags(c);
+    return CD_OK;
+}
+// One fused step: sort + tree with one memset for every counter of the pipeline (Prezeroed, closed before a redo is decided and opened again for it), then `tail`, which
+// enqueues whatever rides behind the tree and ENDS IN A SYNCHRONISE THAT HAS BROUGHT THE SORT FLAGS AND THE ROOT BOX TO THE HOST (sync_with_flags, or a traversal's report).
+// Returns the tail's result (it may be CD_OVERFLOW) once the tree stands; what follows a good step is the caller's.
+template <class Tail> static int fused_step(cd_ctx *c, Tail tail)
+{
+    const int rc = with_sort_redo(c, [&]() -> int {
+        Prezeroed fused(c);
+        int re = enqueue_morton_sort(c, !fused_build_next(c));
+        if (!re) re = enqueue_tree(c);
+        return re ? re : tail();
+    });
+    if (rc >= 0) { c->root_box_valid = true; c->stage = ST_REFIT; }
+    return rc;
+}
+}  // extern "C++"
+// events -> the stage times of a step's build (only with stage timing on are all of them recorded)
+static void read_build_times(cd_ctx *c)
+{
+    c->stats.ms_morton = elapsed(c, EV_MORTON0, EV_MORTON1);
+    c->stats.ms_sort = elapsed(c, EV_MORTON1, EV_SORT1);
+    c->stats.ms_hierarchy = c->left.last_tree_fused ? 0.f : elapsed(c, EV_HIER0, EV_HIER1);
+    c->stats.ms_refit = elapsed(c, EV_REFIT0, EV_REFIT1);
 }
 
 int cd_morton_sort(cd_ctx *c)
 {
     if (!c) return CD_ERR_ARG;
     sort_retry_tick(c);
-    int rc = enqueue_morton_sort(c);
-    if (rc) return rc;
-    rc = check_sort_flags(c);
-    for (int redo = 0; rc == SORT_REDO && redo < SORT_REDO_MAX; ++redo) { if ((rc = enqueue_morton_sort(c))) return rc; rc = check_sort_flags(c); }
-    if (rc == SORT_REDO) rc = CD_ERR_SORT;
+    const int rc = with_sort_redo(c, [c]() -> int {                            // (no tree: the flag words alone)
+        const int re = enqueue_morton_sort(c);
+        if (re) return re;
+        HIPCHK(hipMemcpyAsync(c->sort_flags, c->d_os_ticket + 8, sizeof c->sort_flags, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return CD_OK;
+    });
     if (rc) return rc;
     c->stats.ms_morton = elapsed(c, EV_MORTON0, EV_MORTON1);
     c->stats.ms_sort = elapsed(c, EV_MORTON1, EV_SORT1);
@@ -1321,9 +1364,9 @@ int cd_refit_boxes(cd_ctx *c)
 // them afterwards -- the exported tree, checkInternalNodes' uninitialised-box counter -- gets them from a full refit.
 static int materialise_internal_boxes(cd_ctx *c)
 {
-    if (c->stage < ST_REFIT || (c->internal_boxes_valid && c->hierarchy_valid)) return CD_OK;
+    if (c->stage < ST_REFIT || (c->left.internal_boxes_valid && c->left.hierarchy_valid)) return CD_OK;
     int rc = CD_OK;
-    if (!c->hierarchy_valid) rc = enqueue_hierarchy(c, false);             // k_fill_leaves (parent links reset) + k_hierarchy on the current keys
+    if (!c->left.hierarchy_valid) rc = enqueue_hierarchy(c, false);             // k_fill_leaves (parent links reset) + k_hierarchy on the current keys
     if (!rc) rc = enqueue_refit(c, true, false);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1360,72 +1403,34 @@ int cd_find_collisions(cd_ctx *c, uint32_t *pairs, uint64_t cap_pairs, uint64_t 
     return run_traversal(c, c->tb[0], nullptr, 0, pairs, cap_pairs, n_pairs);
 }
 
-static int build_tree_impl(cd_ctx *c, int redo);
 int cd_build_tree(cd_ctx *c)
 {
     if (!c) return CD_ERR_ARG;
     sort_retry_tick(c);
-    return build_tree_impl(c, 0);
-}
-static int build_tree_impl(cd_ctx *c, int redo)
-{
-    int rc;
-    Prezeroed fused(c);                                                    // one memset for every counter of the pipeline
-    rc = enqueue_morton_sort(c, !fused_build_next(c));
-    if (!rc) rc = enqueue_tree(c);
+    const int rc = fused_step(c, [c] { return sync_with_flags(c); });
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(c->sort_flags, c->d_os_ticket + 8, sizeof c->sort_flags, hipMemcpyDeviceToHost, c->stream));   // words 8..16
-    HIPCHK(hipMemcpyAsync(c->root_box_host, c->d_boxes, sizeof(double) * 6, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    rc = judge_sort_flags(c);
-    if (rc == SORT_REDO) return redo < SORT_REDO_MAX ? build_tree_impl(c, redo + 1) : CD_ERR_SORT;     // (the form has been changed: judge_sort_flags)
-    if (rc) return rc;
-    if (c->stage_events) {
-        c->stats.ms_morton = elapsed(c, EV_MORTON0, EV_MORTON1);
-        c->stats.ms_sort = elapsed(c, EV_MORTON1, EV_SORT1);
-        c->stats.ms_hierarchy = c->last_tree_fused ? 0.f : elapsed(c, EV_HIER0, EV_HIER1);
-        c->stats.ms_refit = elapsed(c, EV_REFIT0, EV_REFIT1);
-    }
-    c->root_box_valid = true;
-    c->stage = ST_REFIT;
+    if (c->stage_events) read_build_times(c);
     return CD_OK;
 }
 
-static int self_collide_impl(cd_ctx *c, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, int redo);
 int cd_self_collide(cd_ctx *c, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs)
 {
     if (!c || (cap_pairs && !pairs)) return CD_ERR_ARG;
     sort_retry_tick(c);                                                    // (before a graph step computes its key)
-    return self_collide_impl(c, pairs, cap_pairs, n_pairs, 0);
-}
-static int self_collide_impl(cd_ctx *c, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, int redo)
-{
-    int rc;
-    if (graph_eligible(c)) {                                               // CD_OPT_GRAPH: the steady-state step as one graph launch
+    // CD_OPT_GRAPH: the steady-state step as one graph launch.  (Tried once, not per redo: a redo follows a raised sort flag, for which judge_sort_flags clears scratch_clean,
+    //  and without scratch_clean no step is eligible.)
+    if (graph_eligible(c)) {
         bool handled = false;
-        rc = graph_step(c, pairs, cap_pairs, n_pairs, handled);
-        if (rc < 0 || handled) return rc;
+        const int rg = graph_step(c, pairs, cap_pairs, n_pairs, handled);
+        if (rg < 0 || handled) return rg;
     }
-    Prezeroed fused(c);                                                    // one memset for every counter of the pipeline
-    rc = enqueue_morton_sort(c, !fused_build_next(c));
-    if (!rc) rc = enqueue_tree(c);
-    if (!rc) rc = run_traversal(c, c->tb[0], nullptr, 0, pairs, cap_pairs, n_pairs);     // synchronises
-    fused.done();
+    const int rc = fused_step(c, [&] { return run_traversal(c, c->tb[0], nullptr, 0, pairs, cap_pairs, n_pairs); });     // (its report carries the flags and the root box)
     if (rc < 0) return rc;
-    { const int rs = judge_sort_flags(c);                                   // flags came back with the traversal counters
-      if (rs == SORT_REDO) return redo < SORT_REDO_MAX ? self_collide_impl(c, pairs, cap_pairs, n_pairs, redo + 1) : CD_ERR_SORT;   // (the form has been changed: judge_sort_flags)
-      if (rs) return rs; }
-    if (c->stage_events) {
-        c->stats.ms_morton = elapsed(c, EV_MORTON0, EV_MORTON1);
-        c->stats.ms_sort = elapsed(c, EV_MORTON1, EV_SORT1);
-        c->stats.ms_hierarchy = c->last_tree_fused ? 0.f : elapsed(c, EV_HIER0, EV_HIER1);
-        c->stats.ms_refit = elapsed(c, EV_REFIT0, EV_REFIT1);
-    } else c->stats.ms_morton = c->stats.ms_sort = c->stats.ms_hierarchy = c->stats.ms_refit = 0.f;
+    if (c->stage_events) read_build_times(c);
+    else c->stats.ms_morton = c->stats.ms_sort = c->stats.ms_hierarchy = c->stats.ms_refit = 0.f;
     const bool all_stamps = c->stage_events || (c->stamp_mask & 14u) == 14u;
     c->stats.ms_pipeline = all_stamps ? elapsed(c, EV_MORTON0, EV_TRAV1) + (c->stats.ms_traverse - elapsed(c, EV_TRAV0, EV_TRAV1)) : 0.f;   // + deep pass, if any
-    c->stats.ms_build_block = (c->last_tree_fused && (c->stamp_mask & 1u)) ? elapsed(c, EV_BLK0, EV_BLK1) : 0.f;
-    c->stage = ST_REFIT;
-    c->root_box_valid = true;
+    c->stats.ms_build_block = (c->left.last_tree_fused && (c->stamp_mask & 1u)) ? elapsed(c, EV_BLK0, EV_BLK1) : 0.f;
     return rc;
 }
 
@@ -1760,7 +1765,7 @@ int cd_debug_option(cd_ctx *c, int key, int64_t value, int64_t *out)
     case CD_DBG_GET_POLL_MAX_WAIT_US: if (!out) return CD_ERR_ARG; *out = c->poll_max_wait_us; return CD_OK;
     case CD_DBG_GET_GRAPH_CAPTURES: if (!out) return CD_ERR_ARG; *out = (int64_t)c->graph_captures; return CD_OK;
     case CD_DBG_GET_GRAPH_REPLAYS:  if (!out) return CD_ERR_ARG; *out = (int64_t)c->graph_replays; return CD_OK;
-    case CD_DBG_GET_TREE_WAS_FUSED: if (!out) return CD_ERR_ARG; *out = c->last_tree_fused ? 1 : 0; return CD_OK;
+    case CD_DBG_GET_TREE_WAS_FUSED: if (!out) return CD_ERR_ARG; *out = c->left.last_tree_fused ? 1 : 0; return CD_OK;
     case CD_DBG_GET_SORT_FORM:   if (out) *out = c->sort_mode; return CD_OK;
     case CD_DBG_GET_ORDER_STATE: {          // the order hint as it stands: 0 none built, 1 a permutation of the groups that differs from the plain order, 2 the plain order itself, -1 NOT a permutation (a bug)
         if (!out) return CD_ERR_ARG;
@@ -1912,28 +1917,6 @@ int cd_find_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, ui
     if ((rc = prox_buffers(c, cap_pairs))) return rc;
     return prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
 }
-static int self_proximity_impl(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested, int redo)
-{
-    int rc;
-    {
-        Prezeroed fused(c);                                                // cd_build_tree's pipeline, then the proximity pass behind it: one synchronisation
-        rc = enqueue_morton_sort(c, !fused_build_next(c));
-        if (!rc) rc = enqueue_tree(c);
-        if (!rc) rc = prox_enqueue(c, dist, cap_pairs);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(c->sort_flags, c->d_os_ticket + 8, sizeof c->sort_flags, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(c->root_box_host, c->d_boxes, sizeof(double) * 6, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    rc = judge_sort_flags(c);
-    if (rc == SORT_REDO) return redo < SORT_REDO_MAX ? self_proximity_impl(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested, redo + 1) : CD_ERR_SORT;
-    if (rc) return rc;
-    c->root_box_valid = true;
-    c->stage = ST_REFIT;
-    if (prox_overflowed(c, rc)) return prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
-    if (rc) return rc;
-    return prox_results(c, pairs, dists, cap_pairs, n_pairs, n_tested);
-}
 int cd_self_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
 {
     int rc = prox_args(c, dist, pairs, cap_pairs);
@@ -1941,7 +1924,11 @@ int cd_self_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, ui
     if ((rc = prox_buffers(c, cap_pairs))) return rc;
     sort_retry_tick(c);
     const cd_stats keep = c->stats;                                        // (the build inside does not count as a stage of the collision path)
-    rc = self_proximity_impl(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested, 0);
+    rc = fused_step(c, [&]() -> int { const int re = prox_enqueue(c, dist, cap_pairs); return re ? re : sync_with_flags(c); });   // the proximity pass behind the tree: one synchronisation
+    if (!rc) {
+        if (prox_overflowed(c, rc)) rc = prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
+        else if (!rc) rc = prox_results(c, pairs, dists, cap_pairs, n_pairs, n_tested);
+    }
     c->stats = keep;
     return rc;
 }
@@ -2077,27 +2064,6 @@ int cd_find_ccd(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs
     HIPCHK(hipStreamSynchronize(c->stream));
     return ccd_finish(c, dist, pairs, toi, dists, cap_pairs, n_pairs, info);
 }
-static int self_ccd_impl(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
-                         cd_ccd_info *info, int redo)
-{
-    int rc;
-    {
-        Prezeroed fused(c);                                                // cd_build_tree's pipeline, then the CCD pass behind it: one synchronisation
-        rc = enqueue_morton_sort(c, !fused_build_next(c));
-        if (!rc) rc = enqueue_tree(c);
-        if (!rc) rc = ccd_enqueue(c, verts_end, dist, cap_pairs);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(c->sort_flags, c->d_os_ticket + 8, sizeof c->sort_flags, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(c->root_box_host, c->d_boxes, sizeof(double) * 6, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    rc = judge_sort_flags(c);
-    if (rc == SORT_REDO) return redo < SORT_REDO_MAX ? self_ccd_impl(c, verts_end, dist, pairs, toi, dists, cap_pairs, n_pairs, info, redo + 1) : CD_ERR_SORT;
-    if (rc) return rc;
-    c->root_box_valid = true;
-    c->stage = ST_REFIT;
-    return ccd_finish(c, dist, pairs, toi, dists, cap_pairs, n_pairs, info);
-}
 int cd_self_ccd(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
                 cd_ccd_info *info)
 {
@@ -2106,7 +2072,8 @@ int cd_self_ccd(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs
     if ((rc = ccd_buffers(c, cap_pairs))) return rc;
     sort_retry_tick(c);
     const cd_stats keep = c->stats;                                        // (the build inside does not count as a stage of the collision path)
-    rc = self_ccd_impl(c, verts_end, dist, pairs, toi, dists, cap_pairs, n_pairs, info, 0);
+    rc = fused_step(c, [&]() -> int { const int re = ccd_enqueue(c, verts_end, dist, cap_pairs); return re ? re : sync_with_flags(c); });   // the CCD pass behind the tree: one synchronisation
+    if (!rc) rc = ccd_finish(c, dist, pairs, toi, dists, cap_pairs, n_pairs, info);
     c->stats = keep;
     return rc;
 }

@@ -1306,6 +1306,46 @@ def test_sort_returns_to_its_first_form_when_the_mesh_is_back_inside_the_frame()
         assert np.array_equal(keys, r_in["keys"]) and np.array_equal(perm, r_in["perm"])
 
 
+@pytest.mark.parametrize("entry", ["build_tree", "self_proximity", "self_ccd"])
+def test_mesh_leaving_the_frame_redoes_the_sort_through_every_stepping_entry_point(entry):
+    """The same mesh as above, but the FIRST call after the vertices have left the frame goes through cd_build_tree / cd_self_proximity / cd_self_ccd: each
+    must redo its step in the second form by itself and return what the same query returns on a context that was stepped stage-wise (cd_morton_sort +
+    cd_build_hierarchy + cd_refit_boxes + cd_find_*), bit for bit (pairs as sorted lists: their order in the buffer is an atomicAdd race)."""
+    verts, vidx = synth.cloth_pair(90)
+    out = verts.copy(); out[verts.shape[0] // 2:, 0] += 0.2
+    end = out + 1e-3 * np.sin(7.0 * out[:, [2, 0, 1]])
+    keys_out = oracle.centroid_morton(out, vidx)
+    assert (keys_out >> np.uint64(60)).max() > 0
+
+    def by_pair(p, *cols):
+        o = np.argsort((p[:, 0].astype(np.uint64) << np.uint64(32)) | p[:, 1], kind="stable")
+        return [p[o]] + [c[o].view(np.uint64) for c in cols]
+
+    def query(cd, fused):
+        if entry == "build_tree":
+            if fused:
+                cd.build_tree()
+            pairs, n, rc = cd.find_collisions(cap=1 << 20)
+            return by_pair(pairs), n, rc, cd.export_keys()
+        if entry == "self_proximity":
+            pairs, dists, n, rc = cd.self_proximity(0.01) if fused else cd.find_proximity(0.01)
+            return by_pair(pairs, dists), n, rc, cd.export_keys()
+        pairs, toi, dists, n, rc = cd.self_ccd(end, 1e-4) if fused else cd.find_ccd(end, 1e-4)
+        return by_pair(pairs, toi, dists), n, rc, cd.export_keys()
+
+    with mi355cd.CollisionDetector(out, vidx) as sw:
+        sw.morton_sort(); sw.build_hierarchy(); sw.refit_boxes()
+        want, wn, wrc, (wkeys, wperm) = query(sw, False)
+    assert wrc == 0 and wn > 0 and np.array_equal(wkeys, np.sort(keys_out, kind="stable"))
+    with mi355cd.CollisionDetector(verts, vidx) as cd:
+        cd.self_collide(cap=1 << 20); assert cd.debug_get(mi355cd.CD_DBG_GET_SORT_FORM) == 0
+        cd.update_vertices(out)
+        got, n, rc, (keys, perm) = query(cd, True)
+        assert cd.debug_get(mi355cd.CD_DBG_GET_SORT_FORM) == 1
+    assert rc == wrc and n == wn and len(got) == len(want) and all(np.array_equal(g, w) for g, w in zip(got, want))
+    assert np.array_equal(keys, wkeys) and np.array_equal(perm, wperm)
+
+
 def test_half_key_sort_equals_full_sort_and_falls_back():
     """CD_OPT_SORT_FULL: the default hybrid (2 global passes on the top 16 key bits + in-LDS sort of run-aligned
     windows + stable fix-up of equal-high-half runs), the half-key form (4 global passes + fix-up) and all 8 passes
