@@ -39,7 +39,7 @@ __global__ __launch_bounds__(CCD_THREADS) void k_between_mbits(const LeafTri *__
         const LeafTri lt = leaf[j];
         const Box b = swept_box(CcdMeshSrc{x0, x1, lt.v0, lt.v1, lt.v2, 0u, 0u, 0u}, 0);
         const double m = fmax2(fmax2(dabs(b.x1), dabs(b.x2)), fmax2(fmax2(dabs(b.y1), dabs(b.y2)), fmax2(dabs(b.z1), dabs(b.z2))));
-        mbits = __float_as_uint(__double2float_ru(m));
+        mbits = __float_as_uint(__double2float_ru(m)) & 0x7fffffffu;         // (as k_ccd_refit: a leaf of -0.0 coordinates has m = -0.0)
     }
     for (int o = 32; o; o >>= 1) { const uint32_t v = __shfl_xor(mbits, o); mbits = v > mbits ? v : mbits; }   // (non-negative floats: bits order as values)
     if ((threadIdx.x & 63) == 0 && mbits) atomicMax(&st->m_bits, mbits);

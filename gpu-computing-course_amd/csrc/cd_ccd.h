@@ -169,7 +169,7 @@ __global__ __launch_bounds__(CCD_THREADS) void k_ccd_refit(const LeafTri *__rest
         float lo[3] = {__double2float_rd(b.x1), __double2float_rd(b.y1), __double2float_rd(b.z1)};
         float hi[3] = {__double2float_ru(b.x2), __double2float_ru(b.y2), __double2float_ru(b.z2)};
         double m = fmax2(fmax2(dabs(b.x1), dabs(b.x2)), fmax2(fmax2(dabs(b.y1), dabs(b.y2)), fmax2(dabs(b.z1), dabs(b.z2))));
-        mbits = __float_as_uint(__double2float_ru(m));
+        mbits = __float_as_uint(__double2float_ru(m)) & 0x7fffffffu;         // (dabs(-0.0) is -0.0: without its sign bit, which would win the unsigned max below)
         int32_t u = up[j];
         for (int steps = 0; u >= 0 && ((uint32_t)u >> 1) < (uint32_t)(n - 1) && steps < n; ++steps) {
             const uint32_t s = (uint32_t)u >> 1;

@@ -14,7 +14,9 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <atomic>
+#include <cfloat>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -180,6 +182,10 @@ struct cd_ctx {
     double *d_bw_x1a = nullptr; double *d_bw_x1b = nullptr; uint64_t bw_x1b_cap = 0;
     NodeRec32 *d_bw_recs = nullptr; int32_t *d_bw_up = nullptr; uint32_t *d_bw_arrive = nullptr; uint64_t bw_rec_cap = 0;
     int device = 0;                         // the HIP device ordinal current at cd_create (the between queries need both contexts on one device)
+    // what cd_debug_swept reports of the last CCD pass (host words only: nothing is enqueued for them)
+    struct SweptSeen { bool ran = false; uint32_t n = 0, m_bits = 0; double dist = 0.0; };
+    SweptSeen cc_seen;                      // cd_find_ccd / cd_self_ccd: the swept tree in d_cc_recs / d_cc_up
+    SweptSeen bw_seen;                      // cd_find_ccd_between with this context as a: b's swept tree in d_bw_recs / d_bw_up
 };
 
 namespace {
@@ -1601,6 +1607,32 @@ int cd_debug_records(cd_ctx *c, void *recs, void *qboxes, int32_t *root)
     return CD_OK;
 }
 
+/* Debug only: the swept tree of the last CCD pass (cd_ccd.h) as its descent read it.  between = 0: this context's own (cd_find_ccd / cd_self_ccd);
+ * 1: the other mesh's, as this context holds it for cd_find_ccd_between.  Records, up[] and M are copies; the pad is recomputed here
+ * (the descent keeps it in registers).  Nothing is launched. */
+int cd_debug_swept(cd_ctx *c, int between, void *recs, int32_t *up, uint32_t *m_bits, float *pad, uint32_t *n_leaves)
+{
+    if (!c || (between != 0 && between != 1)) return CD_ERR_ARG;
+    const cd_ctx::SweptSeen &seen = between ? c->bw_seen : c->cc_seen;
+    if (!seen.ran) return CD_ERR_ORDER;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const size_t n = seen.n;
+    if (n >= 2) {                                                            // (one leaf: no records, no links)
+        if (recs) HIPCHK(hipMemcpy(recs, between ? c->d_bw_recs : c->d_cc_recs, sizeof(NodeRec32) * n, hipMemcpyDeviceToHost));
+        if (up) HIPCHK(hipMemcpy(up, between ? c->d_bw_up : c->d_cc_up, sizeof(int32_t) * (2 * n - 1), hipMemcpyDeviceToHost));
+    }
+    if (m_bits) *m_bits = seen.m_bits;
+    if (pad) {                                                               // ccd_pad's host twin: the same FP64 sum, rounded up to fp32
+        float m; std::memcpy(&m, &seen.m_bits, sizeof m);
+        const double v = 2.0 * seen.dist + 2.0 * seen.dist * PROX_SLACK + (double)m * PROX_SLACK;
+        float f = INFINITY;
+        if (v <= (double)FLT_MAX) { f = (float)v; if ((double)f < v) f = std::nextafterf(f, INFINITY); }
+        *pad = f;
+    }
+    if (n_leaves) *n_leaves = seen.n;
+    return CD_OK;
+}
+
 // morton3D / expand64Bits themselves, on caller-supplied inputs; no context (one-shot device buffers on the null stream)
 static int morton_batch(const void *in, size_t in_bytes, uint64_t n, const double frame[FRAME_WORDS], uint64_t *out)
 {
@@ -2046,6 +2078,7 @@ static int ccd_finish(cd_ctx *c, double dist, uint32_t *pairs, double *toi, doub
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     if (rc) return rc;
+    c->cc_seen = {true, c->nt, c->h_cc_state->m_bits, dist};
     return ccd_results(c, pairs, toi, dists, cap_pairs, n_pairs, info);
 }
 static int ccd_args(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, uint64_t cap_pairs)
@@ -2248,6 +2281,7 @@ int cd_find_ccd_between(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const d
     if (verts_end_a) { HIPCHK(hipMemcpyAsync(a->d_bw_x1a, verts_end_a, sizeof(double) * 3 * (size_t)a->nv, hipMemcpyHostToDevice, a->stream)); ax1 = a->d_bw_x1a; }
     if (verts_end_b) { HIPCHK(hipMemcpyAsync(a->d_bw_x1b, verts_end_b, sizeof(double) * 3 * (size_t)b->nv, hipMemcpyHostToDevice, a->stream)); bx1 = a->d_bw_x1b; }
     if ((rc = bw_pass(a, b, BW_CCD, dist, cap_pairs, ax1, bx1))) return rc;
+    a->bw_seen = {true, b->nt, a->h_bw_state->m_bits, dist};
     if (info) {
         const CcdState *h = a->h_bw_state;
         uint64_t cand = 0;

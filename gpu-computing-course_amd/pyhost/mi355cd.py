@@ -67,7 +67,7 @@ EXPORTS = [
     "cd_load_obj", "cd_free_obj", "cd_create", "cd_destroy", "cd_update_vertices", "cd_set_morton_frame", "cd_get_morton_frame", "cd_set_morton_frame_layout", "cd_morton_sort",
     "cd_build_hierarchy", "cd_refit_boxes", "cd_check_internal", "cd_check_leaves",
     "cd_check_triangle_idx", "cd_find_collisions", "cd_build_tree", "cd_self_collide", "cd_sorted_pairs", "cd_collision_triangles", "cd_brute_force",
-    "cd_test_pairs", "cd_export_keys", "cd_export_tree", "cd_get_stats", "cd_debug_counters", "cd_debug_records", "cd_num_triangles",
+    "cd_test_pairs", "cd_export_keys", "cd_export_tree", "cd_get_stats", "cd_debug_counters", "cd_debug_records", "cd_debug_swept", "cd_num_triangles",
     "cd_set_option", "cd_set_vertex_id_base", "cd_root_box", "cd_pack_queries", "cd_find_collisions_queries", "cd_version",
     "cd_debug_option", "cd_debug_hint", "cd_debug_hint_set", "cd_morton3d_points", "cd_morton3d_points_layout", "cd_expand64_values", "cd_box_pairs", "cd_tri_contact_points", "cd_alloc_host_pairs", "cd_free_host_pairs",
     "cd_multi_unique_id", "cd_multi_create", "cd_multi_create_from_comm", "cd_multi_destroy", "cd_multi_set_flags", "cd_multi_step",
@@ -124,6 +124,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_get_stats.argtypes = [vp, C.POINTER(CdStats)]
     lib.cd_debug_counters.argtypes = [vp, vp]
     lib.cd_debug_records.argtypes = [vp, vp, vp, vp]
+    lib.cd_debug_swept.argtypes = [vp, C.c_int, vp, vp, u32p, C.POINTER(C.c_float), u32p]
     lib.cd_debug_hint.argtypes = [vp, vp, vp, vp]
     lib.cd_debug_hint_set.argtypes = [vp, vp]
     lib.cd_num_triangles.argtypes = [vp, u32p]
@@ -477,6 +478,25 @@ class CollisionDetector:
         root = C.c_int32(0)
         self._chk("cd_debug_records", self.lib.cd_debug_records(self._ctx, recs.ctypes.data, qb.ctypes.data, C.byref(root)))
         return recs[:n], recs[n:], qb, int(root.value)
+
+    def debug_swept(self, other=None):
+        """(right halves u32[n, 8], left halves u32[n, 8], up i32[2n - 1], m_bits, pad as an fp32 scalar) of the swept tree the last CCD
+        pass left: this context's own (find_ccd / self_ccd), or with `other` the one this context holds of `other` after
+        find_ccd_between(other).  n = 1: no records, the arrays come back empty."""
+        which = 0 if other is None else 1
+        m, pad, got = C.c_uint32(0), C.c_float(0.0), C.c_uint32(0)
+        self._chk("cd_debug_swept", self.lib.cd_debug_swept(self._ctx, which, None, None, None, None, C.byref(got)))   # the size first
+        n = got.value
+        if n != (self.nt if other is None else other.nt):
+            raise ValueError(f"the swept tree there has {n} leaves: not this mesh's")
+        if n < 2:                                                              # no records: only M and the pad are there
+            self._chk("cd_debug_swept", self.lib.cd_debug_swept(self._ctx, which, None, None, C.byref(m), C.byref(pad), None))
+            none = np.zeros((0, 8), dtype=np.uint32)
+            return none, none, np.zeros(0, dtype=np.int32), int(m.value), np.float32(pad.value)
+        recs = np.zeros((2 * n, 8), dtype=np.uint32)
+        up = np.zeros(2 * n - 1, dtype=np.int32)
+        self._chk("cd_debug_swept", self.lib.cd_debug_swept(self._ctx, which, recs.ctypes.data, up.ctypes.data, C.byref(m), C.byref(pad), None))
+        return recs[:n], recs[n:], up, int(m.value), np.float32(pad.value)
 
     # ---- cross-rank pass
     def set_vertex_id_base(self, base: int):

@@ -290,6 +290,14 @@ int cd_debug_hint_set(cd_ctx *ctx, const uint32_t *order);
  * of right halves {lo[3], hi[3], link, last | flags}, then n x 32 bytes of left halves {lo[3], hi[3], link, first}, both
  * indexed by split), qboxes: n x 32 bytes {lo[3], hi[3], flags, 0}, root: the root record's split.  Either may be NULL. */
 int cd_debug_records(cd_ctx *ctx, void *recs, void *qboxes, int32_t *root);
+/* Diagnostics: the swept tree of the last continuous collision pass as its descent read it.  between = 0: this context's own, left by
+ * cd_find_ccd / cd_self_ccd; between = 1: the other mesh's, as this context (a) holds it after cd_find_ccd_between (n = b's triangles).
+ * recs: n x 64 bytes in the layout of cd_debug_records (box floats: the swept boxes, true bounds; links and range words: the static
+ * records'), up: 2n - 1 words, up[j] for leaf j and up[n + s] for the node named by split s = (parent split << 1) | side, -1 for the
+ * root; both are left untouched when n = 1 (no records).  m_bits: the fp32 bits of M the descent made its pad from, n_leaves: n.
+ * pad: NOT device data -- the descent computes its pad in registers; this is the host twin of that computation (the same FP64 sum
+ * of dist and M, rounded up to fp32).  Any may be NULL.  CD_ERR_ORDER before the first such pass.  Nothing is launched. */
+int cd_debug_swept(cd_ctx *ctx, int between, void *recs, int32_t *up, uint32_t *m_bits, float *pad, uint32_t *n_leaves);
 int cd_num_triangles(cd_ctx *ctx, uint32_t *nt);
 
 /* ---- multi-GPU cross-rank pass (new work defined by the north star; no reference call site) ----

@@ -74,6 +74,8 @@ def test_argument_errors_do_not_need_a_device():
     assert lib.cd_tri_contact_points(None, 4, None) == mi355cd.CD_ERR_ARG
     assert lib.cd_debug_option(None, 0, 0, None) == mi355cd.CD_ERR_ARG
     assert lib.cd_multi_step(None, None, 0, None, None) == mi355cd.CD_ERR_ARG
+    assert lib.cd_debug_swept(None, 0, None, None, None, None, None) == mi355cd.CD_ERR_ARG
+    assert lib.cd_debug_swept(None, 1, None, None, None, None, None) == mi355cd.CD_ERR_ARG
     rl = mi355rt.load_library()
     rctx = C.c_void_p()
     assert rl.rt_create(C.byref(rctx), None, 0, 0) == mi355rt.RT_ERR_ARG
