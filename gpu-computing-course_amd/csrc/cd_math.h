@@ -268,6 +268,50 @@ __device__ __forceinline__ d3 load_vertex(const double *__restrict__ verts, uint
     return d3{p[0], p[1], p[2]};
 }
 
+// ---------------------------------------------------------------- ray against triangle (not reference behaviour)
+// The ray o + t d, t in [0, tmax] (d not normalised: t is in units of d; 0 <= tmax <= +inf), against the triangle (p0, p1, p2), in
+// FP64 with this operation order, IEEE divide, no contraction.  No face culling; det == 0 (a parallel ray, a degenerate triangle)
+// is a miss; every comparison is written so that a NaN fails it, so any NaN on the way is a miss.
+//   e1 = p1 - p0, e2 = p2 - p0, pv = d x e2, det = e1 . pv, inv = 1 / det, tv = o - p0, qv = tv x e1,
+//   u = (tv . pv) inv in [0, 1];  v = (d . qv) inv >= 0, u + v <= 1;  t = (e2 . qv) inv in [0, tmax];
+//   gate: P_a = o_a + t d_a within [lo_a - G, hi_a + G] on every axis, lo / hi the triangle's box (box_set) and
+//         G = 2^-30 max(|o_x|, |o_y|, |o_z|, the triangle's largest |coordinate|).
+// The gate is to this predicate what the strict box overlap is to tri_distance: on a sliver the computed (t, u, v) can be rounding
+// noise that passes the range checks at a point nowhere near the triangle; a hit the gate lets through has its computed point
+// within G of the triangle's box, which is what lets the walk's box filter only filter (cd_rays.h).
+// side = 1 when det > 0: the ray meets the face whose vertices run counter-clockwise as seen from the ray's origin.
+// Band: scaling o, d and the triangle by 2^k scales nothing in (t, u, v) (t is scale-free when o and d scale together) while no
+// nonzero intermediate -- products of up to three coordinate differences, so magnitudes around m^3 -- leaves the normal FP64 range:
+// for inputs whose largest |coordinate| m is of order 1 .. 16 with features down to about 2^-20 m, |k| <= 300 (m within about
+// 2^-300 .. 2^300; tests/test_ray_ref.py, tests/test_rays_gpu.py).  Outside it the result follows this arithmetic, overflow included.
+constexpr double RAY_GATE = 1.0 / 1073741824.0;        // 2^-30
+struct RayHit { bool hit; double t, u, v; uint32_t side; };
+__device__ __forceinline__ RayHit ray_tri(const d3 o, const d3 d, const double tmax, const d3 p0, const d3 p1, const d3 p2)
+{
+    RayHit r{false, 0.0, 0.0, 0.0, 0u};
+    const d3 e1 = sub(p1, p0), e2 = sub(p2, p0);
+    const d3 pv = cross(d, e2);
+    const double det = dot(e1, pv);
+    if (!(det > 0.0 || det < 0.0)) return r;
+    const double inv = 1.0 / det;
+    const d3 tv = sub(o, p0);
+    const double u = dot(tv, pv) * inv;
+    if (!(u >= 0.0 && u <= 1.0)) return r;
+    const d3 qv = cross(tv, e1);
+    const double v = dot(d, qv) * inv;
+    if (!(v >= 0.0 && u + v <= 1.0)) return r;
+    const double t = dot(e2, qv) * inv;
+    if (!(t >= 0.0 && t <= tmax)) return r;
+    double m = 0.0;
+    m = dmax_abs3(m, o); m = dmax_abs3(m, p0); m = dmax_abs3(m, p1); m = dmax_abs3(m, p2);
+    const double G = RAY_GATE * m;
+    const Box b = box_set(p0, p1, p2);
+    const double Px = o.x + t * d.x, Py = o.y + t * d.y, Pz = o.z + t * d.z;
+    if (!(b.x1 - G <= Px && Px <= b.x2 + G && b.y1 - G <= Py && Py <= b.y2 + G && b.z1 - G <= Pz && Pz <= b.z2 + G)) return r;
+    r.hit = true; r.t = t; r.u = u; r.v = v; r.side = det > 0.0 ? 1u : 0u;
+    return r;
+}
+
 // morton.h:7-29
 __device__ __forceinline__ uint64_t expand64(uint64_t v)
 {

@@ -10,6 +10,7 @@
 #include "cd_proximity.h"
 #include "cd_ccd.h"
 #include "cd_between.h"
+#include "cd_rays.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -186,6 +187,10 @@ struct cd_ctx {
     struct SweptSeen { bool ran = false; uint32_t n = 0, m_bits = 0; double dist = 0.0; };
     SweptSeen cc_seen;                      // cd_find_ccd / cd_self_ccd: the swept tree in d_cc_recs / d_cc_up
     SweptSeen bw_seen;                      // cd_find_ccd_between with this context as a: b's swept tree in d_bw_recs / d_bw_up
+    // ray queries (cd_cast_rays, cd_rays.h): buffers of their own, allocated on first use and grown to the largest ray count seen.
+    // d_ry_block: rays [7 n] | t [n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | side [n] (u8)
+    RayState *d_ry_state = nullptr; RayState *h_ry_state = nullptr;
+    char *d_ry_block = nullptr; uint64_t ry_cap = 0;
 };
 
 namespace {
@@ -220,6 +225,8 @@ void free_all(cd_ctx *c)
     hipFree(c->d_bw_state); hipFree(c->d_bw_cand); hipFree(c->d_bw_pairs); hipFree(c->d_bw_toi); hipFree(c->d_bw_dists);
     hipFree(c->d_bw_x1a); hipFree(c->d_bw_x1b); hipFree(c->d_bw_recs); hipFree(c->d_bw_up); hipFree(c->d_bw_arrive);
     if (c->h_bw_state) hipHostFree(c->h_bw_state);
+    hipFree(c->d_ry_state); hipFree(c->d_ry_block);
+    if (c->h_ry_state) hipHostFree(c->h_ry_state);
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -2289,6 +2296,86 @@ int cd_find_ccd_between(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const d
         info->n_candidates = cand; info->n_tested = h->n_tested; info->n_evals = h->n_evals; info->n_unresolved = h->n_unresolved;
     }
     return bw_results(a, pairs, toi, dists, cap_pairs, n_pairs);
+}
+// ---- ray queries (cd_rays.h) ------------------------------------------------------------------------------------------------------
+// Own buffers (rays, results, counters): nothing any other call keeps is touched.
+constexpr uint64_t RAY_BYTES = 7 * 8 + 8 + 16 + 4 + 4 + 1;                  // device bytes a ray: the ray, t, uv, face, ID, side
+static int ray_buffers(cd_ctx *c, uint64_t n)
+{
+    if (!c->d_ry_state) {
+        HIPCHK(hipMalloc(&c->d_ry_state, sizeof(RayState)));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_ry_state), sizeof(RayState), hipHostMallocDefault));
+    }
+    if (n > c->ry_cap) {
+        hipFree(c->d_ry_block); c->d_ry_block = nullptr; c->ry_cap = 0;
+        HIPCHK(hipMalloc(&c->d_ry_block, RAY_BYTES * n));
+        c->ry_cap = n;
+    }
+    return CD_OK;
+}
+int cd_cast_rays(cd_ctx *c, const double *rays, uint64_t n, int flags, uint32_t *face, uint32_t *ids, double *t, double *uv, uint8_t *side, cd_ray_info *info)
+{
+    const bool any = flags == CD_RAY_ANY;
+    if (!c || (flags != 0 && !any) || (n && (!rays || !face)) || (any && (ids || t || uv || side)) || n > (1ull << 37)) return CD_ERR_ARG;
+    for (uint64_t i = 0; i < n; ++i) {                                      // before anything is launched: nothing is written for a bad ray
+        const double *r = rays + 7 * i;
+        bool finite = true, zero = true;
+        for (int k = 0; k < 6; ++k) finite = finite && std::isfinite(r[k]);
+        for (int k = 3; k < 6; ++k) zero = zero && r[k] == 0.0;
+        if (!finite || zero || !(r[6] >= 0.0)) return CD_ERR_ARG;          // (a NaN tmax fails the comparison)
+    }
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { if (info) *info = cd_ray_info{0, 0, 0}; return CD_OK; }
+    int rc = ray_buffers(c, n);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const uint64_t cap = c->ry_cap;
+    double *d_rays = reinterpret_cast<double *>(c->d_ry_block), *d_t = d_rays + 7 * cap, *d_uv = d_t + cap;
+    uint32_t *d_face = reinterpret_cast<uint32_t *>(d_uv + 2 * cap), *d_ids = d_face + cap;
+    uint8_t *d_side = reinterpret_cast<uint8_t *>(d_ids + cap);
+    HIPCHK(hipMemcpyAsync(d_rays, rays, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(c->d_ry_state, 0, sizeof(RayState), s));
+    const uint32_t grid = cdiv(n, RAY_THREADS);
+    if (any) k_cast_rays<true><<<grid, RAY_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_rays, n, c->d_ry_state,
+                                                            d_face, nullptr, nullptr, nullptr, nullptr);
+    else k_cast_rays<false><<<grid, RAY_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_rays, n, c->d_ry_state,
+                                                         d_face, ids ? d_ids : nullptr, t ? d_t : nullptr, uv ? d_uv : nullptr, side ? d_side : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_ry_state, c->d_ry_state, sizeof(RayState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(face, d_face, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    if (t) HIPCHK(hipMemcpyAsync(t, d_t, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    if (uv) HIPCHK(hipMemcpyAsync(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, s));
+    if (side) HIPCHK(hipMemcpyAsync(side, d_side, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (info) { info->n_hits = c->h_ry_state->n_hits; info->node_visits = c->h_ry_state->node_visits; info->tri_tests = c->h_ry_state->tri_tests; }
+    return CD_OK;
+}
+int cd_ray_tri_points(const double *ray, const double *tri, uint64_t n, uint8_t *hit, double *t, double *uv, uint8_t *side)
+{
+    if (!ray || !tri || !hit) return CD_ERR_ARG;
+    if (n == 0) return CD_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
+    double *d_r = nullptr, *d_p = nullptr, *d_t = nullptr, *d_uv = nullptr; uint8_t *d_h = nullptr, *d_s = nullptr;
+    hipError_t e = hipMalloc(&d_r, sizeof(double) * 7 * n);
+    if (e == hipSuccess) e = hipMalloc(&d_p, sizeof(double) * 9 * n);
+    if (e == hipSuccess) e = hipMalloc(&d_t, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMalloc(&d_uv, sizeof(double) * 2 * n);
+    if (e == hipSuccess) e = hipMalloc(&d_h, n);
+    if (e == hipSuccess) e = hipMalloc(&d_s, n);
+    if (e == hipSuccess) e = hipMemcpy(d_r, ray, sizeof(double) * 7 * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_p, tri, sizeof(double) * 9 * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        k_ray_tri_points<<<cdiv(n, 256) < 4096u ? cdiv(n, 256) : 4096u, 256>>>(d_r, d_p, n, d_h, d_t, d_uv, d_s);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(hit, d_h, n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && t) e = hipMemcpy(t, d_t, sizeof(double) * n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && uv) e = hipMemcpy(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && side) e = hipMemcpy(side, d_s, n, hipMemcpyDeviceToHost);
+    }
+    hipFree(d_r); hipFree(d_p); hipFree(d_t); hipFree(d_uv); hipFree(d_h); hipFree(d_s);
+    return e == hipSuccess ? CD_OK : -(int)e;
 }
 }  // extern "C"
 

@@ -55,6 +55,14 @@ class CdCcdInfo(C.Structure):
     _fields_ = [("n_candidates", C.c_uint64), ("n_tested", C.c_uint64), ("n_evals", C.c_uint64), ("n_unresolved", C.c_uint64)]
 
 
+class CdRayInfo(C.Structure):
+    _fields_ = [("n_hits", C.c_uint64), ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64)]
+
+
+CD_RAY_ANY = 1
+RAY_MISS = 0xFFFFFFFF
+
+
 class CdMultiInfo(C.Structure):
     _fields_ = [("world", C.c_uint32), ("rank", C.c_uint32), ("n_peers", C.c_uint32), ("host_syncs", C.c_uint32), ("attempts", C.c_uint32),
                 ("failed_rank_plus1", C.c_uint32), ("sent_queries", C.c_uint64), ("recv_queries", C.c_uint64), ("local_pairs", C.c_uint64),
@@ -74,6 +82,7 @@ EXPORTS = [
     "cd_find_proximity", "cd_self_proximity", "cd_tri_distance_points",
     "cd_find_ccd", "cd_self_ccd", "cd_ccd_points",
     "cd_find_collisions_between", "cd_find_proximity_between", "cd_find_ccd_between",
+    "cd_cast_rays", "cd_ray_tri_points",
 ]
 
 _lib = None
@@ -152,6 +161,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_find_collisions_between.argtypes = [vp, vp, vp, C.c_uint64, u64p, u64p]
     lib.cd_find_proximity_between.argtypes = [vp, vp, C.c_double, vp, vp, C.c_uint64, u64p, u64p]
     lib.cd_find_ccd_between.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp, C.c_uint64, u64p, vp]
+    lib.cd_cast_rays.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.cd_ray_tri_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -390,6 +401,29 @@ class CollisionDetector:
         got = min(n.value, cap)
         return pairs[:got].copy(), toi[:got].copy(), dists[:got].copy(), n.value, rc
 
+    # ---- ray queries against this mesh (cd_cast_rays)
+    def cast_rays(self, origins, dirs, tmax=np.inf, any_hit: bool = False):
+        """cd_cast_rays on the tree that is there.  origins, dirs: [n, 3]; tmax: a scalar or [n] (t is in units of dirs, which are not
+        normalised; the range is [0, tmax]).  Closest hit: (face[n] (index into the face list, RAY_MISS = 0xFFFFFFFF for a miss),
+        ids[n], t[n] (+inf for a miss), uv[n, 2], side[n], info) -- of the triangles ray_tri hits, the smallest (t, ID, face index).
+        any_hit: (face[n], info); face is RAY_MISS or SOME hit triangle -- which one is not defined, whether there is one is.
+        Rays are walked in the order given: keep coherent rays next to each other."""
+        rays = pack_rays(origins, dirs, tmax)
+        n = rays.shape[0]
+        face = np.empty(n, dtype=np.uint32)
+        info = CdRayInfo()
+        if any_hit:
+            rc = self.lib.cd_cast_rays(self._ctx, _ptr(rays), n, CD_RAY_ANY, _ptr(face), None, None, None, None, C.byref(info))
+            self._chk("cd_cast_rays", rc)
+            return face, info
+        ids = np.empty(n, dtype=np.uint32)
+        t = np.empty(n, dtype=np.float64)
+        uv = np.empty((n, 2), dtype=np.float64)
+        side = np.empty(n, dtype=np.uint8)
+        rc = self.lib.cd_cast_rays(self._ctx, _ptr(rays), n, 0, _ptr(face), _ptr(ids), _ptr(t), _ptr(uv), _ptr(side), C.byref(info))
+        self._chk("cd_cast_rays", rc)
+        return face, ids, t, uv, side, info
+
     def find_collisions(self, cap: int = 1 << 20):
         return self._pairs_call(self.lib.cd_find_collisions, "cd_find_collisions", cap)
 
@@ -624,6 +658,37 @@ def tri_distance_points(tri) -> np.ndarray:
     if rc != CD_OK:
         raise CdError("cd_tri_distance_points", rc)
     return out
+
+
+def pack_rays(origins, dirs, tmax=np.inf) -> np.ndarray:
+    """[n, 7] doubles (o, d, tmax), the layout cd_cast_rays and cd_ray_tri_points take."""
+    o = np.asarray(origins, dtype=np.float64).reshape(-1, 3)
+    d = np.asarray(dirs, dtype=np.float64).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError(f"origins {o.shape} and dirs {d.shape} differ")
+    rays = np.empty((o.shape[0], 7), dtype=np.float64)
+    rays[:, 0:3] = o
+    rays[:, 3:6] = d
+    rays[:, 6] = tmax
+    return rays
+
+
+def ray_tri_points(rays, tris):
+    """ray_tri (the per-pair predicate of cd_cast_rays) on explicit operands, on the device (cd_ray_tri_points): rays [n, 7]
+    (o, d, tmax), tris [n, 3, 3] -> (hit[n] bool, t[n], uv[n, 2], side[n]); t, uv, side are 0 on a miss."""
+    r = np.ascontiguousarray(np.asarray(rays, dtype=np.float64).reshape(-1, 7))
+    p = np.ascontiguousarray(np.asarray(tris, dtype=np.float64).reshape(-1, 9))
+    if r.shape[0] != p.shape[0]:
+        raise ValueError(f"{r.shape[0]} rays against {p.shape[0]} triangles")
+    n = r.shape[0]
+    hit = np.zeros(n, dtype=np.uint8)
+    t = np.zeros(n, dtype=np.float64)
+    uv = np.zeros((n, 2), dtype=np.float64)
+    side = np.zeros(n, dtype=np.uint8)
+    rc = load_library().cd_ray_tri_points(_ptr(r), _ptr(p), n, _ptr(hit), _ptr(t), _ptr(uv), _ptr(side))
+    if rc != CD_OK:
+        raise CdError("cd_ray_tri_points", rc)
+    return hit.astype(bool), t, uv, side
 
 
 def ccd_points(tri, dist: float):

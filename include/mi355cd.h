@@ -483,6 +483,50 @@ int cd_find_ccd_between(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const d
                         uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
                         cd_ccd_info *info);
 
+/* ---- ray queries: closest hit and occlusion (not reference behaviour) ----
+ * A ray is seven doubles: an origin o, a direction d and an upper end tmax.  o and d are finite and d is not all zero; d is NOT
+ * normalised, so t is in units of d; 0 <= tmax <= +inf and the ray's parameter range is [0, tmax] (a segment from a to b: o = a,
+ * d = b - a, tmax = 1).  ray_tri(ray, triangle p0 p1 p2), FP64 with a fixed operation order, IEEE divide and no contraction
+ * (csrc/cd_math.h):
+ *   e1 = p1 - p0, e2 = p2 - p0, pv = d x e2, det = e1 . pv;  det == 0 -> miss (a parallel ray, or a degenerate triangle: segments
+ *   and points are never hit);  inv = 1 / det, tv = o - p0;  u = (tv . pv) inv, u < 0 or u > 1 -> miss;  qv = tv x e1;
+ *   v = (d . qv) inv, v < 0 or u + v > 1 -> miss;  t = (e2 . qv) inv, t < 0 or t > tmax -> miss;
+ *   gate: P_a = o_a + t d_a per axis; G = 2^-30 max(|o_x|, |o_y|, |o_z|, the largest |coordinate| of p0, p1, p2); on every axis
+ *   lo_a - G <= P_a <= hi_a + G with lo / hi the triangle's FP64 box (box.cuh:13-22), else miss;
+ *   hit: (t, u, v, side), the hit point being (1 - u - v) p0 + u p1 + v p2; side = 1 when det > 0 (the ray meets the face whose
+ *   vertices run counter-clockwise as seen from its origin), else 0.
+ * There is no face culling, and any NaN produced on the way is a miss.  The gate rejects the hits that are rounding noise: on a sliver
+ * the computed (t, u, v) can pass the range checks at a point nowhere near the triangle.  Scaling the ray and the triangle by 2^k
+ * changes nothing in (t, u, v, side) while the largest |coordinate| stays within about 2^-300 .. 2^300 (products of three coordinate
+ * differences must stay normal numbers; fp32 overflow and subnormals lie well inside that band); outside it the result follows the
+ * arithmetic above, overflow included.
+ *
+ * cd_cast_rays, flags = 0 (closest hit): for ray k, of the triangles of this context that ray_tri hits, the one with the smallest
+ * (t, triangle ID, face index) in lexicographic order -- so a ray through a shared edge or vertex has one defined answer.
+ * face[k]: its index in cd_create's face list, 0xFFFFFFFF when nothing is hit; ids[k]: its ID; t[k], uv[2 k], uv[2 k + 1], side[k]:
+ * ray_tri's values for it.  On a miss t[k] = +inf and the other outputs are 0.  ids, t, uv, side may each be NULL.
+ * flags = CD_RAY_ANY (occlusion): face[k] = 0xFFFFFFFF for a miss and SOME triangle that ray_tri hits otherwise.  WHETHER there is one
+ * is defined (exactly where the closest-hit call hits); WHICH one is returned is not (it depends on the tree and may change from
+ * build to build).  ids, t, uv and side must be NULL.
+ * info (may be NULL): rays that hit, boxes tested, ray_tri evaluations -- numbers of this tree, not of the mesh.
+ * Guarantee: the closest-hit result depends on the mesh and the rays only -- not on the Morton frame, CD_OPT_TRAVERSAL,
+ * CD_OPT_CELL_TABLE, the build variant or the order of the rays.  Rays are walked in the order given, one lane each, neighbours in
+ * one wave: coherent rays (a camera's rows, a strand's segments) should be neighbours; the library does not sort them.
+ * Needs a tree built from the current vertices (CD_ERR_ORDER otherwise, including after cd_update_vertices without a rebuild).
+ * CD_ERR_ARG: a NULL context; NULL rays or face with n > 0; flags other than 0 / CD_RAY_ANY; with CD_RAY_ANY an output other than
+ * face; a non-finite origin or direction, an all-zero direction, a tmax that is NaN or negative -- checked on the host before
+ * anything is launched, and nothing is written then.  n = 0 returns CD_OK.  The call leaves cd_stats, the last pair list, the order
+ * hint, a captured CD_OPT_GRAPH step and the proximity, CCD and between-mesh buffers as they were; it keeps device buffers of its
+ * own (grown on demand; cd_destroy frees them) and runs on the context's stream with one host synchronisation. */
+typedef struct cd_ray_info { uint64_t n_hits, node_visits, tri_tests; } cd_ray_info;
+enum { CD_RAY_ANY = 1 };
+int cd_cast_rays(cd_ctx *ctx, const double *rays, uint64_t n, int flags, uint32_t *face, uint32_t *ids, double *t,
+                 double *uv, uint8_t *side, cd_ray_info *info);
+/* ray_tri on explicit operands (host pointers; no context): ray is n x 7 doubles (o, d, tmax), tri n x 9 (p0, p1, p2).  hit[k] = 1 / 0;
+ * t[k], uv[2 k], uv[2 k + 1], side[k] (each may be NULL): ray_tri's values, 0 on a miss.  No argument is checked for finiteness: the
+ * arithmetic decides.  The pin of the device function. */
+int cd_ray_tri_points(const double *ray, const double *tri, uint64_t n, uint8_t *hit, double *t, double *uv, uint8_t *side);
+
 /* Library / build identification: "mi355cd <version> gfx950". */
 const char *cd_version(void);
 
