@@ -192,30 +192,35 @@ __device__ __forceinline__ bool tri_contact_fast(const d3 P1, const d3 P2, const
 // numpy restatement (tests/proximity_ref.py) reproduces it bit for bit.  Non-finite vertices: undefined.
 __device__ __forceinline__ double dmin2(double a, double b) { return b < a ? b : a; }
 __device__ __forceinline__ d3 dscale(const d3 a, double s) { return d3{a.x * s, a.y * s, a.z * s}; }
-// squared distance from p to the segment [a, b]
-__device__ __forceinline__ double pt_seg2(const d3 p, const d3 a, const d3 b)
+// squared distance from p to the segment [a, b]; t: the clamped parameter of the closest point a + t (b - a) (0 for a == b)
+__device__ __forceinline__ double pt_seg2_t(const d3 p, const d3 a, const d3 b, double &t)
 {
     const d3 ab = sub(b, a), ap = sub(p, a);
     const double den = dot(ab, ab);
-    double t = 0.0;
+    t = 0.0;
     if (den > 0.0) { t = dot(ap, ab) / den; t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t); }
     const d3 q = d3{a.x + t * ab.x, a.y + t * ab.y, a.z + t * ab.z};
     const d3 d = sub(p, q);
     return dot(d, d);
 }
-// squared distance from p to its projection onto the plane of (a, b, c) when that projection lies in the triangle, else +inf
-__device__ __forceinline__ double pt_face2(const d3 p, const d3 a, const d3 b, const d3 c)
+__device__ __forceinline__ double pt_seg2(const d3 p, const d3 a, const d3 b) { double t; return pt_seg2_t(p, a, b, t); }
+// squared distance from p to its projection a + v (b - a) + w (c - a) onto the plane of (a, b, c) when that projection lies in the
+// triangle, else +inf (and v = w = 0)
+__device__ __forceinline__ double pt_face2_vw(const d3 p, const d3 a, const d3 b, const d3 c, double &v, double &w)
 {
+    v = 0.0; w = 0.0;
     const d3 ab = sub(b, a), ac = sub(c, a), ap = sub(p, a);
     const double d00 = dot(ab, ab), d01 = dot(ab, ac), d11 = dot(ac, ac), d20 = dot(ap, ab), d21 = dot(ap, ac);
     const double den = d00 * d11 - d01 * d01;
     if (!(den > 0.0)) return __builtin_inf();
-    const double v = (d11 * d20 - d01 * d21) / den, w = (d00 * d21 - d01 * d20) / den;
-    if (!(v >= 0.0 && w >= 0.0 && v + w <= 1.0)) return __builtin_inf();
-    const d3 q = d3{(a.x + v * ab.x) + w * ac.x, (a.y + v * ab.y) + w * ac.y, (a.z + v * ab.z) + w * ac.z};
+    const double fv = (d11 * d20 - d01 * d21) / den, fw = (d00 * d21 - d01 * d20) / den;
+    if (!(fv >= 0.0 && fw >= 0.0 && fv + fw <= 1.0)) return __builtin_inf();
+    const d3 q = d3{(a.x + fv * ab.x) + fw * ac.x, (a.y + fv * ab.y) + fw * ac.y, (a.z + fv * ab.z) + fw * ac.z};
     const d3 d = sub(p, q);
+    v = fv; w = fw;
     return dot(d, d);
 }
+__device__ __forceinline__ double pt_face2(const d3 p, const d3 a, const d3 b, const d3 c) { double v, w; return pt_face2_vw(p, a, b, c, v, w); }
 // squared distance between the segments [p1, q1], [p2, q2] at their interior critical point when it lies on both, else +inf
 // (the endpoints' terms are pt_seg2's)
 __device__ __forceinline__ double seg_seg2(const d3 p1, const d3 q1, const d3 p2, const d3 q2)
@@ -309,6 +314,56 @@ __device__ __forceinline__ RayHit ray_tri(const d3 o, const d3 d, const double t
     const double Px = o.x + t * d.x, Py = o.y + t * d.y, Pz = o.z + t * d.z;
     if (!(b.x1 - G <= Px && Px <= b.x2 + G && b.y1 - G <= Py && Py <= b.y2 + G && b.z1 - G <= Pz && Pz <= b.z2 + G)) return r;
     r.hit = true; r.t = t; r.u = u; r.v = v; r.side = det > 0.0 ? 1u : 0u;
+    return r;
+}
+
+// ---------------------------------------------------------------- point against triangle (not reference behaviour)
+// pt_tri(p; p0, p1, p2): the distance from p to the triangle, the closest point q on it and where on the triangle q lies, in FP64 with
+// this operation order, IEEE divide and sqrt, no contraction; tri_distance's blocks and tri_distance's frame, so its band (above):
+//   a = p0 - p, b = p1 - p, c = p2 - p (the query point becomes the origin O);  m = the largest |component| of a, b, c;
+//   m == 0 (three coincident vertices at p): dist = 0, u = v = 0, feature = 4, side = 0, q = p0;
+//   else m = f 2^ex (f in [0.5, 1), |ex| clamped at 1000), a, b, c times 2^-ex (exact), and the minimum of four terms taken in this
+//   order, a later term replacing an earlier one only when it is strictly smaller (an earlier term keeps a tie):
+//     face     pt_face2_vw(O, a, b, c)         u = v_face, v = w_face                 feature 0
+//     edge 01  pt_seg2_t(O, a, b) -> t         u = t,      v = 0                      feature 1; t == 0: 4 (vertex 0); t == 1: 5 (vertex 1)
+//     edge 12  pt_seg2_t(O, b, c) -> t         u = 1 - t,  v = t                      feature 2; t == 0: 5;            t == 1: 6 (vertex 2)
+//     edge 20  pt_seg2_t(O, c, a) -> t         u = 0,      v = 1 - t                  feature 3; t == 0: 6;            t == 1: 4
+//   dist = sqrt(best) 2^ex;   side = (O - a) . ((b - a) x (c - a)) > 0, on the scaled operands;
+//   q_k = (w p0_k + u p1_k) + v p2_k with w = (1 - u) - v, on the ORIGINAL vertices, per coordinate k.
+// (u, v) are the barycentrics of q: q = (1 - u - v) p0 + u p1 + v p2; on an edge or a vertex they are the 0 / t / 1 - t the term implies
+// (a clamped t may be -0.0: it compares equal to 0).  feature 0 means the face term won: the projection onto the plane lies in the
+// CLOSED triangle, so a point whose projection falls exactly on an edge reports 0, not the edge.  A face whose barycentric denominator
+// is not > 0 contributes +inf, so a degenerate triangle has the distance of the segment or point it is, from its edges' terms.
+// side = 1: p lies on the side of the triangle's PLANE that sees the vertices counter-clockwise.  On an edge or vertex feature this is
+// NOT an inside / outside test of a closed surface (the neighbouring face may see p from its other side).
+// Finite input gives no NaN: every division has a denominator > 0 and the scaled operands lie in [-1, 1].  Non-finite vertices: undefined.
+struct PtTri { double dist, u, v; d3 q; uint32_t feature, side; };
+__device__ __forceinline__ PtTri pt_tri(const d3 p, const d3 p0, const d3 p1, const d3 p2)
+{
+    PtTri r{0.0, 0.0, 0.0, p0, 4u, 0u};
+    d3 a = sub(p0, p), b = sub(p1, p), c = sub(p2, p);
+    double m = 0.0;
+    m = dmax_abs3(m, a); m = dmax_abs3(m, b); m = dmax_abs3(m, c);
+    if (!(m > 0.0)) return r;
+    int ex = (int)((__double_as_longlong(m) >> 52) & 0x7ff) - 1022;     // m = f 2^ex, f in [0.5, 1) (as tri_distance)
+    ex = ex < -TRI_DIST_EXP_MAX ? -TRI_DIST_EXP_MAX : (ex > TRI_DIST_EXP_MAX ? TRI_DIST_EXP_MAX : ex);
+    const double sc = pow2(-ex);
+    a = dscale(a, sc); b = dscale(b, sc); c = dscale(c, sc);
+    const d3 o = d3{0.0, 0.0, 0.0};
+    double u, v, t;
+    double best = pt_face2_vw(o, a, b, c, u, v);
+    uint32_t f = 0u;
+    double d = pt_seg2_t(o, a, b, t);
+    if (d < best) { best = d; u = t; v = 0.0; f = t > 0.0 ? (t < 1.0 ? 1u : 5u) : 4u; }
+    d = pt_seg2_t(o, b, c, t);
+    if (d < best) { best = d; u = 1.0 - t; v = t; f = t > 0.0 ? (t < 1.0 ? 2u : 6u) : 5u; }
+    d = pt_seg2_t(o, c, a, t);
+    if (d < best) { best = d; u = 0.0; v = 1.0 - t; f = t > 0.0 ? (t < 1.0 ? 3u : 4u) : 6u; }
+    r.side = dot(sub(o, a), cross(sub(b, a), sub(c, a))) > 0.0 ? 1u : 0u;
+    r.dist = __builtin_sqrt(best) * pow2(ex);
+    r.u = u; r.v = v; r.feature = f;
+    const double w = (1.0 - u) - v;
+    r.q = d3{(w * p0.x + u * p1.x) + v * p2.x, (w * p0.y + u * p1.y) + v * p2.y, (w * p0.z + u * p1.z) + v * p2.z};
     return r;
 }
 

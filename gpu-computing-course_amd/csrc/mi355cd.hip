@@ -11,6 +11,7 @@
 #include "cd_ccd.h"
 #include "cd_between.h"
 #include "cd_rays.h"
+#include "cd_points.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -191,6 +192,10 @@ struct cd_ctx {
     // d_ry_block: rays [7 n] | t [n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | side [n] (u8)
     RayState *d_ry_state = nullptr; RayState *h_ry_state = nullptr;
     char *d_ry_block = nullptr; uint64_t ry_cap = 0;
+    // closest-point queries (cd_closest_points, cd_points.h): buffers of their own, as the rays'.
+    // d_pt_block: points [4 n] | dist [n] | closest [3 n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | feature [n] | side [n] (u8)
+    PointState *d_pt_state = nullptr; PointState *h_pt_state = nullptr;
+    char *d_pt_block = nullptr; uint64_t pt_cap = 0;
 };
 
 namespace {
@@ -227,6 +232,8 @@ void free_all(cd_ctx *c)
     if (c->h_bw_state) hipHostFree(c->h_bw_state);
     hipFree(c->d_ry_state); hipFree(c->d_ry_block);
     if (c->h_ry_state) hipHostFree(c->h_ry_state);
+    hipFree(c->d_pt_state); hipFree(c->d_pt_block);
+    if (c->h_pt_state) hipHostFree(c->h_pt_state);
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -2375,6 +2382,89 @@ int cd_ray_tri_points(const double *ray, const double *tri, uint64_t n, uint8_t 
         if (e == hipSuccess && side) e = hipMemcpy(side, d_s, n, hipMemcpyDeviceToHost);
     }
     hipFree(d_r); hipFree(d_p); hipFree(d_t); hipFree(d_uv); hipFree(d_h); hipFree(d_s);
+    return e == hipSuccess ? CD_OK : -(int)e;
+}
+// ---- closest-point queries (cd_points.h) ------------------------------------------------------------------------------------------
+// Own buffers (points, results, counters): nothing any other call keeps is touched.
+constexpr uint64_t POINT_BYTES = 4 * 8 + 8 + 24 + 16 + 4 + 4 + 1 + 1;       // device bytes a point: the point, dist, closest, uv, face, ID, feature, side
+static int point_buffers(cd_ctx *c, uint64_t n)
+{
+    if (!c->d_pt_state) {
+        HIPCHK(hipMalloc(&c->d_pt_state, sizeof(PointState)));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_pt_state), sizeof(PointState), hipHostMallocDefault));
+    }
+    if (n > c->pt_cap) {
+        hipFree(c->d_pt_block); c->d_pt_block = nullptr; c->pt_cap = 0;
+        HIPCHK(hipMalloc(&c->d_pt_block, POINT_BYTES * n));
+        c->pt_cap = n;
+    }
+    return CD_OK;
+}
+int cd_closest_points(cd_ctx *c, const double *points, uint64_t n, int flags, uint32_t *face, uint32_t *ids, double *dist, double *closest, double *uv,
+                      uint8_t *feature, uint8_t *side, cd_point_info *info)
+{
+    const bool any = flags == CD_POINT_ANY;
+    if (!c || (flags != 0 && !any) || (n && (!points || !face)) || (any && (ids || dist || closest || uv || feature || side)) || n > (1ull << 37)) return CD_ERR_ARG;
+    for (uint64_t i = 0; i < n; ++i) {                                      // before anything is launched: nothing is written for a bad point
+        const double *r = points + 4 * i;
+        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2]) || !(r[3] >= 0.0)) return CD_ERR_ARG;   // (a NaN rmax fails the comparison)
+    }
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { if (info) *info = cd_point_info{0, 0, 0}; return CD_OK; }
+    int rc = point_buffers(c, n);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const uint64_t cap = c->pt_cap;
+    double *d_pts = reinterpret_cast<double *>(c->d_pt_block), *d_dist = d_pts + 4 * cap, *d_q = d_dist + cap, *d_uv = d_q + 3 * cap;
+    uint32_t *d_face = reinterpret_cast<uint32_t *>(d_uv + 2 * cap), *d_ids = d_face + cap;
+    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + cap), *d_side = d_feat + cap;
+    HIPCHK(hipMemcpyAsync(d_pts, points, sizeof(double) * 4 * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(c->d_pt_state, 0, sizeof(PointState), s));
+    const uint32_t grid = cdiv(n, POINT_THREADS);
+    if (any) k_closest_points<true><<<grid, POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_pts, n, c->d_pt_state,
+                                                                  d_face, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    else k_closest_points<false><<<grid, POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_pts, n, c->d_pt_state,
+                                                               d_face, ids ? d_ids : nullptr, dist ? d_dist : nullptr, closest ? d_q : nullptr, uv ? d_uv : nullptr,
+                                                               feature ? d_feat : nullptr, side ? d_side : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_pt_state, c->d_pt_state, sizeof(PointState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(face, d_face, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    if (closest) HIPCHK(hipMemcpyAsync(closest, d_q, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+    if (uv) HIPCHK(hipMemcpyAsync(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, s));
+    if (feature) HIPCHK(hipMemcpyAsync(feature, d_feat, n, hipMemcpyDeviceToHost, s));
+    if (side) HIPCHK(hipMemcpyAsync(side, d_side, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (info) { info->n_found = c->h_pt_state->n_found; info->node_visits = c->h_pt_state->node_visits; info->tri_tests = c->h_pt_state->tri_tests; }
+    return CD_OK;
+}
+int cd_pt_tri_points(const double *points, const double *tri, uint64_t n, double *dist, double *closest, double *uv, uint8_t *feature, uint8_t *side)
+{
+    if (!points || !tri || !dist) return CD_ERR_ARG;
+    if (n == 0) return CD_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
+    double *d_p = nullptr, *d_t = nullptr, *d_d = nullptr, *d_q = nullptr, *d_uv = nullptr; uint8_t *d_f = nullptr, *d_s = nullptr;
+    hipError_t e = hipMalloc(&d_p, sizeof(double) * 3 * n);
+    if (e == hipSuccess) e = hipMalloc(&d_t, sizeof(double) * 9 * n);
+    if (e == hipSuccess) e = hipMalloc(&d_d, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMalloc(&d_q, sizeof(double) * 3 * n);
+    if (e == hipSuccess) e = hipMalloc(&d_uv, sizeof(double) * 2 * n);
+    if (e == hipSuccess) e = hipMalloc(&d_f, n);
+    if (e == hipSuccess) e = hipMalloc(&d_s, n);
+    if (e == hipSuccess) e = hipMemcpy(d_p, points, sizeof(double) * 3 * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_t, tri, sizeof(double) * 9 * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        k_pt_tri_points<<<cdiv(n, 256) < 4096u ? cdiv(n, 256) : 4096u, 256>>>(d_p, d_t, n, d_d, d_q, d_uv, d_f, d_s);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(dist, d_d, sizeof(double) * n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && closest) e = hipMemcpy(closest, d_q, sizeof(double) * 3 * n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && uv) e = hipMemcpy(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && feature) e = hipMemcpy(feature, d_f, n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && side) e = hipMemcpy(side, d_s, n, hipMemcpyDeviceToHost);
+    }
+    hipFree(d_p); hipFree(d_t); hipFree(d_d); hipFree(d_q); hipFree(d_uv); hipFree(d_f); hipFree(d_s);
     return e == hipSuccess ? CD_OK : -(int)e;
 }
 }  // extern "C"

@@ -63,6 +63,14 @@ CD_RAY_ANY = 1
 RAY_MISS = 0xFFFFFFFF
 
 
+class CdPointInfo(C.Structure):
+    _fields_ = [("n_found", C.c_uint64), ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64)]
+
+
+CD_POINT_ANY = 1
+POINT_NONE = 0xFFFFFFFF
+
+
 class CdMultiInfo(C.Structure):
     _fields_ = [("world", C.c_uint32), ("rank", C.c_uint32), ("n_peers", C.c_uint32), ("host_syncs", C.c_uint32), ("attempts", C.c_uint32),
                 ("failed_rank_plus1", C.c_uint32), ("sent_queries", C.c_uint64), ("recv_queries", C.c_uint64), ("local_pairs", C.c_uint64),
@@ -83,6 +91,7 @@ EXPORTS = [
     "cd_find_ccd", "cd_self_ccd", "cd_ccd_points",
     "cd_find_collisions_between", "cd_find_proximity_between", "cd_find_ccd_between",
     "cd_cast_rays", "cd_ray_tri_points",
+    "cd_closest_points", "cd_pt_tri_points",
 ]
 
 _lib = None
@@ -163,6 +172,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_find_ccd_between.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp, C.c_uint64, u64p, vp]
     lib.cd_cast_rays.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.cd_ray_tri_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp]
+    lib.cd_closest_points.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cd_pt_tri_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -423,6 +434,35 @@ class CollisionDetector:
         rc = self.lib.cd_cast_rays(self._ctx, _ptr(rays), n, 0, _ptr(face), _ptr(ids), _ptr(t), _ptr(uv), _ptr(side), C.byref(info))
         self._chk("cd_cast_rays", rc)
         return face, ids, t, uv, side, info
+
+    # ---- closest-point queries against this mesh (cd_closest_points)
+    def closest_points(self, points, rmax=np.inf, any_within: bool = False):
+        """cd_closest_points on the tree that is there.  points: [n, 3]; rmax: a scalar or [n], the search radius (+inf: the nearest
+        triangle wherever it is).  -> (face[n] (index into the face list, POINT_NONE = 0xFFFFFFFF when nothing is within rmax), ids[n],
+        dist[n] (+inf then), closest[n, 3], uv[n, 2], feature[n] (0 face, 1-3 edge 01 / 12 / 20, 4-6 vertex 0 / 1 / 2), side[n], info)
+        -- of the triangles with pt_tri's dist <= rmax, the smallest (dist, ID, face index).  side is the side of that triangle's
+        plane, not an inside / outside test.  any_within: (face[n], info); face is POINT_NONE or SOME triangle within rmax -- which
+        one is not defined, whether there is one is.
+        Projecting mesh a's vertices onto mesh b is  b.closest_points(a_verts): closest is the projection, (face, uv) where it lies.
+        Points are walked in the order given: keep spatially coherent points next to each other."""
+        pts = pack_points(points, rmax)
+        n = pts.shape[0]
+        face = np.empty(n, dtype=np.uint32)
+        info = CdPointInfo()
+        if any_within:
+            rc = self.lib.cd_closest_points(self._ctx, _ptr(pts), n, CD_POINT_ANY, _ptr(face), None, None, None, None, None, None, C.byref(info))
+            self._chk("cd_closest_points", rc)
+            return face, info
+        ids = np.empty(n, dtype=np.uint32)
+        dist = np.empty(n, dtype=np.float64)
+        closest = np.empty((n, 3), dtype=np.float64)
+        uv = np.empty((n, 2), dtype=np.float64)
+        feature = np.empty(n, dtype=np.uint8)
+        side = np.empty(n, dtype=np.uint8)
+        rc = self.lib.cd_closest_points(self._ctx, _ptr(pts), n, 0, _ptr(face), _ptr(ids), _ptr(dist), _ptr(closest), _ptr(uv), _ptr(feature), _ptr(side),
+                                        C.byref(info))
+        self._chk("cd_closest_points", rc)
+        return face, ids, dist, closest, uv, feature, side, info
 
     def find_collisions(self, cap: int = 1 << 20):
         return self._pairs_call(self.lib.cd_find_collisions, "cd_find_collisions", cap)
@@ -689,6 +729,34 @@ def ray_tri_points(rays, tris):
     if rc != CD_OK:
         raise CdError("cd_ray_tri_points", rc)
     return hit.astype(bool), t, uv, side
+
+
+def pack_points(points, rmax=np.inf) -> np.ndarray:
+    """[n, 4] doubles (x, y, z, rmax), the layout cd_closest_points takes."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    pts = np.empty((p.shape[0], 4), dtype=np.float64)
+    pts[:, 0:3] = p
+    pts[:, 3] = rmax
+    return pts
+
+
+def pt_tri_points(points, tris):
+    """pt_tri (the per-pair predicate of cd_closest_points) on explicit operands, on the device (cd_pt_tri_points): points [n, 3],
+    tris [n, 3, 3] -> (dist[n], closest[n, 3], uv[n, 2], feature[n], side[n])."""
+    q = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+    p = np.ascontiguousarray(np.asarray(tris, dtype=np.float64).reshape(-1, 9))
+    if q.shape[0] != p.shape[0]:
+        raise ValueError(f"{q.shape[0]} points against {p.shape[0]} triangles")
+    n = q.shape[0]
+    dist = np.zeros(n, dtype=np.float64)
+    closest = np.zeros((n, 3), dtype=np.float64)
+    uv = np.zeros((n, 2), dtype=np.float64)
+    feature = np.zeros(n, dtype=np.uint8)
+    side = np.zeros(n, dtype=np.uint8)
+    rc = load_library().cd_pt_tri_points(_ptr(q), _ptr(p), n, _ptr(dist), _ptr(closest), _ptr(uv), _ptr(feature), _ptr(side))
+    if rc != CD_OK:
+        raise CdError("cd_pt_tri_points", rc)
+    return dist, closest, uv, feature, side
 
 
 def ccd_points(tri, dist: float):

@@ -527,6 +527,59 @@ int cd_cast_rays(cd_ctx *ctx, const double *rays, uint64_t n, int flags, uint32_
  * arithmetic decides.  The pin of the device function. */
 int cd_ray_tri_points(const double *ray, const double *tri, uint64_t n, uint8_t *hit, double *t, double *uv, uint8_t *side);
 
+/* ---- closest-point queries: nearest triangle and within-radius (not reference behaviour) ----
+ * A query point is four doubles (x, y, z, rmax): finite coordinates and a search radius 0 <= rmax <= +inf.
+ * pt_tri(p; triangle p0 p1 p2) -> (dist, u, v, feature, side, q), FP64 with a fixed operation order, IEEE divide and sqrt and no
+ * contraction (csrc/cd_math.h), built from tri_distance's blocks in tri_distance's frame:
+ *   a = p0 - p, b = p1 - p, c = p2 - p (the query point becomes the origin O); m = the largest |component| of a, b, c;
+ *   m == 0 (three coincident vertices at p): dist = 0, u = v = 0, feature = 4, side = 0, q = p0;
+ *   else m = f 2^ex with f in [0.5, 1) and |ex| clamped at 1000; a, b, c are multiplied by 2^-ex (exact); then the minimum of four
+ *   squared distances taken in this order, a later term replacing an earlier one only when strictly smaller (an earlier term keeps a tie):
+ *     face:    with ab = b - a, ac = c - a, ap = O - a: d00 = ab.ab, d01 = ab.ac, d11 = ac.ac, d20 = ap.ab, d21 = ap.ac,
+ *              den = d00 d11 - d01 d01; +inf unless den > 0; fv = (d11 d20 - d01 d21) / den, fw = (d00 d21 - d01 d20) / den; +inf unless
+ *              fv >= 0, fw >= 0, fv + fw <= 1; the point (a + fv ab) + fw ac, its squared distance from O;  u = fv, v = fw, feature 0
+ *     edge 01: segment (a, b): t = (ap.ab) / (ab.ab) clamped to [0, 1] (0 when ab.ab is not > 0), the point a + t ab;
+ *              u = t, v = 0;      feature 1, or 4 (vertex 0) when t == 0, 5 (vertex 1) when t == 1
+ *     edge 12: segment (b, c) likewise;   u = 1 - t, v = t;  feature 2, or 5 when t == 0, 6 (vertex 2) when t == 1
+ *     edge 20: segment (c, a) likewise;   u = 0, v = 1 - t;  feature 3, or 6 when t == 0, 4 when t == 1
+ *   (a dot product is (x x + y y) + z z);  dist = sqrt(best) 2^ex;  side = 1 when ap . (ab x ac) > 0 on the scaled operands, else 0;
+ *   q = (w p0 + u p1) + v p2 per coordinate with w = (1 - u) - v, on the ORIGINAL vertices (not translated, not scaled).
+ * (u, v) are the barycentrics of the closest point, q = (1 - u - v) p0 + u p1 + v p2; on an edge or vertex feature they are exactly the
+ * 0 / t / 1 - t above.  feature 0 means the face term won -- the projection onto the plane lies in the CLOSED triangle -- so a point that
+ * projects exactly onto an edge reports 0.  q is returned; callers need not recompute it.  side is the side of THIS triangle's plane
+ * (1: the one that sees p0 p1 p2 counter-clockwise); on an edge or vertex feature it is NOT an inside / outside test of a surface.
+ * A degenerate triangle has the distance of the segment or point it is (its face term is +inf).  Finite input never gives a NaN;
+ * non-finite vertices give undefined results.  Scaling the point and the triangle by 2^k scales dist and q exactly and changes nothing
+ * in (u, v, feature, side) over the band of cd_find_proximity (largest |coordinate| from about 2^-320 to 2^256 and beyond).
+ *
+ * cd_closest_points, flags = 0: for point k, of the triangles of this context with pt_tri's dist <= rmax, the one with the smallest
+ * (dist, triangle ID, face index) in lexicographic order -- so a point equally far from two triangles (any point nearest to a shared
+ * edge or vertex) has one defined answer.  face[k]: its index in cd_create's face list, 0xFFFFFFFF when no triangle is within rmax;
+ * ids[k]: its ID; dist[k], closest[3 k ..], uv[2 k], uv[2 k + 1], feature[k], side[k]: pt_tri's values for it.  When nothing is within
+ * rmax dist[k] = +inf and the other outputs are 0.  ids, dist, closest, uv, feature, side may each be NULL.
+ * flags = CD_POINT_ANY (is anything within rmax?): face[k] = 0xFFFFFFFF when nothing is and SOME triangle with dist <= rmax otherwise.
+ * WHETHER there is one is defined (exactly where the closest call finds one); WHICH one is returned is not (it depends on the tree and
+ * may change from build to build).  ids, dist, closest, uv, feature and side must be NULL.
+ * info (may be NULL): points that found a triangle, boxes tested, pt_tri evaluations -- numbers of this tree, not of the mesh.
+ * Guarantee: the closest result depends on the mesh and the points only -- not on the Morton frame, CD_OPT_TRAVERSAL,
+ * CD_OPT_CELL_TABLE, the build variant or the order of the points.  Points are walked in the order given, one lane each, neighbours in
+ * one wave: spatially coherent points (a mesh's vertices in mesh order, a grid's rows) should be neighbours; the library does not sort them.
+ * Needs a tree built from the current vertices (CD_ERR_ORDER otherwise, including after cd_update_vertices without a rebuild).
+ * CD_ERR_ARG: a NULL context; NULL points or face with n > 0; flags other than 0 / CD_POINT_ANY; with CD_POINT_ANY an output other
+ * than face; a non-finite coordinate, an rmax that is NaN or negative -- checked on the host before anything is launched, and nothing
+ * is written then.  n = 0 returns CD_OK.  The call leaves cd_stats, the last pair list, the order hint, a captured CD_OPT_GRAPH step and
+ * the proximity, CCD, between-mesh and ray buffers as they were; it keeps device buffers of its own (grown on demand; cd_destroy frees
+ * them) and runs on the context's stream with one host synchronisation. */
+typedef struct cd_point_info { uint64_t n_found, node_visits, tri_tests; } cd_point_info;
+enum { CD_POINT_ANY = 1 };
+int cd_closest_points(cd_ctx *ctx, const double *points, uint64_t n, int flags, uint32_t *face, uint32_t *ids, double *dist,
+                      double *closest, double *uv, uint8_t *feature, uint8_t *side, cd_point_info *info);
+/* pt_tri on explicit operands (host pointers; no context): points is n x 3 doubles (no radius), tri n x 9 (p0, p1, p2).  dist[k],
+ * closest[3 k ..], uv[2 k], uv[2 k + 1], feature[k], side[k]: pt_tri's values; every output except dist may be NULL.  No argument is
+ * checked for finiteness: the arithmetic decides.  The pin of the device function. */
+int cd_pt_tri_points(const double *points, const double *tri, uint64_t n, double *dist, double *closest, double *uv,
+                     uint8_t *feature, uint8_t *side);
+
 /* Library / build identification: "mi355cd <version> gfx950". */
 const char *cd_version(void);
 
