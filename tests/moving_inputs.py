@@ -1,0 +1,518 @@
+"""Meshes that MOVE: the motion sequences of tests/test_moving_mesh_gpu.py, their per-frame queries and CPU references, and the
+comparison helpers (no test in here: importing it generates nothing; everything is built on first use and cached).
+
+A sequence is a list of vertex arrays over one fixed index array, with a seed, the mean edge length of frame 0 (the way query_meshes
+carries `edge`) and, per frame, the factor its lengths are scaled by (distances and end positions follow it).  What each sequence is
+for is in its builder's docstring; tests/test_moving_inputs.py holds them to it.
+
+Every reference of a frame is the existing CPU restatement on that frame's vertices alone: nothing here knows what the frame before
+it was, so a device result that matches is not the previous frame's (test_moving_inputs.py: consecutive frames differ enough)."""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+import between_ref as br
+import ccd_ref as cr
+import mi355_synth as synth
+import oracle
+import point_ref as ptr
+import proximity_ref as pr
+import ray_ref as rr
+import swept_ref as sr
+from test_between_gpu import _same_ccd as same_between_ccd, _same_contact as same_between_contact, _same_prox as same_between_prox  # noqa: F401
+from test_ccd_gpu import _same as _same_ccd
+from test_points_gpu import _same as same_points
+from test_proximity_gpu import _same as _same_prox
+from test_rays_gpu import _same as same_rays  # noqa: F401
+
+NQ = 1000                       # rays, and points, a frame: 15 full waves and a ragged one of 40
+MISS = 0xFFFFFFFF
+OFFSET = 2.0 ** 20 + 0.37       # the translated tests' offset (test_rays_gpu.py, test_points_gpu.py)
+TINY = (1, 2, 3, 63, 64, 65)
+# the first candidate buffer of the proximity / CCD passes: 64 shards of max(4096, 16 n / 64) (test_swept_gpu.py's regrowth test)
+first_candidate_buffer = lambda n: 64 * max(4096, (16 * n + 63) // 64)
+
+
+def _f32(a):
+    with np.errstate(over="ignore"):
+        return np.ascontiguousarray(np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64))
+
+
+class Sequence:
+    def __init__(self, name, seed, edge, vidx, frames, frame_mode="reference", scales=None, notes=None):
+        self.name, self.seed, self.edge, self.vidx = name, seed, edge, np.ascontiguousarray(vidx, dtype=np.uint32)
+        self.frames = [np.ascontiguousarray(v, dtype=np.float64) for v in frames]
+        self.frame_mode = frame_mode                                           # "reference": morton.h's fixed frame; "auto": CD_FRAME_AUTO
+        self.scales = [1.0] * len(frames) if scales is None else [float(s) for s in scales]
+        self.notes = notes or {}
+        assert len(self.scales) == len(self.frames) and all(v.shape == self.frames[0].shape for v in self.frames)
+
+    @property
+    def nt(self):
+        return self.vidx.shape[0]
+
+    def __len__(self):
+        return len(self.frames)
+
+
+# ---------------------------------------------------------------- the sequences
+JITTER_DENSE, JITTER_DENSE_FRAME = 256, 2
+
+
+def _jitter():
+    """soup(3000, e = 0.05), its centroids drawn in to 0.7 of the generation box (the walk below stays inside the reference's Morton
+    frame: leaving it is frame_exit's subject); every frame adds fresh normal noise of 0.4 edges to the frame before (rounded to
+    fp32, like a loader's output), so the Morton order changes.  Frame 2 is the dense one: the scale of the first JITTER_DENSE
+    triangles' centroids collapses to a fiftieth (the triangles keep their size), so every pair of them is a candidate -- 32 k pairs
+    from a few neighbouring 64-query blocks, which overflows those blocks' shards of the first candidate buffers (4096 a shard for
+    proximity and CCD) and makes those passes grow their buffers and run again.  Collapsing the whole soup
+    far enough for the TOTAL to pass the first buffer would cost the CPU restatements more than 300 k exact pairs a query.  Frame 3
+    continues from frame 1's walk and is sparse again, on the grown buffers."""
+    seed, e = 101, 0.05
+    v, i = synth.soup(3000, e=e, seed=seed)
+    tri = v.reshape(-1, 3, 3)                                                   # (private vertices: triangle t owns vertices 3 t .. 3 t + 2)
+    c = tri.mean(axis=1, keepdims=True)
+    mid = 0.5 * (synth.BOX_LO + synth.BOX_HI)
+    v = _f32((mid + (c - mid) * 0.7 + (tri - c)).reshape(-1, 3))
+    g = np.random.default_rng(seed)
+    frames, walk = [v], v
+    for f in range(1, 7):
+        walk = _f32(walk + g.normal(0.0, 0.4 * e, walk.shape))
+        frames.append(walk)
+    tri = frames[JITTER_DENSE_FRAME].reshape(-1, 3, 3).copy()
+    k = JITTER_DENSE
+    c = tri[:k].mean(axis=1, keepdims=True)
+    c0 = c.mean(axis=0, keepdims=True)
+    tri[:k] = c0 + (c - c0) * 0.02 + (tri[:k] - c)
+    frames[JITTER_DENSE_FRAME] = _f32(tri.reshape(-1, 3))
+    return Sequence("jitter", seed, e, i, frames)
+
+
+SLIDE_QUADS = 24
+SLIDE_SHRINK = 0.8
+SLIDE_PATH = ((0, 0), (1, 0), (2, 0), (2, 1), (2, 2), (1, 2), (0, 2))           # sheet B's position in quads along x and z: one quad a frame
+SLIDE_QUAD = (2.88 / SLIDE_QUADS * SLIDE_SHRINK, 2.18 / SLIDE_QUADS * SLIDE_SHRINK)      # a quad's extent along x and along z
+
+
+@functools.lru_cache(maxsize=None)
+def _slide_base():
+    """cloth_pair(24) drawn in to 0.8 of its size about the middle of the generation box (rounded to fp32), so that a sheet can slide
+    two quads each way and stay inside the reference's Morton frame."""
+    v, i = synth.cloth_pair(SLIDE_QUADS)
+    mid = 0.5 * (synth.BOX_LO + synth.BOX_HI)
+    return _f32(mid + (v - mid) * SLIDE_SHRINK), i
+
+
+def _shifted(v, qx, qz):
+    """bench.py's moving-mesh construction (mi355_synth has none): vertices shifted by whole quads, float-valued like the loader's output."""
+    w = v.copy()
+    w[:, 0] = np.float32(w[:, 0] + np.float32(qx * SLIDE_QUAD[0]))
+    w[:, 2] = np.float32(w[:, 2] + np.float32(qz * SLIDE_QUAD[1]))
+    return w
+
+
+def _slide():
+    """The cloth pair of _slide_base, sheet B sliding one quad a frame over sheet A (two along x, two along z, two back along x):
+    neighbouring frames share sheet A's half of the tree."""
+    v, i = _slide_base()
+    half = v.shape[0] // 2
+    frames = [np.concatenate([v[:half], _shifted(v[half:], qx, qz)]) for qx, qz in SLIDE_PATH]
+    return Sequence("slide", 102, SLIDE_QUAD[0], i, frames)
+
+
+SCALE_WALK_K = (0, 20, 60, 20, -40, 0, 0, 0)
+SCALE_WALK_OFFSET_FRAME = 6
+
+
+def _scale_walk():
+    """soup(1000, e = 0.15) with a fresh jitter every frame, times 2^k for k = 0, 20, 60, 20, -40, 0 (inside the band of
+    tests/scale_inputs.py), then one frame at + (2^20 + 0.37) -- full doubles, M = 2^20 -- and one back at the origin: M and the root
+    box grow, shrink, grow and shrink again.  In CD_FRAME_AUTO (in the reference's frame all of these keys but frame 0's are one)."""
+    seed, e = 103, 0.15
+    v, i = synth.soup(1000, e=e, seed=seed)
+    g = np.random.default_rng(seed)
+    frames = []
+    for f, k in enumerate(SCALE_WALK_K):
+        w = _f32(v + g.normal(0.0, 0.3 * e, v.shape))
+        frames.append(w + OFFSET if f == SCALE_WALK_OFFSET_FRAME else np.ldexp(w, k))
+    return Sequence("scale_walk", seed, e, i, frames, frame_mode="auto", scales=[2.0 ** k for k in SCALE_WALK_K])
+
+
+FRAME_EXIT_OUT = (2, 3)
+
+
+def _frame_exit():
+    """test_sort_returns_to_its_first_form_when_the_mesh_is_back_inside_the_frame's construction at cloth_pair(24): sheet B 0.2 beyond
+    the reference's Morton frame in frames 2 and 3 (keys beyond 2^60: the sort takes its second form), inside before and after, with
+    a jitter of a fifth of a quad from frame 1 on."""
+    seed = 104
+    v, i = synth.cloth_pair(24)
+    quad = 2.88 / 24
+    g = np.random.default_rng(seed)
+    frames = [v]
+    for f in range(1, 6):
+        w = v + g.normal(0.0, 0.2 * quad, v.shape)
+        if f in FRAME_EXIT_OUT:
+            w[v.shape[0] // 2:, 0] += 0.2
+        frames.append(_f32(w))
+    return Sequence("frame_exit", seed, quad, i, frames)
+
+
+def _float_double():
+    """cloth_pair(24) with a fresh jitter every frame: fp32-representable vertices in the even frames, full doubles in the odd ones
+    (test_update_vertices_switches_the_cell_table_on_and_off: the cell table comes and goes).  In CD_FRAME_AUTO, like that test."""
+    seed = 105
+    vd, i = synth.cloth_pair(24, round_f32=False)
+    quad = 2.88 / 24
+    g = np.random.default_rng(seed)
+    frames = []
+    for f in range(6):
+        w = vd + g.normal(0.0, 0.2 * quad, vd.shape)
+        frames.append(w if f % 2 else _f32(w))
+    return Sequence("float_double", seed, quad, i, frames, frame_mode="auto")
+
+
+COLLAPSE_FRAMES = (2,)
+COLLAPSE_LOG2 = -22
+
+
+def _collapse():
+    """soup(1000, e = 0.08), jittered; in frame 2 the whole mesh is scaled by 2^-22 about the centre of one Morton cell of the
+    reference's frame: every centroid lies in that cell (all keys equal: the sort's full form, a tree of index tie-breaks, compare
+    test_every_morton_key_equal), the triangles are far below the fp32 spacing at 1 (full doubles: the cell table), and the frames
+    after it are the ordinary soup again."""
+    seed, e = 106, 0.08
+    v, i = synth.soup(1000, e=e, seed=seed)
+    g = np.random.default_rng(seed)
+    cell = synth.REF_SPAN / 2.0 ** 20
+    centre = synth.REF_OFF + (np.floor((np.array([1.5, -0.1, 0.75]) - synth.REF_OFF) / cell) + 0.5) * cell
+    mid = 0.5 * (synth.BOX_LO + synth.BOX_HI)
+    frames, scales, walk = [], [], v
+    for f in range(6):
+        if f:
+            walk = _f32(walk + g.normal(0.0, 0.5 * e, walk.shape))
+        if f in COLLAPSE_FRAMES:
+            frames.append(centre + np.ldexp(walk - mid, COLLAPSE_LOG2)); scales.append(2.0 ** COLLAPSE_LOG2)
+        else:
+            frames.append(walk); scales.append(1.0)
+    return Sequence("collapse", seed, e, i, frames, scales=scales)
+
+
+def _tiny(n):
+    """query_meshes' soup of n triangles (n = 1, 2, 3, 63, 64, 65: no record, one record, a wave and one more), jittered over 4 frames."""
+    seed, e = 110 + n, 0.3
+    v, i = synth.soup(n, e=e, seed=n)
+    g = np.random.default_rng(seed)
+    frames, walk = [v], v
+    for f in range(1, 4):
+        walk = _f32(walk + g.normal(0.0, 0.5 * e, walk.shape))
+        frames.append(walk)
+    return Sequence(f"tiny{n}", seed, e, i, frames)
+
+
+_BUILDERS = {"jitter": _jitter, "slide": _slide, "scale_walk": _scale_walk, "frame_exit": _frame_exit, "float_double": _float_double,
+             "collapse": _collapse, **{f"tiny{n}": functools.partial(_tiny, n) for n in TINY}}
+NAMES = tuple(_BUILDERS)
+LARGE = tuple(n for n in NAMES if not n.startswith("tiny"))
+
+
+@functools.lru_cache(maxsize=None)
+def seq(name) -> Sequence:
+    return _BUILDERS[name]()
+
+
+# ---------------------------------------------------------------- per-frame queries and their references (cached: the schedules share them)
+def edge_at(name, f):
+    s = seq(name)
+    return s.edge * s.scales[f]
+
+
+def prox_dist(name, f):
+    return edge_at(name, f) / 4
+
+
+def ccd_dist(name, f):
+    return edge_at(name, f) / 10
+
+
+def _brute(s):
+    """The restatements take every pair on the tiny meshes and the grid's candidates (boxes widened by dist and M / 1024: every pair
+    where M is large, as on scale_walk's translated frame and the collapsed one) on the others."""
+    return s.nt <= 65
+
+
+@functools.lru_cache(maxsize=None)
+def x1(name, f):
+    """The CCD end positions of frame f: test_ccd_gpu.py's _move (noise per vertex and one shift of the whole mesh) at that frame's scale,
+    at half its size -- the restatement's cost goes with the pairs whose swept boxes meet."""
+    s = seq(name)
+    g = np.random.default_rng(s.seed)
+    e = edge_at(name, f)
+    v = s.frames[f]
+    return v + g.normal(size=v.shape) * e * 0.15 + g.normal(size=(1, 3)) * e * 0.5
+
+
+@functools.lru_cache(maxsize=None)
+def rays(name, f):
+    s = seq(name)
+    return rr.mesh_rays(s.frames[f], s.vidx, NQ, seed=s.seed)
+
+
+@functools.lru_cache(maxsize=None)
+def want_rays(name, f):
+    s = seq(name)
+    return rr.cast_rays_ref(s.frames[f], s.vidx, None, rays(name, f))
+
+
+@functools.lru_cache(maxsize=None)
+def points(name, f):
+    s = seq(name)
+    return ptr.mesh_points(s.frames[f], s.vidx, NQ, seed=s.seed, edge=edge_at(name, f))
+
+
+@functools.lru_cache(maxsize=None)
+def want_points(name, f):
+    s = seq(name)
+    return ptr.closest_points_ref(s.frames[f], s.vidx, None, points(name, f))
+
+
+@functools.lru_cache(maxsize=None)
+def radii(name, f):
+    return ptr.radii(want_points(name, f)[2], edge_at(name, f), seed=seq(name).seed)
+
+
+@functools.lru_cache(maxsize=None)
+def want_points_r(name, f):
+    s = seq(name)
+    return ptr.closest_points_ref(s.frames[f], s.vidx, None, points(name, f), radii(name, f))
+
+
+@functools.lru_cache(maxsize=None)
+def want_prox(name, f):
+    s = seq(name)
+    return pr.proximity_pairs(s.frames[f], s.vidx, None, prox_dist(name, f), brute=_brute(s))
+
+
+@functools.lru_cache(maxsize=None)
+def want_ccd(name, f):
+    """(pairs, toi, dists), (pairs through the gate, evaluations)"""
+    s = seq(name)
+    return cr.ccd_pairs(s.frames[f], x1(name, f), s.vidx, None, ccd_dist(name, f), counts=True, brute=_brute(s))
+
+
+def _pipeline(mode, v, vidx):
+    if mode == "auto":
+        off, span, lay = oracle.auto_frame(v, vidx)
+        return oracle.pipeline(v, vidx, off=off, span=span, layout=lay)
+    return oracle.pipeline(v, vidx)
+
+
+@functools.lru_cache(maxsize=None)
+def want_step(name, f):
+    """oracle.pipeline on frame f in the sequence's Morton frame: keys, permutation, tree, the collision step's pairs and counters."""
+    s = seq(name)
+    return _pipeline(s.frame_mode, s.frames[f], s.vidx)
+
+
+def root_box(v, vidx):
+    """cd_root_box: (xmin, xmax, ymin, ymax, zmin, zmax) over the triangles' vertices."""
+    p = np.asarray(v, dtype=np.float64)[np.asarray(vidx).astype(np.int64).ravel()]
+    return np.stack([p.min(axis=0), p.max(axis=0)], axis=1).ravel()
+
+
+def want_root_box(name, f):
+    s = seq(name)
+    return root_box(s.frames[f], s.vidx)
+
+
+def expected_swept(x0, x1_, vidx, step, m_bits, dist):
+    """What cd_debug_swept, cd_debug_records and cd_export_keys return for a correct device, from the oracle's tree `step`
+    (oracle.pipeline) and the restatement: the dict test_swept_gpu.py's _read makes (the static records hold their link and range words
+    only; nothing compares their boxes here)."""
+    n = np.asarray(vidx).reshape(-1, 3).shape[0]
+    none = np.zeros((0, 8), dtype=np.uint32)
+    out = dict(perm=step["perm"], m_bits=int(m_bits), pad=sr.pad(int(m_bits), dist))
+    if n < 2:
+        return dict(out, srr=none, srl=none, rr=none, rl=none, up=np.zeros(0, dtype=np.int32))
+    lo, hi = sr.swept_leaf_boxes(x0, x1_, vidx, step["perm"])
+    (L, R, F, La), _ = sr.tree_from_karras(step["left"], step["right"], step["range_first"], step["range_last"])
+    l_lo, l_hi, r_lo, r_hi = sr.swept_records((lo, hi), L, R, F, La)
+    m = n - 1
+    rr_, rl_ = np.zeros((n, 8), dtype=np.uint32), np.zeros((n, 8), dtype=np.uint32)
+    rl_[:m, 0:3], rl_[:m, 3:6], rl_[:m, 6], rl_[:m, 7] = sr.bits(l_lo), sr.bits(l_hi), L.view(np.uint32), F.astype(np.uint32)
+    rr_[:m, 0:3], rr_[:m, 3:6], rr_[:m, 6], rr_[:m, 7] = sr.bits(r_lo), sr.bits(r_hi), R.view(np.uint32), La.astype(np.uint32) | np.uint32(0x80000000)
+    return dict(out, srr=rr_, srl=rl_, rr=rr_, rl=rl_, up=sr.parents(L, R))
+
+
+@functools.lru_cache(maxsize=None)
+def want_swept(name, f):
+    s = seq(name)
+    v, e = s.frames[f], x1(name, f)
+    return expected_swept(v, e, s.vidx, want_step(name, f), sr.m_bits(v, e, s.vidx), ccd_dist(name, f))
+
+
+@functools.lru_cache(maxsize=None)
+def want_candidates(name, f):
+    """n_candidates of cd_find_ccd on frame f (the pairs of query box and leaf box: independent of the tree's shape)."""
+    s = seq(name)
+    v, e = s.frames[f], x1(name, f)
+    lo, hi = sr.swept_leaf_boxes(v, e, s.vidx, want_step(name, f)["perm"])
+    return sr.expected_candidates(lo, hi, sr.pad(sr.m_bits(v, e, s.vidx), ccd_dist(name, f)))
+
+
+@functools.lru_cache(maxsize=None)
+def ccd_shard_load(name, f):
+    """The largest number of candidates one shard of cd_find_ccd's candidate buffer is asked to hold on frame f: the descent runs 64
+    queries (sorted leaves) a block and block b reserves in shard b & 63 (cd_proximity.h).  Above SHARD_FIRST the pass has to grow."""
+    s = seq(name)
+    v, e = s.frames[f], x1(name, f)
+    lo, hi = sr.swept_leaf_boxes(v, e, s.vidx, want_step(name, f)["perm"])
+    qlo, qhi = sr.query_boxes(lo, hi, sr.pad(sr.m_bits(v, e, s.vidx), ccd_dist(name, f)))
+    n = lo.shape[0]
+    per_query = np.zeros(n, dtype=np.int64)
+    for r0 in range(0, n, 512):
+        r1 = min(n, r0 + 512)
+        ok = np.all((qlo[r0:r1, None, :] <= hi[None, :, :]) & (lo[None, :, :] <= qhi[r0:r1, None, :]), axis=-1)
+        ok &= np.arange(n)[None, :] > np.arange(r0, r1)[:, None]
+        per_query[r0:r1] = ok.sum(axis=1)
+    per_block = np.add.reduceat(per_query, np.arange(0, n, 64))
+    return int(np.bincount(np.arange(per_block.shape[0]) & 63, weights=per_block).max())
+
+
+SHARD_FIRST = 4096              # slots a shard of the first proximity / CCD candidate buffer has: max(4096, 16 n / 64), 4096 up to 16 k triangles
+
+
+# ---------------------------------------------------------------- the comparisons (each raises AssertionError; test_moving_inputs.py plants the error)
+def _bits(d):
+    return np.ascontiguousarray(d, dtype=np.float64).view(np.uint64)
+
+
+def read_swept(cd, other=None):
+    """test_swept_gpu.py's _read: the swept tree `cd` holds with the static records and the order it lies over."""
+    srr, srl, up, mb, pad = cd.debug_swept(other)
+    owner = cd if other is None else other
+    rec_r, rec_l, _, _ = owner.debug_records()
+    _, perm = owner.export_keys()
+    return dict(srr=srr, srl=srl, up=up, m_bits=mb, pad=pad, rr=rec_r, rl=rec_l, perm=perm)
+
+
+def same_prox(got, want, what=""):
+    """got: find_proximity's (pairs, dists, n, rc); want: the restatement's sorted (pairs, dists)."""
+    assert got[3] == 0 and got[2] == want[0].shape[0], (what, got[3], got[2], want[0].shape[0])
+    _same_prox(got, want)
+
+
+def same_ccd(got, want, what="", info=None, counts=None):
+    """got: find_ccd's (pairs, toi, dists, n, rc); want: the restatement's sorted (pairs, toi, dists); info / counts: cd_ccd_info
+    against the restatement's (pairs through the gate, evaluations), as test_ccd_gpu.py compares them."""
+    assert got[4] == 0 and got[3] == want[0].shape[0], (what, got[4], got[3], want[0].shape[0])
+    _same_ccd(got, want)
+    if info is not None:
+        assert (info.n_tested, info.n_evals) == tuple(counts), (what, info.n_tested, info.n_evals, counts)
+        assert info.n_candidates >= info.n_tested, what
+
+
+def same_any_hit(face, n_hits, rays_, verts, vidx, want, what=""):
+    """test_any_hit_is_defined_where_it_is_defined's rule: WHETHER there is a hit is defined, and the triangle returned is one ray_tri hits."""
+    assert np.array_equal(face != MISS, want[0] != MISS), what
+    k = np.nonzero(face != MISS)[0]
+    nt = np.asarray(vidx).shape[0]
+    assert (face[k] < nt).all(), what
+    tris = np.asarray(verts, dtype=np.float64)[np.asarray(vidx).astype(np.int64)]
+    assert rr.ray_tri_np(rays_[k], tris[face[k]])[0].all(), what
+    assert n_hits == k.size, what
+
+
+def same_any_within(face, n_found, pts, rm, verts, vidx, want, what=""):
+    """test_any_within_is_defined_where_it_is_defined's rule, for points."""
+    assert np.array_equal(face != MISS, want[0] != MISS), what
+    k = np.nonzero(face != MISS)[0]
+    nt = np.asarray(vidx).shape[0]
+    assert (face[k] < nt).all(), what
+    tris = np.asarray(verts, dtype=np.float64)[np.asarray(vidx).astype(np.int64)]
+    assert (ptr.pt_tri_np(pts[k], tris[face[k]])[0] <= np.broadcast_to(rm, (pts.shape[0],))[k]).all(), what
+    assert n_found == k.size, what
+
+
+def same_swept(t, x0, x1_, vidx, m_bits, dist, what="", leaves_perm_a=None, a=None, n_candidates=None):
+    """The read-back `t` (read_swept) of the swept tree over (x0, x1_, vidx) against the restatement: links, up[], every box float, M
+    and the pad, as test_swept_gpu.py's _check_self / _check_between do.  n_candidates: the descent's count, compared with the
+    restatement's (self; between two meshes with a = (x0, x1, vidx, perm) of the query side)."""
+    n = np.asarray(vidx).reshape(-1, 3).shape[0]
+    lo, hi = sr.swept_leaf_boxes(x0, x1_, vidx, t["perm"])
+    if n < 2:
+        assert t["srr"].shape[0] == 0 and t["srl"].shape[0] == 0 and t["up"].shape[0] == 0, what
+        halves = 0
+    else:
+        assert t["srr"].shape[0] == n, (what, t["srr"].shape[0], n)
+        halves = sr.compare_links(t["rr"], t["rl"], t["srr"], t["srl"], t["up"])
+        want = sr.swept_records((lo, hi), *sr.tree_from_records(t["rr"], t["rl"]))
+        assert sr.compare_records(t["srr"], t["srl"], want, t["up"], what, leaves=(lo, hi)) == halves == 2 * (n - 1)
+    p = sr.compare_pad(t["m_bits"], t["pad"], m_bits, dist)
+    if n_candidates is not None:
+        if a is None:
+            sr.compare_count(n_candidates, sr.expected_candidates(lo, hi, p), what)
+        else:
+            lo_a, hi_a = sr.swept_leaf_boxes(*a)
+            sr.compare_count(n_candidates, sr.expected_candidates(lo_a, hi_a, p, lo, hi), what)
+    return halves
+
+
+def same_root_box(got, want, what=""):
+    assert np.array_equal(_bits(got), _bits(want)), (what, np.asarray(got).tolist(), np.asarray(want).tolist())
+
+
+def same_step(pairs, n, rc, pairs_tested, step, what=""):
+    """A collision step's own result against oracle.pipeline's: the pair set, the count and pairs_tested."""
+    assert rc == 0 and n == step["stats"].n_pairs, (what, rc, n, step["stats"].n_pairs)
+    assert np.array_equal(oracle.pair_set(pairs), oracle.pair_set(step["pairs"])), what
+    assert pairs_tested == step["stats"].pairs_tested, (what, pairs_tested, step["stats"].pairs_tested)
+
+
+# ---------------------------------------------------------------- between two meshes
+BETWEEN_FRAMES = 6
+BETWEEN_SCHEDULES = ("a_moves", "b_moves", "both_move")
+BETWEEN_DIST = SLIDE_QUAD[0] / 4
+BETWEEN_CCD_DIST = SLIDE_QUAD[0] / 10
+
+
+@functools.lru_cache(maxsize=None)
+def between_meshes():
+    """The two sheets of `slide` as meshes of their own: (va, ia, vb, ib), each with 0-based vertex indices."""
+    v, i = _slide_base()
+    half, na = v.shape[0] // 2, i.shape[0] // 2
+    assert i[:na].max() < half and i[na:].min() >= half
+    return np.ascontiguousarray(v[:half]), np.ascontiguousarray(i[:na]), np.ascontiguousarray(v[half:]), np.ascontiguousarray((i[na:] - half).astype(np.uint32))
+
+
+@functools.lru_cache(maxsize=None)
+def between_positions(schedule):
+    """Per frame (va, vb, a moved, b moved): a slides along x, b along z, one quad a frame (0, 1, 2, 1, 0, 1: inside the reference's
+    frame), whichever the schedule moves."""
+    va, ia, vb, ib = between_meshes()
+    at = lambda k: 2 - abs(2 - k % 4)
+    out = []
+    for f in range(BETWEEN_FRAMES):
+        ma, mb = f > 0 and schedule != "b_moves", f > 0 and schedule != "a_moves"
+        out.append((_shifted(va, at(f) if schedule != "b_moves" else 0, 0), _shifted(vb, 0, at(f) if schedule != "a_moves" else 0), ma, mb))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def between_x1(schedule, f):
+    wa, wb, _, _ = between_positions(schedule)[f]
+    return br.motion(wa, 0.15 * SLIDE_QUAD[0], 11), br.motion(wb, 0.15 * SLIDE_QUAD[0], 12)
+
+
+@functools.lru_cache(maxsize=None)
+def want_between(schedule, f, swap=False):
+    """between_ref's contact, proximity and CCD pairs of frame f in the roles (a, b), or (b, a) with swap."""
+    wa, wb, _, _ = between_positions(schedule)[f]
+    _, ia, _, ib = between_meshes()
+    ea, eb = between_x1(schedule, f)
+    if swap:
+        wa, ia, ea, wb, ib, eb = wb, ib, eb, wa, ia, ea
+    return dict(contact=br.contact_pairs(wa, ia, wb, ib, brute=False), prox=br.proximity_pairs(wa, ia, wb, ib, BETWEEN_DIST, brute=False),
+                ccd=br.ccd_pairs(wa, ia, wb, ib, BETWEEN_CCD_DIST, ea, eb, brute=False))       # (the grid's candidates: 1.3 M pairs otherwise)

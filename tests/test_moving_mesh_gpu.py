@@ -1,0 +1,241 @@
+"""Every query on a mesh that MOVES, through every rebuild path: one long-lived context per sequence of tests/moving_inputs.py (two
+for the queries between meshes); per frame cd_update_vertices, ONE rebuild entry, then every query in a seeded order that changes from
+frame to frame.  Each result is compared bit for bit with the CPU restatement of that frame (the reference) and with a fresh context
+created on that frame's vertices and built with cd_build_tree (a differential check: it also covers what the restatements do not
+restate).  tests/test_moving_inputs.py shows, without a GPU, that the previous frame's result fails every comparison used here.
+
+Counters that are NOT compared with the fresh context's: node_visits and tri_tests of cd_cast_rays / cd_closest_points, and the
+collision step's node_visits and wave_steps -- they count the walk, which may legitimately differ with the options the entry left
+behind (traversal bookkeeping, the order hint).  pairs_tested of a collision step is compared with the oracle's, proximity's and CCD's
+evaluation counts with the restatement's and the fresh context's, n_candidates with swept_ref's count and the fresh context's."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import ccd_ref as cr
+import mi355cd
+import moving_inputs as mi
+import proximity_ref as pr
+import swept_ref as sr
+
+pytestmark = pytest.mark.gpu
+
+CAP = 1 << 20
+ENTRIES = ("build_tree", "self_collide", "graph", "self_proximity", "self_ccd", "stagewise")
+FRAME = {"reference": mi355cd.CD_FRAME_REFERENCE, "auto": mi355cd.CD_FRAME_AUTO}
+
+
+def _enter(cd, entry, x1, prox_d, ccd_d):
+    """One rebuild entry on the vertices the context holds.  -> the entry's own result: (pairs, n, rc) of a collision step,
+    find_proximity's / find_ccd's tuple of cd_self_proximity / cd_self_ccd, None of cd_build_tree."""
+    cd.set_option(mi355cd.CD_OPT_GRAPH, 1 if entry == "graph" else 0)
+    if entry == "build_tree":
+        cd.build_tree()
+        return None
+    if entry == "self_collide":
+        return cd.self_collide(cap=CAP)
+    if entry == "stagewise":
+        cd.debug_set(mi355cd.CD_DBG_STAGEWISE_BUILD, 1)
+        try:
+            got = cd.self_collide(cap=CAP)
+            assert cd.debug_get(mi355cd.CD_DBG_GET_TREE_WAS_FUSED) == 0
+        finally:
+            cd.debug_set(mi355cd.CD_DBG_STAGEWISE_BUILD, 0)
+        return got
+    if entry == "graph":                                                       # what a captured step needs; the frame's step is a replay
+        cd.set_option(mi355cd.CD_OPT_STAGE_TIMING, 0)
+        cd.set_option(mi355cd.CD_OPT_KERNEL_STAMPS, 0)
+        for _ in range(2):                                                     # capture (again, if the sort changed its form), a replay
+            cd.self_collide(cap=CAP)
+        rep0 = cd.debug_get(mi355cd.CD_DBG_GET_GRAPH_REPLAYS)
+        got = cd.self_collide(cap=CAP)
+        # A context whose sort has gone to its half-key or full form (one long run of equal keys: `collapse`) stays with it for good and
+        # captures nothing (graph_eligible in csrc/mi355cd.hip): there the step with the option on is the stream's, and must say so.
+        replayed = 1 if cd.debug_get(mi355cd.CD_DBG_GET_SORT_FORM) <= 1 else 0
+        assert cd.debug_get(mi355cd.CD_DBG_GET_GRAPH_REPLAYS) == rep0 + replayed, "the frame's step is not a replay: nothing of the graph path would be tested"
+        return got
+    if entry == "self_proximity":
+        return cd.self_proximity(prox_d, cap=CAP)
+    assert entry == "self_ccd"
+    return cd.self_ccd(x1, ccd_d, cap=CAP)
+
+
+def _rebuild(cd, entry, name, f):
+    """The entry, with its own result against the frame's reference where it has one."""
+    what = f"{name} frame {f}: {entry}'s own result"
+    got = _enter(cd, entry, mi.x1(name, f), mi.prox_dist(name, f), mi.ccd_dist(name, f))
+    if entry in ("self_collide", "graph", "stagewise"):
+        mi.same_step(*got, cd.stats().pairs_tested, mi.want_step(name, f), what)
+    elif entry == "self_proximity":
+        mi.same_prox(got, mi.want_prox(name, f), what)
+    elif entry == "self_ccd":
+        want, counts = mi.want_ccd(name, f)
+        mi.same_ccd(got, want, what, cd.ccd_info, counts)
+
+
+def _equal_bytes(a, b, what):
+    for k, (x, y) in enumerate(zip(a, b)):
+        assert np.array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8)), (what, k)
+
+
+def _queries(cd, fresh, name, f):
+    """The queries of frame f as (label, callable): each compares the long-lived context with the reference and with the fresh one."""
+    s = mi.seq(name)
+    v, vidx = s.frames[f], s.vidx
+    what = f"{name} frame {f}"
+    rays, pts, rm = mi.rays(name, f), mi.points(name, f), mi.radii(name, f)
+    cast = lambda c, **kw: c.cast_rays(rays[:, 0:3], rays[:, 3:6], rays[:, 6], **kw)
+
+    def proximity():
+        d = mi.prox_dist(name, f)
+        got = cd.find_proximity(d, cap=CAP)
+        mi.same_prox(got, mi.want_prox(name, f), what + " proximity")
+        tested = cd.proximity_tested
+        gf = fresh.find_proximity(d, cap=CAP)
+        mi.same_prox(got, pr.sort_pairs(gf[0], gf[1]), what + " proximity against the fresh context")
+        assert tested == fresh.proximity_tested, (what, tested, fresh.proximity_tested)
+
+    def ccd():
+        d, e = mi.ccd_dist(name, f), mi.x1(name, f)
+        want, counts = mi.want_ccd(name, f)
+        got = cd.find_ccd(e, d, cap=CAP)
+        info = cd.ccd_info
+        mi.same_ccd(got, want, what + " ccd", info, counts)
+        sr.compare_count(info.n_candidates, mi.want_candidates(name, f), what + " ccd")
+        t = mi.read_swept(cd)                                                  # right after the CCD call: records, up[], M bits, the pad
+        mi.same_swept(t, v, e, vidx, sr.m_bits(v, e, vidx), d, what + " swept tree")
+        gf = fresh.find_ccd(e, d, cap=CAP)
+        mi.same_ccd(got, cr.sort_pairs(*gf[:3]), what + " ccd against the fresh context")
+        fi = fresh.ccd_info
+        assert bytes(info) == bytes(fi), (what, [(k, getattr(info, k), getattr(fi, k)) for k, _ in mi355cd.CdCcdInfo._fields_])
+        tf = mi.read_swept(fresh)
+        # slot n - 1 of the records names no split: nothing writes it.  Word 7 is the range word: its low 30 bits; bits 30 / 31 are the static
+        # records' CERTAIN / EXACT flags, copied along, defined only where a child is a leaf, and differ between the stage-wise and the fused
+        # build elsewhere (test_cd_gpu.py's _compare_records) -- no walk of the swept tree reads them (REC_LAST_MASK)
+        m = max(s.nt - 1, 0)
+        part = lambda r: (r["srr"][:m, :7], r["srl"][:m, :7], r["srr"][:m, 7] & sr.REC_MASK, r["srl"][:m, 7] & sr.REC_MASK, r["up"], r["perm"])
+        _equal_bytes(part(t), part(tf), what + " swept tree against the fresh context")
+        assert t["m_bits"] == tf["m_bits"] and sr.bits1(t["pad"]) == sr.bits1(tf["pad"]), what
+
+    def ray_queries():
+        want = mi.want_rays(name, f)
+        got = cast(cd)
+        mi.same_rays(got, want, what + " rays")
+        gf = cast(fresh)
+        mi.same_rays(got[:5], gf[:5], what + " rays against the fresh context")
+        assert got[5].n_hits == gf[5].n_hits
+        face, info = cast(cd, any_hit=True)
+        mi.same_any_hit(face, info.n_hits, rays, v, vidx, want, what + " any hit")
+
+    def point_queries():
+        got = cd.closest_points(pts)
+        mi.same_points(got, mi.want_points(name, f), what + " points")
+        got = cd.closest_points(pts, rm)
+        mi.same_points(got, mi.want_points_r(name, f), what + " points with radii")
+        gf = fresh.closest_points(pts, rm)
+        mi.same_points(got[:7], gf[:7], what + " points against the fresh context")
+        assert got[7].n_found == gf[7].n_found
+        face, info = cd.closest_points(pts, rm, any_within=True)
+        mi.same_any_within(face, info.n_found, pts, rm, v, vidx, mi.want_points_r(name, f), what + " any within")
+
+    def box():
+        got = cd.root_box()
+        mi.same_root_box(got, mi.want_root_box(name, f), what + " root box")
+        mi.same_root_box(got, fresh.root_box(), what + " root box against the fresh context")
+
+    return [("proximity", proximity), ("ccd", ccd), ("rays", ray_queries), ("points", point_queries), ("root box", box)]
+
+
+def _new(verts, vidx, mode):
+    cd = mi355cd.CollisionDetector(verts, vidx)
+    if mode != "reference":
+        cd.set_morton_frame(FRAME[mode])
+    return cd
+
+
+def _run(name, schedule):
+    s = mi.seq(name)
+    order = np.random.default_rng(s.seed)
+    used = []
+    with _new(s.frames[0], s.vidx, s.frame_mode) as cd:
+        for f, v in enumerate(s.frames):
+            entry = ENTRIES[(f + s.seed) % len(ENTRIES)] if schedule == "rotate" else schedule
+            if name == "frame_exit" and f == len(s) - 1:                       # back inside for a frame already: after 64 more sorts the first form gets its try
+                for _ in range(70):
+                    cd.build_tree()
+            cd.update_vertices(v)
+            _rebuild(cd, entry, name, f)
+            used.append(entry)
+            if name == "frame_exit":
+                form = cd.debug_get(mi355cd.CD_DBG_GET_SORT_FORM)
+                assert form == (1 if f in mi.FRAME_EXIT_OUT else 0) or (f == len(s) - 2 and form == 1), (f, form)
+            with _new(v, s.vidx, s.frame_mode) as fresh:
+                fresh.build_tree()
+                qs = _queries(cd, fresh, name, f)
+                for k in order.permutation(len(qs)):                           # no query's result depends on which one ran before it
+                    qs[k][1]()
+    if schedule == "rotate" and len(s) >= len(ENTRIES):
+        assert set(used) == set(ENTRIES)
+    assert all(a != b for a, b in zip(used, used[1:])) or schedule != "rotate"
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_jitter_through_one_entry_every_frame(entry):
+    """The same rebuild entry every frame; frame 2 is the dense one (a shard of the first candidate buffers overflows: the passes grow
+    their buffers), the later frames are sparse again and still exact, with CD_OK (same_prox / same_ccd assert the return code)."""
+    assert mi.ccd_shard_load("jitter", mi.JITTER_DENSE_FRAME) > mi.SHARD_FIRST
+    _run("jitter", entry)
+
+
+@pytest.mark.parametrize("name", mi.NAMES)
+def test_every_sequence_through_rotating_entries(name):
+    """Consecutive frames go through different entries; a sequence of six frames or more goes through all six."""
+    _run(name, "rotate")
+
+
+# ---------------------------------------------------------------- between two meshes
+def _order_errors(a, b):
+    """A mesh moved and its tree was not rebuilt: every query between the two, in both roles, returns CD_ERR_ORDER and writes nothing."""
+    lib = a.lib
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)
+    pairs, toi, d = np.full((16, 2), 0xDEADBEEF, dtype=np.uint32), np.full(16, -7.0), np.full(16, -7.0)
+    n, t, info = C.c_uint64(0), C.c_uint64(0), mi355cd.CdCcdInfo()
+    for x, y in ((a, b), (b, a)):
+        assert lib.cd_find_collisions_between(x._ctx, y._ctx, vp(pairs), 16, C.byref(n), C.byref(t)) == mi355cd.CD_ERR_ORDER
+        assert lib.cd_find_proximity_between(x._ctx, y._ctx, mi.BETWEEN_DIST, vp(pairs), vp(d), 16, C.byref(n), C.byref(t)) == mi355cd.CD_ERR_ORDER
+        assert lib.cd_find_ccd_between(x._ctx, None, y._ctx, None, mi.BETWEEN_CCD_DIST, vp(pairs), vp(toi), vp(d), 16, C.byref(n), C.byref(info)) == mi355cd.CD_ERR_ORDER
+    assert (pairs == 0xDEADBEEF).all() and (toi == -7.0).all() and (d == -7.0).all()
+
+
+@pytest.mark.parametrize("schedule", mi.BETWEEN_SCHEDULES)
+def test_between_two_meshes_that_move(schedule):
+    """Context a is one sheet of `slide`, b the other; only a moves, only b moves, or both.  A context that did not move is neither
+    updated nor rebuilt: what a keeps of b from the last CCD call (and b of a) is the previous frame's and must not be used."""
+    va, ia, vb, ib = mi.between_meshes()
+    pos = mi.between_positions(schedule)
+    with mi355cd.CollisionDetector(pos[0][0], ia) as a, mi355cd.CollisionDetector(pos[0][1], ib) as b:
+        for f, (wa, wb, ma, mb) in enumerate(pos):
+            ea, eb = mi.between_x1(schedule, f)
+            if ma:
+                a.update_vertices(wa)
+            if mb:
+                b.update_vertices(wb)
+            if ma or mb:
+                _order_errors(a, b)
+            for cd, moved, e, k in ((a, ma, ea, f), (b, mb, eb, f + 3)):
+                if moved or f == 0:
+                    _enter(cd, ENTRIES[k % len(ENTRIES)], e, mi.BETWEEN_DIST, mi.BETWEEN_CCD_DIST)
+            for x, y, swap in ((a, b, False), (b, a, True)):
+                what = f"{schedule} frame {f}, roles {'(b, a)' if swap else '(a, b)'}"
+                w = mi.want_between(schedule, f, swap)
+                (vx, ex, ix), (vy, ey, iy) = ((wb, eb, ib), (wa, ea, ia)) if swap else ((wa, ea, ia), (wb, eb, ib))
+                mi.same_between_contact(x.find_collisions_between(y, cap=CAP), w["contact"][0], what + " contact")
+                assert x.between_tested == w["contact"][1], (what, x.between_tested, w["contact"][1])
+                mi.same_between_prox(x.find_proximity_between(y, mi.BETWEEN_DIST, cap=CAP), w["prox"], what + " proximity")
+                mi.same_between_ccd(x.find_ccd_between(y, mi.BETWEEN_CCD_DIST, ex, ey, cap=CAP), w["ccd"], what + " ccd")
+                t = mi.read_swept(x, y)                                        # what x holds of y after the CCD call
+                mi.same_swept(t, vy, ey, iy, sr.m_bits_between(vx, ex, ix, vy, ey, iy), mi.BETWEEN_CCD_DIST, what + " swept tree",
+                              a=(vx, ex, ix, x.export_keys()[1]), n_candidates=x.ccd_info.n_candidates)

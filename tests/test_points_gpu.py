@@ -319,7 +319,9 @@ def test_order_and_argument_errors_write_nothing():
         rc, o = call(pts)
         assert rc == mi355cd.CD_ERR_ORDER and untouched(o)                 # after update_vertices without a rebuild
         cd.build_tree()
-        assert call(pts)[0] == mi355cd.CD_OK
+        rc, o = call(pts)
+        assert rc == mi355cd.CD_OK
+        _same(o, ptr.closest_points_ref(np.asarray(v) + 0.001, i, ids, pts[:, :3]), "after update_vertices and a rebuild")   # the moved mesh's answers, not the old tree's
 
 
 def test_buffers_grow_from_one_point_to_a_million_and_back():
