@@ -107,10 +107,18 @@ class RayTracer:
         if rc:
             raise RtError("rt_set_mode", rc)
 
-    # ---- device-resident animation state (sphere.cuh:50-118)
     def _chk(self, fn, rc):
         if rc:
             raise RtError(fn, rc)
+
+    def set_spheres(self, spheres: np.ndarray):
+        """Re-upload the spheres (same count); a refused upload (an idx outside [0, n)) leaves the old ones in place."""
+        s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
+        assert s.shape[0] == self.n
+        self._chk("rt_set_spheres", self.lib.rt_set_spheres(self._ctx, _ptr(s)))
+        self.spheres = s
+
+    # ---- device-resident animation state (sphere.cuh:50-118)
 
     def anim_init(self):
         self._chk("rt_anim_init", self.lib.rt_anim_init(self._ctx))
