@@ -177,7 +177,17 @@ int cd_self_collide(cd_ctx *ctx, uint32_t *pairs, uint64_t cap_pairs, uint64_t *
 
 /* main.cu:149-154: the pair list of the LAST traversal, sorted ascending by (smaller ID, larger ID) on the device --
  * a deterministic order for diffing (the reference prints in atomicAdd arrival order).  Needs the last
- * cd_find_collisions / cd_self_collide to have had cap_pairs >= its n_pairs (else CD_OVERFLOW). */
+ * cd_find_collisions / cd_self_collide to have had cap_pairs >= its n_pairs (else CD_OVERFLOW).
+ * "The last traversal" is the last call that left ONE pair list on the device: cd_find_collisions, cd_self_collide (stream or graph
+ * replay, into any buffer), cd_brute_force, cd_find_collisions_queries (its list: external queries against the local tree).  Calls that
+ * run no such traversal leave the list as it was: cd_update_vertices followed by cd_build_tree (between the two there is no tree:
+ * CD_ERR_ORDER) returns the previous step's list, and so it is after the proximity, CCD, between-mesh, ray and point queries.
+ * Both calls need the tree of the current vertices to be there (CD_ERR_ORDER otherwise) -- also after cd_brute_force, which itself
+ * needs none: build the tree first (cd_build_tree) when its list is to be post-processed.
+ * cd_multi_step leaves two lists (local, cross) and no single one: after it both calls return CD_OVERFLOW when the step found any
+ * pair, and n = 0 with CD_OK when it found none, until the next traversal named above.  A call that returns CD_OVERFLOW for a
+ * truncated or absent list, or CD_ERR_ORDER, writes nothing -- neither the buffer nor the count; cap below the count: CD_OVERFLOW, the count, and
+ * the first cap entries of the sorted result.  Both calls leave cd_stats and the list itself untouched and may be repeated. */
 int cd_sorted_pairs(cd_ctx *ctx, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs);
 /* main.cu:33-45 makeAndPrintSet: the sorted set of distinct triangle IDs that occur in the pair list,
  * built on the device (sort + unique).  *n = number of distinct IDs (may exceed cap -> CD_OVERFLOW). */
