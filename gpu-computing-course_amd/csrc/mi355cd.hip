@@ -23,6 +23,7 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -58,6 +59,143 @@ struct TravBuf {
     // the report of the pass being enqueued, decided BEFORE its kernels are (run_traversal, prepare_report): the exact kernel posts the first pairs into pinned host memory itself
     uint32_t *post_dst = nullptr; uint64_t post_n = 0;                     // where to (the caller's pinned buffer, or the staging area behind the report), how many at most
     bool prepared = false; unsigned long long prep_seq = 0; uint32_t *prep_area = nullptr; bool posted = false;   // the polled completion's sequence number and the scan's area of that report; the pass's k_exact did post
+};
+
+// ---- the buffers of the queries behind the tree (proximity, CCD, between-mesh, rays, closest points) --------------------------------
+// Every record allocates a group of buffers as a whole: the group's capacity (for the state words: the mirror's pointer) is set only
+// after every allocation in it has succeeded, and a group that failed is freed again -- a later call finds it absent, never half there.
+template <typename T> void dev_alloc(hipError_t &e, T *&p, size_t bytes)      // e carries the first error: nothing is tried after it
+{
+    if (e == hipSuccess && (e = hipMalloc(reinterpret_cast<void **>(&p), bytes)) != hipSuccess) p = nullptr;
+}
+template <typename T> void dev_free(T *&p) { hipFree(p); p = nullptr; }
+
+// a query's device counters and their pinned mirror
+template <typename State>
+struct StateWords {
+    State *d = nullptr, *h = nullptr;
+    int ensure()
+    {
+        if (h) return CD_OK;
+        hipError_t e = hipSuccess;
+        State *mirror = nullptr;
+        dev_alloc(e, d, sizeof(State));
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&mirror), sizeof(State), hipHostMallocDefault);
+        if (e != hipSuccess) { dev_free(d); return -(int)e; }
+        h = mirror;
+        return CD_OK;
+    }
+    void release() { dev_free(d); if (h) hipHostFree(h); h = nullptr; }
+};
+
+// What a pair query (self-proximity, self-CCD, between two meshes) owns: counters, NSHARD shards of candidates, the result arrays
+template <typename State>
+struct PairBuf {
+    static constexpr bool HAS_TOI = std::is_same<State, CcdState>::value;   // (proximity reports no times; between-mesh always has the array)
+    StateWords<State> state;
+    uint2 *d_cand = nullptr; uint64_t shard_cap = 0;                        // candidates a shard
+    uint32_t *d_pairs = nullptr; double *d_toi = nullptr, *d_dists = nullptr; uint64_t pairs_cap = 0;
+
+    int alloc_cand(uint64_t per)
+    {
+        hipError_t e = hipSuccess;
+        dev_alloc(e, d_cand, sizeof(uint2) * per * NSHARD);
+        shard_cap = e == hipSuccess ? per : 0;
+        return e == hipSuccess ? CD_OK : -(int)e;
+    }
+    void release_results() { dev_free(d_pairs); dev_free(d_toi); dev_free(d_dists); pairs_cap = 0; }
+    void release() { state.release(); dev_free(d_cand); shard_cap = 0; release_results(); }
+    // nt: the triangles whose candidates the shards take (16 a triangle to start with; grown on overflow)
+    int ensure(uint32_t nt, uint64_t cap_pairs)
+    {
+        int rc = state.ensure();
+        if (!rc && !shard_cap) rc = alloc_cand(std::max<uint64_t>(4096, (16ull * nt + NSHARD - 1) / NSHARD));
+        const uint64_t want = cap_pairs > 0 ? cap_pairs : 1;
+        if (rc || want <= pairs_cap) return rc;
+        release_results();
+        hipError_t e = hipSuccess;
+        dev_alloc(e, d_pairs, sizeof(uint32_t) * 2 * want);
+        if (HAS_TOI) dev_alloc(e, d_toi, sizeof(double) * want);
+        dev_alloc(e, d_dists, sizeof(double) * want);
+        if (e != hipSuccess) { release_results(); return -(int)e; }
+        pairs_cap = want;
+        return CD_OK;
+    }
+    // after the synchronisation: true = a shard overflowed and the buffer has been grown (enqueue again); false = done, or rc says why not
+    bool overflowed(int &rc)
+    {
+        uint64_t mx = 0;
+        for (int i = 0; i < NSHARD; ++i) mx = std::max<uint64_t>(mx, state.h->shard[i * PROX_SHARD_STRIDE]);
+        rc = CD_OK;
+        if (mx <= shard_cap) return false;
+        dev_free(d_cand);
+        rc = alloc_cand(mx + mx / 4 + 1024);
+        return rc == CD_OK;
+    }
+    int results(uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs) const
+    {
+        const uint64_t np = state.h->n_pairs, take = std::min(np, cap_pairs);
+        if (take) {
+            HIPCHK(hipMemcpy(pairs, d_pairs, sizeof(uint32_t) * 2 * take, hipMemcpyDeviceToHost));
+            if (toi) HIPCHK(hipMemcpy(toi, d_toi, sizeof(double) * take, hipMemcpyDeviceToHost));
+            if (dists) HIPCHK(hipMemcpy(dists, d_dists, sizeof(double) * take, hipMemcpyDeviceToHost));
+        }
+        if (n_pairs) *n_pairs = np;
+        return np > cap_pairs ? CD_OVERFLOW : CD_OK;
+    }
+    void fill_info(cd_ccd_info *info) const                                 // (CcdState only)
+    {
+        if (!info) return;
+        uint64_t cand = 0;
+        for (int i = 0; i < NSHARD; ++i) cand += state.h->shard[i * PROX_SHARD_STRIDE];
+        info->n_candidates = cand; info->n_tested = state.h->n_tested; info->n_evals = state.h->n_evals; info->n_unresolved = state.h->n_unresolved;
+    }
+};
+
+// The swept tree of a CCD pass (cd_ccd.h) over `cap` leaves at most, and what cd_debug_swept reports of the last pass through it (host
+// words only: nothing is enqueued for them)
+struct SweptBuf {
+    NodeRec32 *d_recs = nullptr; int32_t *d_up = nullptr; uint32_t *d_arrive = nullptr; uint64_t cap = 0;
+    struct Seen { bool ran = false; uint32_t n = 0, m_bits = 0; double dist = 0.0; } seen;
+    void release() { dev_free(d_recs); dev_free(d_up); dev_free(d_arrive); cap = 0; }
+    int ensure(uint32_t n)
+    {
+        if (n <= cap) return CD_OK;
+        release();
+        hipError_t e = hipSuccess;
+        dev_alloc(e, d_recs, sizeof(NodeRec32) * (size_t)n);
+        dev_alloc(e, d_up, sizeof(int32_t) * 2 * (size_t)n);
+        dev_alloc(e, d_arrive, sizeof(uint32_t) * (size_t)n);
+        if (e != hipSuccess) { release(); return -(int)e; }
+        cap = n;
+        return CD_OK;
+    }
+};
+
+// one device array of `cap` items, grown to the largest count seen (the old contents are not kept)
+template <typename T>
+struct DevArray {
+    T *d = nullptr; uint64_t cap = 0;
+    void release() { dev_free(d); cap = 0; }
+    int ensure(uint64_t n, uint64_t elems_per_item)
+    {
+        if (n <= cap) return CD_OK;
+        release();
+        hipError_t e = hipSuccess;
+        dev_alloc(e, d, sizeof(T) * elems_per_item * n);
+        if (e != hipSuccess) return -(int)e;
+        cap = n;
+        return CD_OK;
+    }
+};
+
+// What a per-item query (rays, closest points) owns: counters and ONE block of the items' inputs and results, which the entry point carves
+template <typename State>
+struct ItemBuf {
+    StateWords<State> state;
+    DevArray<char> block;
+    void release() { state.release(); block.release(); }
+    int ensure(uint64_t n, uint64_t bytes_per_item) { const int rc = state.ensure(); return rc ? rc : block.ensure(n, bytes_per_item); }
 };
 
 struct cd_multi;
@@ -168,34 +306,23 @@ struct cd_ctx {
     double root_box_host[6] = {};           // AABB of the whole tree, fetched together with other read-backs
     bool root_box_valid = false;
     // self-proximity (cd_find_proximity, cd_proximity.h): buffers of its own -- nothing the collision path keeps is touched
-    ProxState *d_px_state = nullptr; ProxState *h_px_state = nullptr;
-    uint2 *d_px_cand = nullptr; uint64_t px_shard_cap = 0;
-    uint32_t *d_px_pairs = nullptr; double *d_px_dists = nullptr; uint64_t px_pairs_cap = 0;
+    PairBuf<ProxState> prox;
     // continuous collision queries (cd_find_ccd, cd_ccd.h): buffers of their own, allocated on first use
-    CcdState *d_cc_state = nullptr; CcdState *h_cc_state = nullptr;
-    uint2 *d_cc_cand = nullptr; uint64_t cc_shard_cap = 0;
-    uint32_t *d_cc_pairs = nullptr; double *d_cc_toi = nullptr, *d_cc_dists = nullptr; uint64_t cc_pairs_cap = 0;
-    double *d_cc_x1 = nullptr; NodeRec32 *d_cc_recs = nullptr; int32_t *d_cc_up = nullptr; uint32_t *d_cc_arrive = nullptr;
+    PairBuf<CcdState> ccd;
+    DevArray<double> ccd_x1;                // the end positions, nv vertices
     // queries between two meshes (cd_find_*_between, cd_between.h) with this context as a: buffers of their own, allocated on first use and
-    // grown to the other context's sizes (x1 of b, b's swept records, parent links, arrival counters)
-    CcdState *d_bw_state = nullptr; CcdState *h_bw_state = nullptr;
-    uint2 *d_bw_cand = nullptr; uint64_t bw_shard_cap = 0;
-    uint32_t *d_bw_pairs = nullptr; double *d_bw_toi = nullptr, *d_bw_dists = nullptr; uint64_t bw_pairs_cap = 0;
-    double *d_bw_x1a = nullptr; double *d_bw_x1b = nullptr; uint64_t bw_x1b_cap = 0;
-    NodeRec32 *d_bw_recs = nullptr; int32_t *d_bw_up = nullptr; uint32_t *d_bw_arrive = nullptr; uint64_t bw_rec_cap = 0;
+    // grown to the other context's sizes (x1 of b, b's swept tree)
+    PairBuf<CcdState> bw;
+    DevArray<double> bw_x1a, bw_x1b;
+    // the swept trees of the CCD passes: [0] this mesh's own (cd_find_ccd / cd_self_ccd), [1] b's, of cd_find_ccd_between with this context as a
+    SweptBuf swept[2];
     int device = 0;                         // the HIP device ordinal current at cd_create (the between queries need both contexts on one device)
-    // what cd_debug_swept reports of the last CCD pass (host words only: nothing is enqueued for them)
-    struct SweptSeen { bool ran = false; uint32_t n = 0, m_bits = 0; double dist = 0.0; };
-    SweptSeen cc_seen;                      // cd_find_ccd / cd_self_ccd: the swept tree in d_cc_recs / d_cc_up
-    SweptSeen bw_seen;                      // cd_find_ccd_between with this context as a: b's swept tree in d_bw_recs / d_bw_up
     // ray queries (cd_cast_rays, cd_rays.h): buffers of their own, allocated on first use and grown to the largest ray count seen.
-    // d_ry_block: rays [7 n] | t [n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | side [n] (u8)
-    RayState *d_ry_state = nullptr; RayState *h_ry_state = nullptr;
-    char *d_ry_block = nullptr; uint64_t ry_cap = 0;
+    // rays.block: rays [7 n] | t [n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | side [n] (u8)
+    ItemBuf<RayState> rays;
     // closest-point queries (cd_closest_points, cd_points.h): buffers of their own, as the rays'.
-    // d_pt_block: points [4 n] | dist [n] | closest [3 n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | feature [n] | side [n] (u8)
-    PointState *d_pt_state = nullptr; PointState *h_pt_state = nullptr;
-    char *d_pt_block = nullptr; uint64_t pt_cap = 0;
+    // points.block: points [4 n] | dist [n] | closest [3 n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | feature [n] | side [n] (u8)
+    ItemBuf<PointState> points;
 };
 
 namespace {
@@ -222,18 +349,9 @@ void free_all(cd_ctx *c)
     }
     for (int i = 0; i < 2; ++i) { hipFree(c->pp_keys[i]); hipFree(c->pp_vals[i]); }
     hipFree(c->pp_flags); hipFree(c->pp_os);
-    hipFree(c->d_px_state); hipFree(c->d_px_cand); hipFree(c->d_px_pairs); hipFree(c->d_px_dists);
-    if (c->h_px_state) hipHostFree(c->h_px_state);
-    hipFree(c->d_cc_state); hipFree(c->d_cc_cand); hipFree(c->d_cc_pairs); hipFree(c->d_cc_toi); hipFree(c->d_cc_dists);
-    hipFree(c->d_cc_x1); hipFree(c->d_cc_recs); hipFree(c->d_cc_up); hipFree(c->d_cc_arrive);
-    if (c->h_cc_state) hipHostFree(c->h_cc_state);
-    hipFree(c->d_bw_state); hipFree(c->d_bw_cand); hipFree(c->d_bw_pairs); hipFree(c->d_bw_toi); hipFree(c->d_bw_dists);
-    hipFree(c->d_bw_x1a); hipFree(c->d_bw_x1b); hipFree(c->d_bw_recs); hipFree(c->d_bw_up); hipFree(c->d_bw_arrive);
-    if (c->h_bw_state) hipHostFree(c->h_bw_state);
-    hipFree(c->d_ry_state); hipFree(c->d_ry_block);
-    if (c->h_ry_state) hipHostFree(c->h_ry_state);
-    hipFree(c->d_pt_state); hipFree(c->d_pt_block);
-    if (c->h_pt_state) hipHostFree(c->h_pt_state);
+    c->prox.release(); c->ccd.release(); c->bw.release(); c->ccd_x1.release(); c->bw_x1a.release(); c->bw_x1b.release();
+    for (SweptBuf &sw : c->swept) sw.release();
+    c->rays.release(); c->points.release();
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -241,6 +359,36 @@ void free_all(cd_ctx *c)
 }
 
 inline uint32_t cdiv(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
+inline uint32_t strided_grid(uint64_t n, uint32_t threads) { return std::min(cdiv(n, threads), 4096u); }   // the grid-stride kernels on explicit operands
+inline uint32_t shard_blocks(uint32_t n) { return std::max(1u, std::min(64u, cdiv(n, 4096))); }             // exact stage of the pair queries: workgroups per shard
+inline bool have_device() { int ndev = 0; return hipGetDeviceCount(&ndev) == hipSuccess && ndev != 0; }
+
+// The device buffers of ONE call on explicit operands (no context, null stream): freed when the call returns.  e is the first HIP
+// error; every operation after it does nothing and hands out nullptr, so the caller launches only while e == hipSuccess.
+struct OneShot {
+    hipError_t e = hipSuccess;
+    void *owned[8] = {}; int n_owned = 0;
+    OneShot() = default; OneShot(const OneShot &) = delete;
+    ~OneShot() { for (int i = 0; i < n_owned; ++i) hipFree(owned[i]); }
+    template <typename T> T *out(uint64_t count)                             // an output of `count` elements
+    {
+        void *p = nullptr;
+        if (e == hipSuccess && n_owned == 8) e = hipErrorOutOfMemory;
+        if (e == hipSuccess && (e = hipMalloc(&p, sizeof(T) * count)) == hipSuccess) owned[n_owned++] = p;
+        return e == hipSuccess ? static_cast<T *>(p) : nullptr;
+    }
+    template <typename T> T *in(const T *host, uint64_t count)              // a host array, uploaded
+    {
+        T *p = out<T>(count);
+        if (e == hipSuccess) e = hipMemcpy(p, host, sizeof(T) * count, hipMemcpyHostToDevice);
+        return p;
+    }
+    template <typename T> void back(T *host, const T *dev, uint64_t count)  // an output copied back, if the caller asked for it
+    {
+        if (host && e == hipSuccess) e = hipMemcpy(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost);
+    }
+    int rc() const { return e == hipSuccess ? CD_OK : -(int)e; }
+};
 
 // pair buffers handed out by cd_alloc_host_pairs: pinned host memory the report kernel writes STRAIGHT into (no staging copy on the host)
 // (id: a buffer's serial number -- an address the allocator hands out again is a NEW buffer, with pages the device has never written)
@@ -1112,8 +1260,7 @@ int cd_create(cd_ctx **out, const double *verts_xyz, uint32_t nv, const uint32_t
 {
     if (!out || !verts_xyz || !vidx3 || nv == 0 || nt == 0) return CD_ERR_ARG;
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
+    if (!have_device()) return CD_ERR_NO_DEVICE;
     for (uint64_t k = 0; k < 3ull * nt; ++k) if (vidx3[k] >= nv) return CD_ERR_INDEX;
     bool all_ref = true;                                // is every vertex used by some triangle?  (then the box of the triangles is the box of the vertices: cd_multi.h)
     { std::vector<uint8_t> used(nv, 0);
@@ -1627,13 +1774,14 @@ int cd_debug_records(cd_ctx *c, void *recs, void *qboxes, int32_t *root)
 int cd_debug_swept(cd_ctx *c, int between, void *recs, int32_t *up, uint32_t *m_bits, float *pad, uint32_t *n_leaves)
 {
     if (!c || (between != 0 && between != 1)) return CD_ERR_ARG;
-    const cd_ctx::SweptSeen &seen = between ? c->bw_seen : c->cc_seen;
+    const SweptBuf &sw = c->swept[between];
+    const SweptBuf::Seen &seen = sw.seen;
     if (!seen.ran) return CD_ERR_ORDER;
     HIPCHK(hipStreamSynchronize(c->stream));
     const size_t n = seen.n;
     if (n >= 2) {                                                            // (one leaf: no records, no links)
-        if (recs) HIPCHK(hipMemcpy(recs, between ? c->d_bw_recs : c->d_cc_recs, sizeof(NodeRec32) * n, hipMemcpyDeviceToHost));
-        if (up) HIPCHK(hipMemcpy(up, between ? c->d_bw_up : c->d_cc_up, sizeof(int32_t) * (2 * n - 1), hipMemcpyDeviceToHost));
+        if (recs) HIPCHK(hipMemcpy(recs, sw.d_recs, sizeof(NodeRec32) * n, hipMemcpyDeviceToHost));
+        if (up) HIPCHK(hipMemcpy(up, sw.d_up, sizeof(int32_t) * (2 * n - 1), hipMemcpyDeviceToHost));
     }
     if (m_bits) *m_bits = seen.m_bits;
     if (pad) {                                                               // ccd_pad's host twin: the same FP64 sum, rounded up to fp32
@@ -1650,25 +1798,18 @@ int cd_debug_swept(cd_ctx *c, int between, void *recs, int32_t *up, uint32_t *m_
 // morton3D / expand64Bits themselves, on caller-supplied inputs; no context (one-shot device buffers on the null stream)
 static int morton_batch(const void *in, size_t in_bytes, uint64_t n, const double frame[FRAME_WORDS], uint64_t *out)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
-    void *d_in = nullptr; uint64_t *d_out = nullptr; double *d_frame = nullptr;
-    int rc = CD_OK;
-    hipError_t e = hipMalloc(&d_in, in_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(uint64_t) * n);
-    if (e == hipSuccess && frame) e = hipMalloc(&d_frame, sizeof(double) * FRAME_WORDS);
-    if (e == hipSuccess) e = hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && frame) e = hipMemcpy(d_frame, frame, sizeof(double) * FRAME_WORDS, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const uint32_t blocks = cdiv(n, 256) < 4096u ? cdiv(n, 256) : 4096u;
-        if (frame) k_morton_points<<<blocks, 256>>>(static_cast<const double *>(d_in), n, d_frame, d_out);
-        else k_expand_values<<<blocks, 256>>>(static_cast<const uint64_t *>(d_in), n, d_out);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(uint64_t) * n, hipMemcpyDeviceToHost);
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const char *d_in = dev.in(static_cast<const char *>(in), in_bytes);
+    uint64_t *d_out = dev.out<uint64_t>(n);
+    const double *d_frame = frame ? dev.in(frame, FRAME_WORDS) : nullptr;
+    if (dev.e == hipSuccess) {
+        if (frame) k_morton_points<<<strided_grid(n, 256), 256>>>(reinterpret_cast<const double *>(d_in), n, d_frame, d_out);
+        else k_expand_values<<<strided_grid(n, 256), 256>>>(reinterpret_cast<const uint64_t *>(d_in), n, d_out);
+        dev.e = hipGetLastError();
     }
-    if (e != hipSuccess) rc = -(int)e;
-    hipFree(d_in); hipFree(d_out); hipFree(d_frame);
-    return rc;
+    dev.back(out, d_out, n);
+    return dev.rc();
 }
 int cd_morton3d_points(const double *xyz, uint64_t n, const double offset[3], const double span[3], uint64_t *keys)
 {
@@ -1700,50 +1841,40 @@ int cd_box_pairs(const double *a, const double *b, uint64_t n, uint8_t *overlap,
 {
     if (!a || !b || (!overlap && !merged)) return CD_ERR_ARG;
     if (n == 0) return CD_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
-    double *d_a = nullptr, *d_b = nullptr, *d_m = nullptr; uint8_t *d_o = nullptr;
-    const size_t bytes = sizeof(double) * 6 * n;
-    hipError_t e = hipMalloc(&d_a, bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_b, bytes);
-    if (e == hipSuccess && overlap) e = hipMalloc(&d_o, n);
-    if (e == hipSuccess && merged) e = hipMalloc(&d_m, bytes);
-    if (e == hipSuccess) e = hipMemcpy(d_a, a, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        k_box_pairs<<<cdiv(n, 256) < 4096u ? cdiv(n, 256) : 4096u, 256>>>(d_a, d_b, n, d_o, d_m);
-        e = hipGetLastError();
-        if (e == hipSuccess && overlap) e = hipMemcpy(overlap, d_o, n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && merged) e = hipMemcpy(merged, d_m, bytes, hipMemcpyDeviceToHost);
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_a = dev.in(a, 6 * n), *d_b = dev.in(b, 6 * n);
+    uint8_t *d_o = overlap ? dev.out<uint8_t>(n) : nullptr;
+    double *d_m = merged ? dev.out<double>(6 * n) : nullptr;
+    if (dev.e == hipSuccess) {
+        k_box_pairs<<<strided_grid(n, 256), 256>>>(d_a, d_b, n, d_o, d_m);
+        dev.e = hipGetLastError();
     }
-    hipFree(d_a); hipFree(d_b); hipFree(d_o); hipFree(d_m);
-    return e == hipSuccess ? CD_OK : -(int)e;
+    dev.back(overlap, d_o, n);
+    dev.back(merged, d_m, 6 * n);
+    return dev.rc();
 }
 int cd_tri_contact_points(const double *tri, uint64_t n, uint8_t *out)
 {
     if (!tri || !out) return CD_ERR_ARG;
     if (n == 0) return CD_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
-    double *d_t = nullptr; uint8_t *d_o = nullptr;
-    hipError_t e = hipMalloc(&d_t, sizeof(double) * 18 * n);
-    if (e == hipSuccess) e = hipMalloc(&d_o, n);
-    if (e == hipSuccess) e = hipMemcpy(d_t, tri, sizeof(double) * 18 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        k_tri_contact_points<<<cdiv(n, 256) < 4096u ? cdiv(n, 256) : 4096u, 256>>>(d_t, n, d_o);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(out, d_o, n, hipMemcpyDeviceToHost);
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_t = dev.in(tri, 18 * n);
+    uint8_t *d_o = dev.out<uint8_t>(n);
+    if (dev.e == hipSuccess) {
+        k_tri_contact_points<<<strided_grid(n, 256), 256>>>(d_t, n, d_o);
+        dev.e = hipGetLastError();
     }
-    hipFree(d_t); hipFree(d_o);
-    return e == hipSuccess ? CD_OK : -(int)e;
+    dev.back(out, d_o, n);
+    return dev.rc();
 }
 
 int cd_alloc_host_pairs(uint64_t cap_pairs, uint32_t **pairs)
 {
     if (!pairs || cap_pairs == 0) return CD_ERR_ARG;
     *pairs = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
+    if (!have_device()) return CD_ERR_NO_DEVICE;
     void *p = nullptr;
     // (coherent = fine-grained: the memory the HSA memory model defines system-scope release / acquire between device and host on)
     HIPCHK(hipHostMalloc(&p, sizeof(uint32_t) * 2 * cap_pairs + 16, hipHostMallocCoherent));     // +16: the report kernel moves pairs as 16-byte quads
@@ -1880,65 +2011,25 @@ int cd_find_collisions_queries(cd_ctx *c, const void *d_queries, uint64_t nq, ui
 // ---- self-proximity (cd_proximity.h) ------------------------------------------------------------------------------------------------
 // Own buffers (state, candidates, pairs, distances): the collision path's counters, pair list, statistics and captured step stay as they were.
 static bool prox_dist_ok(double dist) { return dist >= 0.0 && dist <= 1.7976931348623157e308; }      // (NaN fails both)
-static int prox_buffers(cd_ctx *c, uint64_t cap_pairs)
-{
-    if (!c->d_px_state) {
-        HIPCHK(hipMalloc(&c->d_px_state, sizeof(ProxState)));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_px_state), sizeof(ProxState), hipHostMallocDefault));
-    }
-    if (!c->d_px_cand) {                                                    // 16 candidates a triangle to start with; grown on overflow
-        const uint64_t per = std::max<uint64_t>(4096, (16ull * c->nt + NSHARD - 1) / NSHARD);
-        HIPCHK(hipMalloc(&c->d_px_cand, sizeof(uint2) * per * NSHARD));
-        c->px_shard_cap = per;
-    }
-    const uint64_t want = cap_pairs > 0 ? cap_pairs : 1;
-    if (want > c->px_pairs_cap) {
-        hipFree(c->d_px_pairs); hipFree(c->d_px_dists); c->d_px_pairs = nullptr; c->d_px_dists = nullptr; c->px_pairs_cap = 0;
-        HIPCHK(hipMalloc(&c->d_px_pairs, sizeof(uint32_t) * 2 * want));
-        HIPCHK(hipMalloc(&c->d_px_dists, sizeof(double) * want));
-        c->px_pairs_cap = want;
-    }
-    return CD_OK;
-}
 // the two kernels of one pass and the read-back of the counters (no synchronisation)
 static int prox_enqueue(cd_ctx *c, double dist, uint64_t cap_pairs)
 {
     hipStream_t s = c->stream;
     const uint32_t n = c->nt;
-    HIPCHK(hipMemsetAsync(c->d_px_state, 0, sizeof(ProxState), s));
+    PairBuf<ProxState> &q = c->prox;
+    HIPCHK(hipMemsetAsync(q.state.d, 0, sizeof(ProxState), s));
     k_prox_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(c->d_recs32, c->d_leaf, c->d_verts, c->d_boxes, (int)n, dist,
-                                                                             c->d_os_ticket + 8, c->d_px_state, c->d_px_cand, c->px_shard_cap);
-    const uint32_t xb = std::max<uint32_t>(1u, std::min<uint32_t>(64u, cdiv(n, 4096)));   // workgroups per shard
-    k_prox_exact<<<dim3(xb, NSHARD), PROX_EXACT_THREADS, 0, s>>>(c->d_px_cand, c->px_shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, dist,
-                                                                 c->d_px_state, c->d_px_pairs, c->d_px_dists, cap_pairs);
+                                                                             c->d_os_ticket + 8, q.state.d, q.d_cand, q.shard_cap);
+    k_prox_exact<<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, dist,
+                                                                              q.state.d, q.d_pairs, q.d_dists, cap_pairs);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_px_state, c->d_px_state, sizeof(ProxState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(q.state.h, q.state.d, sizeof(ProxState), hipMemcpyDeviceToHost, s));
     return CD_OK;
-}
-// after the synchronisation: 1 = a shard overflowed (the buffer has been grown: enqueue again), 0 = done
-static int prox_overflowed(cd_ctx *c, int &rc)
-{
-    uint64_t mx = 0;
-    for (int i = 0; i < NSHARD; ++i) mx = std::max<uint64_t>(mx, c->h_px_state->shard[i * PROX_SHARD_STRIDE]);
-    rc = CD_OK;
-    if (mx <= c->px_shard_cap) return 0;
-    hipFree(c->d_px_cand); c->d_px_cand = nullptr;
-    const uint64_t per = mx + mx / 4 + 1024;
-    const hipError_t e = hipMalloc(&c->d_px_cand, sizeof(uint2) * per * NSHARD);
-    if (e != hipSuccess) { c->px_shard_cap = 0; rc = -(int)e; return 0; }
-    c->px_shard_cap = per;
-    return 1;
 }
 static int prox_results(cd_ctx *c, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
 {
-    const uint64_t np = c->h_px_state->n_pairs, take = std::min(np, cap_pairs);
-    if (take) {
-        HIPCHK(hipMemcpy(pairs, c->d_px_pairs, sizeof(uint32_t) * 2 * take, hipMemcpyDeviceToHost));
-        if (dists) HIPCHK(hipMemcpy(dists, c->d_px_dists, sizeof(double) * take, hipMemcpyDeviceToHost));
-    }
-    if (n_pairs) *n_pairs = np;
-    if (n_tested) *n_tested = c->h_px_state->n_tested;
-    return np > cap_pairs ? CD_OVERFLOW : CD_OK;
+    if (n_tested) *n_tested = c->prox.state.h->n_tested;
+    return c->prox.results(pairs, nullptr, dists, cap_pairs, n_pairs);
 }
 static int prox_pass(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
 {
@@ -1946,7 +2037,7 @@ static int prox_pass(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uin
         int rc = prox_enqueue(c, dist, cap_pairs);
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (!prox_overflowed(c, rc)) { if (rc) return rc; break; }
+        if (!c->prox.overflowed(rc)) { if (rc) return rc; break; }
     }
     return prox_results(c, pairs, dists, cap_pairs, n_pairs, n_tested);
 }
@@ -1960,19 +2051,19 @@ int cd_find_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, ui
     int rc = prox_args(c, dist, pairs, cap_pairs);
     if (rc) return rc;
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
-    if ((rc = prox_buffers(c, cap_pairs))) return rc;
+    if ((rc = c->prox.ensure(c->nt, cap_pairs))) return rc;
     return prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
 }
 int cd_self_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
 {
     int rc = prox_args(c, dist, pairs, cap_pairs);
     if (rc) return rc;
-    if ((rc = prox_buffers(c, cap_pairs))) return rc;
+    if ((rc = c->prox.ensure(c->nt, cap_pairs))) return rc;
     sort_retry_tick(c);
     const cd_stats keep = c->stats;                                        // (the build inside does not count as a stage of the collision path)
     rc = fused_step(c, [&]() -> int { const int re = prox_enqueue(c, dist, cap_pairs); return re ? re : sync_with_flags(c); });   // the proximity pass behind the tree: one synchronisation
     if (!rc) {
-        if (prox_overflowed(c, rc)) rc = prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
+        if (c->prox.overflowed(rc)) rc = prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
         else if (!rc) rc = prox_results(c, pairs, dists, cap_pairs, n_pairs, n_tested);
     }
     c->stats = keep;
@@ -1982,21 +2073,17 @@ int cd_tri_distance_points(const double *tri, uint64_t n, double *dist)
 {
     if (!tri || !dist) return CD_ERR_ARG;
     if (n == 0) return CD_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
-    double *d_t = nullptr, *d_o = nullptr;
-    hipError_t e = hipMalloc(&d_t, sizeof(double) * 18 * n);
-    if (e == hipSuccess) e = hipMalloc(&d_o, sizeof(double) * n);
-    if (e == hipSuccess) e = hipMemcpy(d_t, tri, sizeof(double) * 18 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        k_tri_distance_points<<<cdiv(n, 256) < 4096u ? cdiv(n, 256) : 4096u, 256>>>(d_t, n, d_o);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(dist, d_o, sizeof(double) * n, hipMemcpyDeviceToHost);
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_t = dev.in(tri, 18 * n);
+    double *d_o = dev.out<double>(n);
+    if (dev.e == hipSuccess) {
+        k_tri_distance_points<<<strided_grid(n, 256), 256>>>(d_t, n, d_o);
+        dev.e = hipGetLastError();
     }
-    hipFree(d_t); hipFree(d_o);
-    return e == hipSuccess ? CD_OK : -(int)e;
+    dev.back(dist, d_o, n);
+    return dev.rc();
 }
-
 
 // ---- continuous collision queries (cd_ccd.h) ------------------------------------------------------------------------------------
 // Own buffers (x1, swept records, parent links, arrival counters, state, candidates, pairs, times, distances): the context's vertices,
@@ -2004,96 +2091,54 @@ int cd_tri_distance_points(const double *tri, uint64_t n, double *dist)
 static bool ccd_dist_ok(double dist) { return dist > 0.0 && dist <= 1.7976931348623157e308; }       // (NaN fails both)
 static int ccd_buffers(cd_ctx *c, uint64_t cap_pairs)
 {
-    if (!c->d_cc_state) {
-        HIPCHK(hipMalloc(&c->d_cc_state, sizeof(CcdState)));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_cc_state), sizeof(CcdState), hipHostMallocDefault));
-    }
-    if (!c->d_cc_x1) {
-        HIPCHK(hipMalloc(&c->d_cc_x1, sizeof(double) * 3 * (size_t)std::max<uint32_t>(c->nv, 1u)));
-        HIPCHK(hipMalloc(&c->d_cc_recs, sizeof(NodeRec32) * (size_t)std::max<uint32_t>(c->nt, 1u)));
-        HIPCHK(hipMalloc(&c->d_cc_up, sizeof(int32_t) * 2 * (size_t)std::max<uint32_t>(c->nt, 1u)));
-        HIPCHK(hipMalloc(&c->d_cc_arrive, sizeof(uint32_t) * (size_t)std::max<uint32_t>(c->nt, 1u)));
-    }
-    if (!c->d_cc_cand) {                                                    // 16 candidates a triangle to start with; grown on overflow
-        const uint64_t per = std::max<uint64_t>(4096, (16ull * c->nt + NSHARD - 1) / NSHARD);
-        HIPCHK(hipMalloc(&c->d_cc_cand, sizeof(uint2) * per * NSHARD));
-        c->cc_shard_cap = per;
-    }
-    const uint64_t want = cap_pairs > 0 ? cap_pairs : 1;
-    if (want > c->cc_pairs_cap) {
-        hipFree(c->d_cc_pairs); hipFree(c->d_cc_toi); hipFree(c->d_cc_dists);
-        c->d_cc_pairs = nullptr; c->d_cc_toi = nullptr; c->d_cc_dists = nullptr; c->cc_pairs_cap = 0;
-        HIPCHK(hipMalloc(&c->d_cc_pairs, sizeof(uint32_t) * 2 * want));
-        HIPCHK(hipMalloc(&c->d_cc_toi, sizeof(double) * want));
-        HIPCHK(hipMalloc(&c->d_cc_dists, sizeof(double) * want));
-        c->cc_pairs_cap = want;
-    }
+    int rc = c->ccd.ensure(c->nt, cap_pairs);
+    if (!rc) rc = c->ccd_x1.ensure(c->nv, 3);
+    return rc ? rc : c->swept[0].ensure(c->nt);
+}
+// The swept refit of src's tree into sw (sized for src->nt >= 2 leaves): parent links, then the climb from the leaves moving from
+// src's vertices to x1.  d_state: the pass's counters, which take M.  On stream s (the between queries run b's refit on a's).
+static int enqueue_swept_refit(hipStream_t s, const cd_ctx *src, const double *x1, SweptBuf &sw, CcdState *d_state)
+{
+    const uint32_t n = src->nt;
+    const uint32_t *flags = src->d_os_ticket + 8;
+    HIPCHK(hipMemsetAsync(sw.d_up, 0xff, sizeof(int32_t) * 2 * (size_t)n, s));   // -1: no parent (the root; and any link a broken tree lacks)
+    k_ccd_links<<<cdiv(n - 1, CCD_THREADS), CCD_THREADS, 0, s>>>(src->d_recs32, (int)n, flags, sw.d_recs, sw.d_up, sw.d_arrive);
+    k_ccd_refit<<<cdiv(n, CCD_THREADS), CCD_THREADS, 0, s>>>(src->d_leaf, src->d_verts, x1, (int)n, flags, sw.d_up, sw.d_arrive, sw.d_recs, d_state);
     return CD_OK;
 }
-// x1 upload, swept refit (links, then the climb), descent, exact pass and the read-back of the counters (no synchronisation)
+// x1 upload, swept refit, descent, exact pass and the read-back of the counters (no synchronisation)
 static int ccd_enqueue(cd_ctx *c, const double *verts_end /* NULL: a redo, x1 is there */, double dist, uint64_t cap_pairs)
 {
     hipStream_t s = c->stream;
     const uint32_t n = c->nt;
-    if (verts_end) HIPCHK(hipMemcpyAsync(c->d_cc_x1, verts_end, sizeof(double) * 3 * (size_t)c->nv, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(c->d_cc_state, 0, sizeof(CcdState), s));
+    PairBuf<CcdState> &q = c->ccd;
+    double *x1 = c->ccd_x1.d;
+    if (verts_end) HIPCHK(hipMemcpyAsync(x1, verts_end, sizeof(double) * 3 * (size_t)c->nv, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(q.state.d, 0, sizeof(CcdState), s));
     if (n >= 2) {
-        HIPCHK(hipMemsetAsync(c->d_cc_up, 0xff, sizeof(int32_t) * 2 * (size_t)n, s));   // -1: no parent (the root; and any link a broken tree lacks)
-        k_ccd_links<<<cdiv(n - 1, CCD_THREADS), CCD_THREADS, 0, s>>>(c->d_recs32, (int)n, c->d_os_ticket + 8, c->d_cc_recs, c->d_cc_up, c->d_cc_arrive);
-        k_ccd_refit<<<cdiv(n, CCD_THREADS), CCD_THREADS, 0, s>>>(c->d_leaf, c->d_verts, c->d_cc_x1, (int)n, c->d_os_ticket + 8, c->d_cc_up, c->d_cc_arrive,
-                                                                 c->d_cc_recs, c->d_cc_state);
-        k_ccd_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(c->d_cc_recs, c->d_leaf, c->d_verts, c->d_cc_x1, (int)n, dist,
-                                                                               c->d_os_ticket + 8, c->d_cc_state, c->d_cc_cand, c->cc_shard_cap);
-        const uint32_t xb = std::max<uint32_t>(1u, std::min<uint32_t>(64u, cdiv(n, 4096)));   // workgroups per shard
-        k_ccd_exact<<<dim3(xb, NSHARD), PROX_EXACT_THREADS, 0, s>>>(c->d_cc_cand, c->cc_shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, c->d_cc_x1, dist,
-                                                                    c->d_cc_state, c->d_cc_pairs, c->d_cc_toi, c->d_cc_dists, cap_pairs);
+        const int rc = enqueue_swept_refit(s, c, x1, c->swept[0], q.state.d);
+        if (rc) return rc;
+        k_ccd_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(c->swept[0].d_recs, c->d_leaf, c->d_verts, x1, (int)n, dist,
+                                                                               c->d_os_ticket + 8, q.state.d, q.d_cand, q.shard_cap);
+        k_ccd_exact<<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, x1, dist,
+                                                                                 q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_cc_state, c->d_cc_state, sizeof(CcdState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(q.state.h, q.state.d, sizeof(CcdState), hipMemcpyDeviceToHost, s));
     return CD_OK;
-}
-// after the synchronisation: 1 = a shard overflowed (the buffer has been grown: enqueue again), 0 = done
-static int ccd_overflowed(cd_ctx *c, int &rc)
-{
-    uint64_t mx = 0;
-    for (int i = 0; i < NSHARD; ++i) mx = std::max<uint64_t>(mx, c->h_cc_state->shard[i * PROX_SHARD_STRIDE]);
-    rc = CD_OK;
-    if (mx <= c->cc_shard_cap) return 0;
-    hipFree(c->d_cc_cand); c->d_cc_cand = nullptr;
-    const uint64_t per = mx + mx / 4 + 1024;
-    const hipError_t e = hipMalloc(&c->d_cc_cand, sizeof(uint2) * per * NSHARD);
-    if (e != hipSuccess) { c->cc_shard_cap = 0; rc = -(int)e; return 0; }
-    c->cc_shard_cap = per;
-    return 1;
-}
-static int ccd_results(cd_ctx *c, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info)
-{
-    const CcdState *h = c->h_cc_state;
-    const uint64_t np = h->n_pairs, take = std::min(np, cap_pairs);
-    if (take) {
-        HIPCHK(hipMemcpy(pairs, c->d_cc_pairs, sizeof(uint32_t) * 2 * take, hipMemcpyDeviceToHost));
-        if (toi) HIPCHK(hipMemcpy(toi, c->d_cc_toi, sizeof(double) * take, hipMemcpyDeviceToHost));
-        if (dists) HIPCHK(hipMemcpy(dists, c->d_cc_dists, sizeof(double) * take, hipMemcpyDeviceToHost));
-    }
-    if (n_pairs) *n_pairs = np;
-    if (info) {
-        uint64_t cand = 0;
-        for (int i = 0; i < NSHARD; ++i) cand += h->shard[i * PROX_SHARD_STRIDE];
-        info->n_candidates = cand; info->n_tested = h->n_tested; info->n_evals = h->n_evals; info->n_unresolved = h->n_unresolved;
-    }
-    return np > cap_pairs ? CD_OVERFLOW : CD_OK;
 }
 // after a pass that is already enqueued and synchronised: redo it while a shard overflows, then the results
 static int ccd_finish(cd_ctx *c, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info)
 {
     int rc;
-    while (ccd_overflowed(c, rc)) {
+    while (c->ccd.overflowed(rc)) {
         if ((rc = ccd_enqueue(c, nullptr, dist, cap_pairs))) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     if (rc) return rc;
-    c->cc_seen = {true, c->nt, c->h_cc_state->m_bits, dist};
-    return ccd_results(c, pairs, toi, dists, cap_pairs, n_pairs, info);
+    c->swept[0].seen = {true, c->nt, c->ccd.state.h->m_bits, dist};
+    c->ccd.fill_info(info);
+    return c->ccd.results(pairs, toi, dists, cap_pairs, n_pairs);
 }
 static int ccd_args(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, uint64_t cap_pairs)
 {
@@ -2128,23 +2173,19 @@ int cd_ccd_points(const double *tri, uint64_t n, double dist, double *toi, doubl
 {
     if (!tri || !toi || !dists || !evals || !ccd_dist_ok(dist)) return CD_ERR_ARG;
     if (n == 0) return CD_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
-    double *d_t = nullptr, *d_toi = nullptr, *d_d = nullptr; uint32_t *d_e = nullptr;
-    hipError_t e = hipMalloc(&d_t, sizeof(double) * 36 * n);
-    if (e == hipSuccess) e = hipMalloc(&d_toi, sizeof(double) * n);
-    if (e == hipSuccess) e = hipMalloc(&d_d, sizeof(double) * n);
-    if (e == hipSuccess) e = hipMalloc(&d_e, sizeof(uint32_t) * n);
-    if (e == hipSuccess) e = hipMemcpy(d_t, tri, sizeof(double) * 36 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        k_ccd_points<<<cdiv(n, CCD_THREADS) < 4096u ? cdiv(n, CCD_THREADS) : 4096u, CCD_THREADS>>>(d_t, n, dist, d_toi, d_d, d_e);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(toi, d_toi, sizeof(double) * n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(dists, d_d, sizeof(double) * n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(evals, d_e, sizeof(uint32_t) * n, hipMemcpyDeviceToHost);
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_t = dev.in(tri, 36 * n);
+    double *d_toi = dev.out<double>(n), *d_d = dev.out<double>(n);
+    uint32_t *d_e = dev.out<uint32_t>(n);
+    if (dev.e == hipSuccess) {
+        k_ccd_points<<<strided_grid(n, CCD_THREADS), CCD_THREADS>>>(d_t, n, dist, d_toi, d_d, d_e);
+        dev.e = hipGetLastError();
     }
-    hipFree(d_t); hipFree(d_toi); hipFree(d_d); hipFree(d_e);
-    return e == hipSuccess ? CD_OK : -(int)e;
+    dev.back(toi, d_toi, n);
+    dev.back(dists, d_d, n);
+    dev.back(evals, d_e, n);
+    return dev.rc();
 }
 
 // ---- queries between two meshes (cd_between.h) ------------------------------------------------------------------------------------
@@ -2158,41 +2199,10 @@ static int bw_args(cd_ctx *a, cd_ctx *b, uint32_t *pairs, uint64_t cap_pairs)
 }
 static int bw_buffers(cd_ctx *a, const cd_ctx *b, uint64_t cap_pairs, bool ccd)
 {
-    if (!a->d_bw_state) {
-        HIPCHK(hipMalloc(&a->d_bw_state, sizeof(CcdState)));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&a->h_bw_state), sizeof(CcdState), hipHostMallocDefault));
-    }
-    if (!a->d_bw_cand) {                                                    // 16 candidates a triangle of a to start with; grown on overflow
-        const uint64_t per = std::max<uint64_t>(4096, (16ull * a->nt + NSHARD - 1) / NSHARD);
-        HIPCHK(hipMalloc(&a->d_bw_cand, sizeof(uint2) * per * NSHARD));
-        a->bw_shard_cap = per;
-    }
-    const uint64_t want = cap_pairs > 0 ? cap_pairs : 1;
-    if (want > a->bw_pairs_cap) {
-        hipFree(a->d_bw_pairs); hipFree(a->d_bw_toi); hipFree(a->d_bw_dists);
-        a->d_bw_pairs = nullptr; a->d_bw_toi = nullptr; a->d_bw_dists = nullptr; a->bw_pairs_cap = 0;
-        HIPCHK(hipMalloc(&a->d_bw_pairs, sizeof(uint32_t) * 2 * want));
-        HIPCHK(hipMalloc(&a->d_bw_toi, sizeof(double) * want));
-        HIPCHK(hipMalloc(&a->d_bw_dists, sizeof(double) * want));
-        a->bw_pairs_cap = want;
-    }
-    if (ccd) {
-        if (!a->d_bw_x1a) HIPCHK(hipMalloc(&a->d_bw_x1a, sizeof(double) * 3 * (size_t)a->nv));
-        if (b->nv > a->bw_x1b_cap) {
-            hipFree(a->d_bw_x1b); a->d_bw_x1b = nullptr; a->bw_x1b_cap = 0;
-            HIPCHK(hipMalloc(&a->d_bw_x1b, sizeof(double) * 3 * (size_t)b->nv));
-            a->bw_x1b_cap = b->nv;
-        }
-        if (b->nt > a->bw_rec_cap) {
-            hipFree(a->d_bw_recs); hipFree(a->d_bw_up); hipFree(a->d_bw_arrive);
-            a->d_bw_recs = nullptr; a->d_bw_up = nullptr; a->d_bw_arrive = nullptr; a->bw_rec_cap = 0;
-            HIPCHK(hipMalloc(&a->d_bw_recs, sizeof(NodeRec32) * (size_t)b->nt));
-            HIPCHK(hipMalloc(&a->d_bw_up, sizeof(int32_t) * 2 * (size_t)b->nt));
-            HIPCHK(hipMalloc(&a->d_bw_arrive, sizeof(uint32_t) * (size_t)b->nt));
-            a->bw_rec_cap = b->nt;
-        }
-    }
-    return CD_OK;
+    int rc = a->bw.ensure(a->nt, cap_pairs);
+    if (!ccd || rc) return rc;
+    if ((rc = a->bw_x1a.ensure(a->nv, 3)) || (rc = a->bw_x1b.ensure(b->nv, 3))) return rc;
+    return a->swept[1].ensure(b->nt);
 }
 // one pass (CCD: a's M, b's swept refit; descent; exact stage) and the read-back of the counters (no synchronisation).  ax1 / bx1: device
 // pointers to the end positions (CCD only).
@@ -2201,33 +2211,29 @@ static int bw_enqueue(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_
     hipStream_t s = a->stream;
     const uint32_t na = a->nt, nb = b->nt;
     const uint32_t *fa = a->d_os_ticket + 8, *fb = b->d_os_ticket + 8;
-    HIPCHK(hipMemsetAsync(a->d_bw_state, 0, sizeof(CcdState), s));
+    PairBuf<CcdState> &q = a->bw;
+    HIPCHK(hipMemsetAsync(q.state.d, 0, sizeof(CcdState), s));
     if (kind == BW_CCD) {
-        k_between_mbits<<<cdiv(na, CCD_THREADS), CCD_THREADS, 0, s>>>(a->d_leaf, a->d_verts, ax1, (int)na, a->d_bw_state);
-        if (nb >= 2) {
-            HIPCHK(hipMemsetAsync(a->d_bw_up, 0xff, sizeof(int32_t) * 2 * (size_t)nb, s));   // -1: no parent (the root)
-            k_ccd_links<<<cdiv(nb - 1, CCD_THREADS), CCD_THREADS, 0, s>>>(b->d_recs32, (int)nb, fb, a->d_bw_recs, a->d_bw_up, a->d_bw_arrive);
-            k_ccd_refit<<<cdiv(nb, CCD_THREADS), CCD_THREADS, 0, s>>>(b->d_leaf, b->d_verts, bx1, (int)nb, fb, a->d_bw_up, a->d_bw_arrive, a->d_bw_recs, a->d_bw_state);
-        }
-        k_between_descend<true><<<cdiv(na, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(a->d_bw_recs, b->d_root, (int)nb, a->d_leaf, a->d_verts, ax1, (int)na,
-                                                                                         a->d_boxes, b->d_boxes, dist, fa, fb, a->d_bw_state, a->d_bw_cand, a->bw_shard_cap);
+        k_between_mbits<<<cdiv(na, CCD_THREADS), CCD_THREADS, 0, s>>>(a->d_leaf, a->d_verts, ax1, (int)na, q.state.d);
+        if (nb >= 2) { const int rc = enqueue_swept_refit(s, b, bx1, a->swept[1], q.state.d); if (rc) return rc; }
+        k_between_descend<true><<<cdiv(na, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(a->swept[1].d_recs, b->d_root, (int)nb, a->d_leaf, a->d_verts, ax1, (int)na,
+                                                                                         a->d_boxes, b->d_boxes, dist, fa, fb, q.state.d, q.d_cand, q.shard_cap);
     } else {
         k_between_descend<false><<<cdiv(na, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(b->d_recs32, b->d_root, (int)nb, a->d_leaf, a->d_verts, nullptr, (int)na,
-                                                                                          a->d_boxes, b->d_boxes, dist, fa, fb, a->d_bw_state, a->d_bw_cand, a->bw_shard_cap);
+                                                                                          a->d_boxes, b->d_boxes, dist, fa, fb, q.state.d, q.d_cand, q.shard_cap);
     }
-    const uint32_t xb = std::max<uint32_t>(1u, std::min<uint32_t>(64u, cdiv(na, 4096)));   // workgroups per shard
-    const dim3 grid(xb, NSHARD);
+    const dim3 grid(shard_blocks(na), NSHARD);
     if (kind == BW_CONTACT)
-        k_between_exact<BW_CONTACT><<<grid, PROX_EXACT_THREADS, 0, s>>>(a->d_bw_cand, a->bw_shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
-                                                                        dist, a->d_bw_state, a->d_bw_pairs, a->d_bw_toi, a->d_bw_dists, cap_pairs);
+        k_between_exact<BW_CONTACT><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
+                                                                        dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs);
     else if (kind == BW_PROXIMITY)
-        k_between_exact<BW_PROXIMITY><<<grid, PROX_EXACT_THREADS, 0, s>>>(a->d_bw_cand, a->bw_shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
-                                                                          dist, a->d_bw_state, a->d_bw_pairs, a->d_bw_toi, a->d_bw_dists, cap_pairs);
+        k_between_exact<BW_PROXIMITY><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
+                                                                          dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs);
     else
-        k_between_exact<BW_CCD><<<grid, PROX_EXACT_THREADS, 0, s>>>(a->d_bw_cand, a->bw_shard_cap, a->d_leaf, a->d_verts, ax1, b->d_leaf, b->d_verts, bx1,
-                                                                    dist, a->d_bw_state, a->d_bw_pairs, a->d_bw_toi, a->d_bw_dists, cap_pairs);
+        k_between_exact<BW_CCD><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, ax1, b->d_leaf, b->d_verts, bx1,
+                                                                    dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(a->h_bw_state, a->d_bw_state, sizeof(CcdState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(q.state.h, q.state.d, sizeof(CcdState), hipMemcpyDeviceToHost, s));
     return CD_OK;
 }
 // enqueue, synchronise, and again with a grown candidate buffer while a shard overflowed
@@ -2237,26 +2243,8 @@ static int bw_pass(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_pai
         int rc = bw_enqueue(a, b, kind, dist, cap_pairs, ax1, bx1);
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(a->stream));
-        uint64_t mx = 0;
-        for (int i = 0; i < NSHARD; ++i) mx = std::max<uint64_t>(mx, a->h_bw_state->shard[i * PROX_SHARD_STRIDE]);
-        if (mx <= a->bw_shard_cap) return CD_OK;
-        hipFree(a->d_bw_cand); a->d_bw_cand = nullptr;
-        const uint64_t per = mx + mx / 4 + 1024;
-        const hipError_t e = hipMalloc(&a->d_bw_cand, sizeof(uint2) * per * NSHARD);
-        if (e != hipSuccess) { a->bw_shard_cap = 0; return -(int)e; }
-        a->bw_shard_cap = per;
+        if (!a->bw.overflowed(rc)) return rc;
     }
-}
-static int bw_results(cd_ctx *a, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs)
-{
-    const uint64_t np = a->h_bw_state->n_pairs, take = std::min(np, cap_pairs);
-    if (take) {
-        HIPCHK(hipMemcpy(pairs, a->d_bw_pairs, sizeof(uint32_t) * 2 * take, hipMemcpyDeviceToHost));
-        if (toi) HIPCHK(hipMemcpy(toi, a->d_bw_toi, sizeof(double) * take, hipMemcpyDeviceToHost));
-        if (dists) HIPCHK(hipMemcpy(dists, a->d_bw_dists, sizeof(double) * take, hipMemcpyDeviceToHost));
-    }
-    if (n_pairs) *n_pairs = np;
-    return np > cap_pairs ? CD_OVERFLOW : CD_OK;
 }
 static int bw_start(cd_ctx *a, cd_ctx *b, uint64_t cap_pairs, bool ccd)
 {
@@ -2271,8 +2259,8 @@ int cd_find_collisions_between(cd_ctx *a, cd_ctx *b, uint32_t *pairs, uint64_t c
     int rc = bw_args(a, b, pairs, cap_pairs);
     if (rc || (rc = bw_start(a, b, cap_pairs, false))) return rc;
     if ((rc = bw_pass(a, b, BW_CONTACT, 0.0, cap_pairs, nullptr, nullptr))) return rc;
-    if (n_tested) *n_tested = a->h_bw_state->n_tested;
-    return bw_results(a, pairs, nullptr, nullptr, cap_pairs, n_pairs);
+    if (n_tested) *n_tested = a->bw.state.h->n_tested;
+    return a->bw.results(pairs, nullptr, nullptr, cap_pairs, n_pairs);
 }
 int cd_find_proximity_between(cd_ctx *a, cd_ctx *b, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
 {
@@ -2281,8 +2269,8 @@ int cd_find_proximity_between(cd_ctx *a, cd_ctx *b, double dist, uint32_t *pairs
     if (!prox_dist_ok(dist)) return CD_ERR_ARG;
     if ((rc = bw_start(a, b, cap_pairs, false))) return rc;
     if ((rc = bw_pass(a, b, BW_PROXIMITY, dist, cap_pairs, nullptr, nullptr))) return rc;
-    if (n_tested) *n_tested = a->h_bw_state->n_tested;
-    return bw_results(a, pairs, nullptr, dists, cap_pairs, n_pairs);
+    if (n_tested) *n_tested = a->bw.state.h->n_tested;
+    return a->bw.results(pairs, nullptr, dists, cap_pairs, n_pairs);
 }
 int cd_find_ccd_between(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const double *verts_end_b, double dist, uint32_t *pairs, double *toi, double *dists,
                         uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info)
@@ -2292,34 +2280,16 @@ int cd_find_ccd_between(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const d
     if (!ccd_dist_ok(dist)) return CD_ERR_ARG;
     if ((rc = bw_start(a, b, cap_pairs, true))) return rc;
     const double *ax1 = a->d_verts, *bx1 = b->d_verts;                     // NULL: that mesh does not move (x1 = x0)
-    if (verts_end_a) { HIPCHK(hipMemcpyAsync(a->d_bw_x1a, verts_end_a, sizeof(double) * 3 * (size_t)a->nv, hipMemcpyHostToDevice, a->stream)); ax1 = a->d_bw_x1a; }
-    if (verts_end_b) { HIPCHK(hipMemcpyAsync(a->d_bw_x1b, verts_end_b, sizeof(double) * 3 * (size_t)b->nv, hipMemcpyHostToDevice, a->stream)); bx1 = a->d_bw_x1b; }
+    if (verts_end_a) { HIPCHK(hipMemcpyAsync(a->bw_x1a.d, verts_end_a, sizeof(double) * 3 * (size_t)a->nv, hipMemcpyHostToDevice, a->stream)); ax1 = a->bw_x1a.d; }
+    if (verts_end_b) { HIPCHK(hipMemcpyAsync(a->bw_x1b.d, verts_end_b, sizeof(double) * 3 * (size_t)b->nv, hipMemcpyHostToDevice, a->stream)); bx1 = a->bw_x1b.d; }
     if ((rc = bw_pass(a, b, BW_CCD, dist, cap_pairs, ax1, bx1))) return rc;
-    a->bw_seen = {true, b->nt, a->h_bw_state->m_bits, dist};
-    if (info) {
-        const CcdState *h = a->h_bw_state;
-        uint64_t cand = 0;
-        for (int i = 0; i < NSHARD; ++i) cand += h->shard[i * PROX_SHARD_STRIDE];
-        info->n_candidates = cand; info->n_tested = h->n_tested; info->n_evals = h->n_evals; info->n_unresolved = h->n_unresolved;
-    }
-    return bw_results(a, pairs, toi, dists, cap_pairs, n_pairs);
+    a->swept[1].seen = {true, b->nt, a->bw.state.h->m_bits, dist};
+    a->bw.fill_info(info);
+    return a->bw.results(pairs, toi, dists, cap_pairs, n_pairs);
 }
 // ---- ray queries (cd_rays.h) ------------------------------------------------------------------------------------------------------
 // Own buffers (rays, results, counters): nothing any other call keeps is touched.
 constexpr uint64_t RAY_BYTES = 7 * 8 + 8 + 16 + 4 + 4 + 1;                  // device bytes a ray: the ray, t, uv, face, ID, side
-static int ray_buffers(cd_ctx *c, uint64_t n)
-{
-    if (!c->d_ry_state) {
-        HIPCHK(hipMalloc(&c->d_ry_state, sizeof(RayState)));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_ry_state), sizeof(RayState), hipHostMallocDefault));
-    }
-    if (n > c->ry_cap) {
-        hipFree(c->d_ry_block); c->d_ry_block = nullptr; c->ry_cap = 0;
-        HIPCHK(hipMalloc(&c->d_ry_block, RAY_BYTES * n));
-        c->ry_cap = n;
-    }
-    return CD_OK;
-}
 int cd_cast_rays(cd_ctx *c, const double *rays, uint64_t n, int flags, uint32_t *face, uint32_t *ids, double *t, double *uv, uint8_t *side, cd_ray_info *info)
 {
     const bool any = flags == CD_RAY_ANY;
@@ -2333,73 +2303,53 @@ int cd_cast_rays(cd_ctx *c, const double *rays, uint64_t n, int flags, uint32_t 
     }
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if (n == 0) { if (info) *info = cd_ray_info{0, 0, 0}; return CD_OK; }
-    int rc = ray_buffers(c, n);
+    int rc = c->rays.ensure(n, RAY_BYTES);
     if (rc) return rc;
     hipStream_t s = c->stream;
-    const uint64_t cap = c->ry_cap;
-    double *d_rays = reinterpret_cast<double *>(c->d_ry_block), *d_t = d_rays + 7 * cap, *d_uv = d_t + cap;
+    const uint64_t cap = c->rays.block.cap;
+    double *d_rays = reinterpret_cast<double *>(c->rays.block.d), *d_t = d_rays + 7 * cap, *d_uv = d_t + cap;
     uint32_t *d_face = reinterpret_cast<uint32_t *>(d_uv + 2 * cap), *d_ids = d_face + cap;
     uint8_t *d_side = reinterpret_cast<uint8_t *>(d_ids + cap);
     HIPCHK(hipMemcpyAsync(d_rays, rays, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(c->d_ry_state, 0, sizeof(RayState), s));
+    HIPCHK(hipMemsetAsync(c->rays.state.d, 0, sizeof(RayState), s));
     const uint32_t grid = cdiv(n, RAY_THREADS);
-    if (any) k_cast_rays<true><<<grid, RAY_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_rays, n, c->d_ry_state,
+    if (any) k_cast_rays<true><<<grid, RAY_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_rays, n, c->rays.state.d,
                                                             d_face, nullptr, nullptr, nullptr, nullptr);
-    else k_cast_rays<false><<<grid, RAY_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_rays, n, c->d_ry_state,
+    else k_cast_rays<false><<<grid, RAY_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_rays, n, c->rays.state.d,
                                                          d_face, ids ? d_ids : nullptr, t ? d_t : nullptr, uv ? d_uv : nullptr, side ? d_side : nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_ry_state, c->d_ry_state, sizeof(RayState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(c->rays.state.h, c->rays.state.d, sizeof(RayState), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(face, d_face, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
     if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
     if (t) HIPCHK(hipMemcpyAsync(t, d_t, sizeof(double) * n, hipMemcpyDeviceToHost, s));
     if (uv) HIPCHK(hipMemcpyAsync(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, s));
     if (side) HIPCHK(hipMemcpyAsync(side, d_side, n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (info) { info->n_hits = c->h_ry_state->n_hits; info->node_visits = c->h_ry_state->node_visits; info->tri_tests = c->h_ry_state->tri_tests; }
+    if (info) { info->n_hits = c->rays.state.h->n_hits; info->node_visits = c->rays.state.h->node_visits; info->tri_tests = c->rays.state.h->tri_tests; }
     return CD_OK;
 }
 int cd_ray_tri_points(const double *ray, const double *tri, uint64_t n, uint8_t *hit, double *t, double *uv, uint8_t *side)
 {
     if (!ray || !tri || !hit) return CD_ERR_ARG;
     if (n == 0) return CD_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
-    double *d_r = nullptr, *d_p = nullptr, *d_t = nullptr, *d_uv = nullptr; uint8_t *d_h = nullptr, *d_s = nullptr;
-    hipError_t e = hipMalloc(&d_r, sizeof(double) * 7 * n);
-    if (e == hipSuccess) e = hipMalloc(&d_p, sizeof(double) * 9 * n);
-    if (e == hipSuccess) e = hipMalloc(&d_t, sizeof(double) * n);
-    if (e == hipSuccess) e = hipMalloc(&d_uv, sizeof(double) * 2 * n);
-    if (e == hipSuccess) e = hipMalloc(&d_h, n);
-    if (e == hipSuccess) e = hipMalloc(&d_s, n);
-    if (e == hipSuccess) e = hipMemcpy(d_r, ray, sizeof(double) * 7 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_p, tri, sizeof(double) * 9 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        k_ray_tri_points<<<cdiv(n, 256) < 4096u ? cdiv(n, 256) : 4096u, 256>>>(d_r, d_p, n, d_h, d_t, d_uv, d_s);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(hit, d_h, n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && t) e = hipMemcpy(t, d_t, sizeof(double) * n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && uv) e = hipMemcpy(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && side) e = hipMemcpy(side, d_s, n, hipMemcpyDeviceToHost);
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_r = dev.in(ray, 7 * n), *d_p = dev.in(tri, 9 * n);
+    double *d_t = dev.out<double>(n), *d_uv = dev.out<double>(2 * n);
+    uint8_t *d_h = dev.out<uint8_t>(n), *d_s = dev.out<uint8_t>(n);
+    if (dev.e == hipSuccess) {
+        k_ray_tri_points<<<strided_grid(n, 256), 256>>>(d_r, d_p, n, d_h, d_t, d_uv, d_s);
+        dev.e = hipGetLastError();
     }
-    hipFree(d_r); hipFree(d_p); hipFree(d_t); hipFree(d_uv); hipFree(d_h); hipFree(d_s);
-    return e == hipSuccess ? CD_OK : -(int)e;
+    dev.back(hit, d_h, n);
+    dev.back(t, d_t, n);
+    dev.back(uv, d_uv, 2 * n);
+    dev.back(side, d_s, n);
+    return dev.rc();
 }
 // ---- closest-point queries (cd_points.h) ------------------------------------------------------------------------------------------
 // Own buffers (points, results, counters): nothing any other call keeps is touched.
 constexpr uint64_t POINT_BYTES = 4 * 8 + 8 + 24 + 16 + 4 + 4 + 1 + 1;       // device bytes a point: the point, dist, closest, uv, face, ID, feature, side
-static int point_buffers(cd_ctx *c, uint64_t n)
-{
-    if (!c->d_pt_state) {
-        HIPCHK(hipMalloc(&c->d_pt_state, sizeof(PointState)));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_pt_state), sizeof(PointState), hipHostMallocDefault));
-    }
-    if (n > c->pt_cap) {
-        hipFree(c->d_pt_block); c->d_pt_block = nullptr; c->pt_cap = 0;
-        HIPCHK(hipMalloc(&c->d_pt_block, POINT_BYTES * n));
-        c->pt_cap = n;
-    }
-    return CD_OK;
-}
 int cd_closest_points(cd_ctx *c, const double *points, uint64_t n, int flags, uint32_t *face, uint32_t *ids, double *dist, double *closest, double *uv,
                       uint8_t *feature, uint8_t *side, cd_point_info *info)
 {
@@ -2411,23 +2361,23 @@ int cd_closest_points(cd_ctx *c, const double *points, uint64_t n, int flags, ui
     }
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if (n == 0) { if (info) *info = cd_point_info{0, 0, 0}; return CD_OK; }
-    int rc = point_buffers(c, n);
+    int rc = c->points.ensure(n, POINT_BYTES);
     if (rc) return rc;
     hipStream_t s = c->stream;
-    const uint64_t cap = c->pt_cap;
-    double *d_pts = reinterpret_cast<double *>(c->d_pt_block), *d_dist = d_pts + 4 * cap, *d_q = d_dist + cap, *d_uv = d_q + 3 * cap;
+    const uint64_t cap = c->points.block.cap;
+    double *d_pts = reinterpret_cast<double *>(c->points.block.d), *d_dist = d_pts + 4 * cap, *d_q = d_dist + cap, *d_uv = d_q + 3 * cap;
     uint32_t *d_face = reinterpret_cast<uint32_t *>(d_uv + 2 * cap), *d_ids = d_face + cap;
     uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + cap), *d_side = d_feat + cap;
     HIPCHK(hipMemcpyAsync(d_pts, points, sizeof(double) * 4 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(c->d_pt_state, 0, sizeof(PointState), s));
+    HIPCHK(hipMemsetAsync(c->points.state.d, 0, sizeof(PointState), s));
     const uint32_t grid = cdiv(n, POINT_THREADS);
-    if (any) k_closest_points<true><<<grid, POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_pts, n, c->d_pt_state,
+    if (any) k_closest_points<true><<<grid, POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_pts, n, c->points.state.d,
                                                                   d_face, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    else k_closest_points<false><<<grid, POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_pts, n, c->d_pt_state,
+    else k_closest_points<false><<<grid, POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_pts, n, c->points.state.d,
                                                                d_face, ids ? d_ids : nullptr, dist ? d_dist : nullptr, closest ? d_q : nullptr, uv ? d_uv : nullptr,
                                                                feature ? d_feat : nullptr, side ? d_side : nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_pt_state, c->d_pt_state, sizeof(PointState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(c->points.state.h, c->points.state.d, sizeof(PointState), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(face, d_face, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
     if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
     if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist, sizeof(double) * n, hipMemcpyDeviceToHost, s));
@@ -2436,36 +2386,28 @@ int cd_closest_points(cd_ctx *c, const double *points, uint64_t n, int flags, ui
     if (feature) HIPCHK(hipMemcpyAsync(feature, d_feat, n, hipMemcpyDeviceToHost, s));
     if (side) HIPCHK(hipMemcpyAsync(side, d_side, n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (info) { info->n_found = c->h_pt_state->n_found; info->node_visits = c->h_pt_state->node_visits; info->tri_tests = c->h_pt_state->tri_tests; }
+    if (info) { info->n_found = c->points.state.h->n_found; info->node_visits = c->points.state.h->node_visits; info->tri_tests = c->points.state.h->tri_tests; }
     return CD_OK;
 }
 int cd_pt_tri_points(const double *points, const double *tri, uint64_t n, double *dist, double *closest, double *uv, uint8_t *feature, uint8_t *side)
 {
     if (!points || !tri || !dist) return CD_ERR_ARG;
     if (n == 0) return CD_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return CD_ERR_NO_DEVICE;
-    double *d_p = nullptr, *d_t = nullptr, *d_d = nullptr, *d_q = nullptr, *d_uv = nullptr; uint8_t *d_f = nullptr, *d_s = nullptr;
-    hipError_t e = hipMalloc(&d_p, sizeof(double) * 3 * n);
-    if (e == hipSuccess) e = hipMalloc(&d_t, sizeof(double) * 9 * n);
-    if (e == hipSuccess) e = hipMalloc(&d_d, sizeof(double) * n);
-    if (e == hipSuccess) e = hipMalloc(&d_q, sizeof(double) * 3 * n);
-    if (e == hipSuccess) e = hipMalloc(&d_uv, sizeof(double) * 2 * n);
-    if (e == hipSuccess) e = hipMalloc(&d_f, n);
-    if (e == hipSuccess) e = hipMalloc(&d_s, n);
-    if (e == hipSuccess) e = hipMemcpy(d_p, points, sizeof(double) * 3 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_t, tri, sizeof(double) * 9 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        k_pt_tri_points<<<cdiv(n, 256) < 4096u ? cdiv(n, 256) : 4096u, 256>>>(d_p, d_t, n, d_d, d_q, d_uv, d_f, d_s);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(dist, d_d, sizeof(double) * n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && closest) e = hipMemcpy(closest, d_q, sizeof(double) * 3 * n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && uv) e = hipMemcpy(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && feature) e = hipMemcpy(feature, d_f, n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && side) e = hipMemcpy(side, d_s, n, hipMemcpyDeviceToHost);
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_p = dev.in(points, 3 * n), *d_t = dev.in(tri, 9 * n);
+    double *d_d = dev.out<double>(n), *d_q = dev.out<double>(3 * n), *d_uv = dev.out<double>(2 * n);
+    uint8_t *d_f = dev.out<uint8_t>(n), *d_s = dev.out<uint8_t>(n);
+    if (dev.e == hipSuccess) {
+        k_pt_tri_points<<<strided_grid(n, 256), 256>>>(d_p, d_t, n, d_d, d_q, d_uv, d_f, d_s);
+        dev.e = hipGetLastError();
     }
-    hipFree(d_p); hipFree(d_t); hipFree(d_d); hipFree(d_q); hipFree(d_uv); hipFree(d_f); hipFree(d_s);
-    return e == hipSuccess ? CD_OK : -(int)e;
+    dev.back(dist, d_d, n);
+    dev.back(closest, d_q, 3 * n);
+    dev.back(uv, d_uv, 2 * n);
+    dev.back(feature, d_f, n);
+    dev.back(side, d_s, n);
+    return dev.rc();
 }
 }  // extern "C"
 

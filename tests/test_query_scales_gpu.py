@@ -143,7 +143,7 @@ def test_far_from_origin(name):
 
 
 # ---------------------------------------------------------------- candidate-buffer growth
-# Both queries start with shards of max(4096, ceil(16 n / 64)) candidates (mi355cd.hip prox_buffers / ccd_buffers); a shard that
+# Both queries start with shards of max(4096, ceil(16 n / 64)) candidates (mi355cd.hip PairBuf::ensure); a shard that
 # overflows is detected, the buffer grows and the pass is redone.  More candidates in all than 64 shards hold forces that path.
 NSHARD = 64
 
@@ -189,6 +189,23 @@ def test_candidate_growth_on_all_pairs(all_pairs_soup):
                 _same_ccd(cd.find_ccd(x1, d, cap=cap), ccd[d], f"ccd dist={d} after growth")
         _same_prox(cd.self_proximity(small, cap=cap), prox[small], "self_proximity after growth")
         _same_ccd(cd.self_ccd(x1, small, cap=cap), ccd[small], "self_ccd after growth")
+
+
+def test_first_query_overflows_behind_the_build(all_pairs_soup):
+    """A fresh context whose very first call is a build-and-query entry point: every buffer of the query is allocated by that call,
+    the pass behind the build overflows its initial shards, and the redo runs on the grown buffer and the tree just built."""
+    v, vidx, x1, big, small, prox, ccd = all_pairs_soup
+    n = vidx.shape[0]
+    every = n * (n - 1) // 2
+    assert every > NSHARD * _shard_cap0(n)
+    cap = every + 16
+    with mi355cd.CollisionDetector(v, vidx) as cd:
+        _same_ccd(cd.self_ccd(x1, big, cap=cap), ccd[big], "self_ccd first, all pairs")
+        assert cd.ccd_info.n_candidates == every
+        assert cd.debug_swept()[0].shape[0] == n                          # (debug_swept itself refuses a swept tree of another size)
+    with mi355cd.CollisionDetector(v, vidx) as cd:
+        _same_prox(cd.self_proximity(big, cap=cap), prox[big], "self_proximity first, all pairs")
+        assert cd.proximity_tested == every
 
 
 def test_candidate_growth_above_the_per_triangle_capacity():
