@@ -330,7 +330,7 @@ def want_root_box(name, f):
 def expected_swept(x0, x1_, vidx, step, m_bits, dist):
     """What cd_debug_swept, cd_debug_records and cd_export_keys return for a correct device, from the oracle's tree `step`
     (oracle.pipeline) and the restatement: the dict test_swept_gpu.py's _read makes (the static records hold their link and range words
-    only; nothing compares their boxes here)."""
+    only here; their boxes, flag bits and the query boxes are pinned to records_ref.py's restatement by test_records_gpu.py)."""
     n = np.asarray(vidx).reshape(-1, 3).shape[0]
     none = np.zeros((0, 8), dtype=np.uint32)
     out = dict(perm=step["perm"], m_bits=int(m_bits), pad=sr.pad(int(m_bits), dist))
