@@ -3,14 +3,14 @@
 // predicate takes a's triangle first; the two vertex arrays are unrelated, so there is no neighbour filter.
 //   k_between_mbits   : CCD only.  The largest |coordinate| of a's swept leaf boxes (x0 and x1) into CcdState::m_bits, beside what
 //       k_ccd_refit leaves there for b's: M of the CCD pad covers both meshes.
-//   k_between_descend : fp32 filter.  One lane per leaf of a (sorted order) walks b's records in pre-order from b's ROOT (prox_walk,
-//       cd_proximity.h): the root's left child, ending at its split, then the chain of right children.  Static: b's records read as
+//   k_between_descend : fp32 filter.  One lane per leaf of a (sorted order) walks b's records from b's ROOT (prox_walk,
+//       cd_proximity.h, with the cursor of cd_bvh.h started at the root).  Static: b's records read as
 //       [lo, prox_hi(hi)], the query box a's FP64 leaf box widened by prox_pad over both root boxes.  Swept: b's swept records (true
 //       bounds, k_ccd_links + k_ccd_refit over b), the query box a's swept box widened by ccd_pad.  nb == 1: no records; every leaf of
 //       a is a candidate against b's leaf 0 and the exact stage decides.
 //   k_between_exact   : FP64, one instance per query kind.  Contact: the strict box test (box.cuh:40-43, counted), then tri_contact.
 //       Proximity: tri_distance.  CCD: the swept-box gate, then ccd_advance on a two-mesh source.  Append with one atomic per workgroup
-//       and round, as k_prox_exact.
+//       and round, as k_prox_exact (the exact stage's scaffold, cd_proximity.h).
 // The pads are section 10's and 11's with M over both meshes, so every pair the FP64 definition accepts is a candidate and the FP64
 // stage alone decides: the result does not depend on either tree.
 #pragma once
@@ -57,12 +57,11 @@ __global__ __launch_bounds__(PROX_DESC_THREADS) void k_between_descend(const Nod
 {
     if (sort_failed(flags_a) || sort_failed(flags_b)) return;           // the records are not a tree (the host redoes the build)
     const uint32_t j = blockIdx.x * PROX_DESC_THREADS + threadIdx.x;
-    unsigned long long *ctr = &st->shard[(blockIdx.x & (NSHARD - 1)) * PROX_SHARD_STRIDE];
-    uint2 *shard = cand + (size_t)(blockIdx.x & (NSHARD - 1)) * shard_cap;
     if (nb == 1) {                                                       // no records: leaf 0 is the whole tree
         if ((int)j < na) {
-            const unsigned long long at = atomicAdd(ctr, 1ull);
-            if (at < shard_cap) shard[at] = make_uint2(j, 0u);
+            const uint32_t sh = blockIdx.x & (NSHARD - 1);               // (the workgroup's shard, as prox_walk takes it)
+            const unsigned long long at = atomicAdd(&st->shard[sh * PROX_SHARD_STRIDE], 1ull);
+            if (at < shard_cap) cand[(size_t)sh * shard_cap + at] = make_uint2(j, 0u);
         }
         return;
     }
@@ -73,24 +72,16 @@ __global__ __launch_bounds__(PROX_DESC_THREADS) void k_between_descend(const Nod
         pad = pa > pb ? pa : pb;                                         // (prox_pad is monotonic in M: the pad of the larger M)
     }
     bool active = (int)j < na;
-    float qlx = 0.f, qly = 0.f, qlz = 0.f, qhx = 0.f, qhy = 0.f, qhz = 0.f;
-    float4 h0 = make_float4(0.f, 0.f, 0.f, 0.f), h1 = h0;
-    uint32_t end = 0;
+    QueryBox32 q{};
+    RecCursor w{};
     if (active) {
         const LeafTri lt = leaf_a[j];
-        const Box b = SWEPT ? swept_box(CcdMeshSrc{ax0, ax1, lt.v0, lt.v1, lt.v2, 0u, 0u, 0u}, 0)
-                            : box_set(load_vertex(ax0, lt.v0), load_vertex(ax0, lt.v1), load_vertex(ax0, lt.v2));
-        qlx = __ocml_sub_rtn_f32(__double2float_rd(b.x1), pad); qly = __ocml_sub_rtn_f32(__double2float_rd(b.y1), pad); qlz = __ocml_sub_rtn_f32(__double2float_rd(b.z1), pad);
-        qhx = __ocml_add_rtp_f32(__double2float_ru(b.x2), pad); qhy = __ocml_add_rtp_f32(__double2float_ru(b.y2), pad); qhz = __ocml_add_rtp_f32(__double2float_ru(b.z2), pad);
-        const uint32_t root = (uint32_t)*root_name_b;
-        if (root < (uint32_t)(nb - 1)) {                                 // the root's left child, which ends at the root's split
-            const float4 *l = rec_left(recs_b, nb, root);
-            h0 = l[0]; h1 = l[1];
-            end = root;
-        } else active = false;                                           // (no tree: nothing is read)
+        q = query_box32(SWEPT ? swept_box(CcdMeshSrc{ax0, ax1, lt.v0, lt.v1, lt.v2, 0u, 0u, 0u}, 0)
+                              : box_set(load_vertex(ax0, lt.v0), load_vertex(ax0, lt.v1), load_vertex(ax0, lt.v2)), pad);
+        active = w.start_root(recs_b, nb, (uint32_t)*root_name_b);
     }
-    if (SWEPT) prox_walk<HiTrue>(recs_b, nb, j, active, h0, h1, end, qlx, qly, qlz, qhx, qhy, qhz, ctr, shard, shard_cap);
-    else prox_walk<HiNextUp>(recs_b, nb, j, active, h0, h1, end, qlx, qly, qlz, qhx, qhy, qhz, ctr, shard, shard_cap);
+    if (SWEPT) prox_walk<HiTrue>(recs_b, nb, j, active, w, q, st->shard, cand, shard_cap);
+    else prox_walk<HiNextUp>(recs_b, nb, j, active, w, q, st->shard, cand, shard_cap);
 }
 
 template <int KIND>
@@ -100,71 +91,47 @@ __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_between_exact(const uint
                                                                      double dist, CcdState *__restrict__ st, uint32_t *__restrict__ pairs,
                                                                      double *__restrict__ toi_out, double *__restrict__ dists, unsigned long long cap)
 {
-    __shared__ uint32_t s_cnt;
-    __shared__ unsigned long long s_base;
-    __shared__ unsigned long long s_sum[3][PROX_EXACT_THREADS / 64];
-    const uint32_t tid = threadIdx.x, sh = blockIdx.y;
-    const unsigned long long reserved = st->shard[sh * PROX_SHARD_STRIDE];
-    const unsigned long long total = reserved < shard_cap ? reserved : shard_cap;
-    const uint2 *list = cand + (size_t)sh * shard_cap;
-    unsigned long long tested = 0, evals = 0, unresolved = 0;
-    for (unsigned long long b0 = (unsigned long long)blockIdx.x * PROX_EXACT_THREADS; b0 < total; b0 += (unsigned long long)gridDim.x * PROX_EXACT_THREADS) {
-        const unsigned long long i = b0 + tid;
+    const ShardSlice sl(st->shard, cand, shard_cap);
+    unsigned long long sums[3] = {0, 0, 0};                              // tested, evals, unresolved: CcdState's order
+    for (unsigned long long b0 = sl.first(); b0 < sl.total; b0 += sl.stride()) {
+        const unsigned long long i = b0 + threadIdx.x;
         bool hit = false;
         uint32_t ida = 0, idb = 0; double toi = 0.0, d = 0.0;
-        if (i < total) {
-            const uint2 c = list[i];
+        if (i < sl.total) {
+            const uint2 c = sl.list[i];
             const LeafTri A = leaf_a[c.x], B = leaf_b[c.y];
             ida = A.id; idb = B.id;
             if (KIND == BW_CONTACT) {
                 const d3 P1 = load_vertex(ax0, A.v0), P2 = load_vertex(ax0, A.v1), P3 = load_vertex(ax0, A.v2);
                 const d3 Q1 = load_vertex(bx0, B.v0), Q2 = load_vertex(bx0, B.v1), Q3 = load_vertex(bx0, B.v2);
                 if (box_overlap(box_set(P1, P2, P3), box_set(Q1, Q2, Q3))) {                  // box.cuh:40-43
-                    ++tested;
+                    ++sums[0];
                     hit = tri_contact_fast(P1, P2, P3, Q1, Q2, Q3);                           // tri_contact.cuh:19-78, a's triangle as P
                 }
             } else if (KIND == BW_PROXIMITY) {
-                ++tested;
+                ++sums[0];
                 d = tri_distance(load_vertex(ax0, A.v0), load_vertex(ax0, A.v1), load_vertex(ax0, A.v2),
                                  load_vertex(bx0, B.v0), load_vertex(bx0, B.v1), load_vertex(bx0, B.v2));
                 hit = d <= dist;
             } else {
                 const CcdTwoMeshSrc src{ax0, ax1, bx0, bx1, A.v0, A.v1, A.v2, B.v0, B.v1, B.v2};
                 if (ccd_gate(src, dist)) {
-                    ++tested;
+                    ++sums[0];
                     uint32_t ne = 0;
                     ccd_advance(src, dist, toi, d, ne);
-                    evals += ne;
+                    sums[1] += ne;
                     hit = toi <= 1.0;
-                    unresolved += (hit && !(d <= dist)) ? 1u : 0u;
+                    sums[2] += (hit && !(d <= dist)) ? 1u : 0u;
                 }
             }
         }
-        if (tid == 0) s_cnt = 0u;
-        __syncthreads();
-        const uint32_t slot = hit ? atomicAdd(&s_cnt, 1u) : 0u;
-        __syncthreads();
-        if (tid == 0 && s_cnt) s_base = atomicAdd(&st->n_pairs, (unsigned long long)s_cnt);
-        __syncthreads();
-        if (hit) {
-            const unsigned long long at = s_base + slot;
-            if (at < cap) {
-                pairs[2 * at] = ida; pairs[2 * at + 1] = idb;
-                if (KIND == BW_PROXIMITY) dists[at] = d;
-                if (KIND == BW_CCD) { toi_out[at] = toi; dists[at] = d; }
-            }
-        }
-        __syncthreads();                                                 // (s_cnt / s_base are reused by the next round)
+        pair_append(hit, &st->n_pairs, cap, [&](unsigned long long at) {
+            pairs[2 * at] = ida; pairs[2 * at + 1] = idb;
+            if (KIND == BW_PROXIMITY) dists[at] = d;
+            if (KIND == BW_CCD) { toi_out[at] = toi; dists[at] = d; }
+        });
     }
-    tested = wave_sum_u64(tested);
-    if (KIND == BW_CCD) { evals = wave_sum_u64(evals); unresolved = wave_sum_u64(unresolved); }
-    if ((tid & 63) == 0) { s_sum[0][tid >> 6] = tested; s_sum[1][tid >> 6] = evals; s_sum[2][tid >> 6] = unresolved; }
-    __syncthreads();
-    if (tid < 3) {
-        unsigned long long t = 0;
-        for (int w = 0; w < PROX_EXACT_THREADS / 64; ++w) t += s_sum[tid][w];
-        if (t) atomicAdd(tid == 0 ? &st->n_tested : (tid == 1 ? &st->n_evals : &st->n_unresolved), t);
-    }
+    group_counters_add<KIND == BW_CCD ? 3 : 1>(sums, &st->n_tested, &st->n_evals, &st->n_unresolved);     // (only CCD counts evaluations and unresolved pairs)
 }
 
 }  // namespace cd

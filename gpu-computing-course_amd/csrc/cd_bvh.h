@@ -131,6 +131,63 @@ static_assert(sizeof(NodeRec32) == 64, "NodeRec32 is two 32-byte halves");
 __device__ __forceinline__ const float4 *rec_right(const NodeRec32 *recs, int n, uint32_t s) { return reinterpret_cast<const float4 *>(recs) + 2 * (size_t)s; }
 __device__ __forceinline__ const float4 *rec_left(const NodeRec32 *recs, int n, uint32_t s) { return reinterpret_cast<const float4 *>(recs) + 2 * (size_t)n + 2 * (size_t)s; }
 
+// THE QUERIES' WALK over these records, stackless and in pre-order, written once (prox_walk in cd_proximity.h,
+// k_cast_rays, k_closest_points; the collision descents of cd_traverse.h read the records their own way).
+// The cursor is the subtree at hand: its box and link as a record half holds them (h0, h1: lo = h0.xyz,
+// hi = (h0.w, h1.x, h1.y), link = h1.z) and `end`, its last leaf.
+//   descend : an internal node that the query enters goes on to its left child, which ends at the node's split;
+//   next    : a subtree that is done -- missed, or a leaf -- is followed by the right child of the split at `end`,
+//             the next subtree in pre-order, until end == n-1.
+// Nothing is pushed, so no depth can overflow anything.
+// ONE step rule: every move counts, and a walk makes at most 2 n of them.  A tree needs at most 2 n - 2 (every
+// node but the root is visited once), so the bound only ends a walk over records that are not a tree.
+// ONE guard set: a link is an internal node iff 0 <= link < n - 1 and a leaf iff it is ~k with k < n; a link that
+// is neither is not entered and not tested, so not even a broken tree sends a lane out of bounds.
+__device__ __forceinline__ bool rec_internal(int32_t link, int n) { return (uint32_t)link < (uint32_t)(n - 1); }   // (n >= 1; one compare for both ends)
+struct RecCursor {
+    float4 h0, h1; uint32_t end, steps;
+    __device__ __forceinline__ int32_t link() const { return (int32_t)__float_as_uint(h1.z); }
+    __device__ __forceinline__ bool internal(int n) const { return rec_internal(link(), n); }
+    __device__ __forceinline__ bool leaf(int n) const { return ~(uint32_t)link() < (uint32_t)n; }   // (n <= 2^30: a link >= 0 has ~link >= 2^31)
+    __device__ __forceinline__ uint32_t leaf_index() const { return ~(uint32_t)link(); }
+    // placed at a child of split s (not a move of the walk: the starts, and the closest-point seed's look at both children)
+    __device__ __forceinline__ void at_left(const NodeRec32 *recs, int n, uint32_t s)
+    {
+        const float4 *l = rec_left(recs, n, s);
+        h0 = l[0]; h1 = l[1];
+        end = s;
+    }
+    __device__ __forceinline__ void at_right(const NodeRec32 *recs, int n, uint32_t s)
+    {
+        const float4 *r = rec_right(recs, n, s);
+        h0 = r[0]; h1 = r[1];
+        end = __float_as_uint(h1.w) & REC_LAST_MASK;
+    }
+    // the starts: behind leaf j < n - 1 (the leaves (j, n-1]: the right child of recs[j]), and at the root named `root`
+    // (its left child; false: there is no tree, nothing is read)
+    __device__ __forceinline__ void start_behind(const NodeRec32 *recs, int n, uint32_t j) { steps = 0; at_right(recs, n, j); }
+    __device__ __forceinline__ bool start_root(const NodeRec32 *recs, int n, uint32_t root)
+    {
+        steps = 0;
+        if (!rec_internal((int32_t)root, n)) return false;
+        at_left(recs, n, root);
+        return true;
+    }
+    // the moves; false: the walk is over
+    __device__ __forceinline__ bool count(int n) { return ++steps <= 2u * (uint32_t)n; }        // the step rule
+    __device__ __forceinline__ bool descend(const NodeRec32 *recs, int n)                       // (internal(n) held)
+    {
+        at_left(recs, n, (uint32_t)link());
+        return count(n);
+    }
+    __device__ __forceinline__ bool next(const NodeRec32 *recs, int n)
+    {
+        if (end >= (uint32_t)(n - 1) || !count(n)) return false;
+        at_right(recs, n, end);
+        return true;
+    }
+};
+
 // fp32 query box of leaf j, encoded like the records', written by the refit: 32 coalesced bytes per query
 // instead of the 48-byte FP64 box (k_descend and the packers read it; k_descend_half takes the same box and the same
 // certain bit out of the leaf's parent record, which it reads anyway -- cd_traverse.h).  flags bit 0: the box is EXACT (fp32 values, certain); bit 2: CERTAIN; bit 1: the FP64 box strictly

@@ -7,9 +7,10 @@
 //   k_ccd_refit    : one lane per leaf: the FP64 box of the leaf's six points (x0 and x1) rounded outward to fp32 is written into
 //       its parent's record half; the lane climbs while it is the second to arrive at a record (per-split arrival counter) and
 //       writes the union of that record's two halves into ITS parent's half.  fp32 unions of outward-rounded boxes are true bounds.
-//   k_ccd_descend  : k_prox_descend's stackless pre-order walk (prox_walk) over the swept records; the query box is the leaf's swept box
-//       widened by ccd_pad with directed rounding; candidates go through the same LDS queue to the same shards.
-//   k_ccd_exact    : neighbour filter, FP64 swept-box gate, ccd_advance, append (IDs, toi, d) with one atomic per workgroup and round.
+//   k_ccd_descend  : k_prox_descend over the swept records (prox_walk with the records' hi read as they are); the query box is the
+//       leaf's swept box widened by ccd_pad with directed rounding; candidates go through the same LDS queue to the same shards.
+//   k_ccd_exact    : neighbour filter, FP64 swept-box gate, ccd_advance, append (IDs, toi, d) with one atomic per workgroup and round
+//       (the exact stage's scaffold, cd_proximity.h).
 //   k_ccd_points   : ccd_advance on explicit positions (cd_ccd_points): the pin of the device code.
 #pragma once
 #include "cd_proximity.h"
@@ -111,15 +112,9 @@ template <class S> __device__ __forceinline__ bool ccd_gate(const S &s, double d
 
 // ---------------------------------------------------------------- swept records
 // up[j] (leaf j) and up[n + s] (internal node named by split s): (parent split << 1) | side (0 left, 1 right); -1 (the host's memset)
-// for the root.  Both kernels check the sort flags first, as k_prox_descend does: after a failed sort the records are not a tree
+// for the root.  Both kernels check the sort flags first (sort_failed, cd_traverse.h), as k_prox_descend does: after a failed sort the records are not a tree
 // (the host redoes the build), and nothing is read from them or written through them.  Links outside [0, n) are skipped and the
 // climb is bounded by n steps, so not even a broken tree can send a lane out of bounds.
-__device__ __forceinline__ bool sort_failed(const uint32_t *__restrict__ sort_flags)
-{
-    uint32_t bad = 0;
-    for (int i = 0; i < 9; ++i) bad |= sort_flags[i];
-    return bad != 0u;
-}
 __global__ __launch_bounds__(CCD_THREADS) void k_ccd_links(const NodeRec32 *__restrict__ recs, int n, const uint32_t *__restrict__ sort_flags /* 9 words */,
                                                            NodeRec32 *__restrict__ swept, int32_t *__restrict__ up, uint32_t *__restrict__ arrive)
 {
@@ -203,23 +198,16 @@ __global__ __launch_bounds__(PROX_DESC_THREADS) void k_ccd_descend(const NodeRec
 {
     if (sort_failed(sort_flags)) return;                                 // the records are not a tree (the host redoes the build)
     const uint32_t j = blockIdx.x * PROX_DESC_THREADS + threadIdx.x;
-    unsigned long long *ctr = &st->shard[(blockIdx.x & (NSHARD - 1)) * PROX_SHARD_STRIDE];
-    uint2 *shard = cand + (size_t)(blockIdx.x & (NSHARD - 1)) * shard_cap;
     const float pad = ccd_pad(st, dist);
-    bool active = (int)j < n - 1;
-    float qlx = 0.f, qly = 0.f, qlz = 0.f, qhx = 0.f, qhy = 0.f, qhz = 0.f;
-    float4 h0 = make_float4(0.f, 0.f, 0.f, 0.f), h1 = h0;                // the subtree at hand: its box and link, as a record half holds them
-    uint32_t end = 0;                                                    // its last leaf
+    const bool active = (int)j < n - 1;
+    QueryBox32 q{};
+    RecCursor w{};
     if (active) {
         const LeafTri lt = leaf[j];
-        const Box b = swept_box(CcdMeshSrc{x0, x1, lt.v0, lt.v1, lt.v2, 0u, 0u, 0u}, 0);
-        qlx = __ocml_sub_rtn_f32(__double2float_rd(b.x1), pad); qly = __ocml_sub_rtn_f32(__double2float_rd(b.y1), pad); qlz = __ocml_sub_rtn_f32(__double2float_rd(b.z1), pad);
-        qhx = __ocml_add_rtp_f32(__double2float_ru(b.x2), pad); qhy = __ocml_add_rtp_f32(__double2float_ru(b.y2), pad); qhz = __ocml_add_rtp_f32(__double2float_ru(b.z2), pad);
-        const float4 *r = rec_right(recs, n, j);
-        h0 = r[0]; h1 = r[1];
-        end = __float_as_uint(h1.w) & REC_LAST_MASK;
+        q = query_box32(swept_box(CcdMeshSrc{x0, x1, lt.v0, lt.v1, lt.v2, 0u, 0u, 0u}, 0), pad);
+        w.start_behind(recs, n, j);
     }
-    prox_walk<HiTrue>(recs, n, j, active, h0, h1, end, qlx, qly, qlz, qhx, qhy, qhz, ctr, shard, shard_cap);
+    prox_walk<HiTrue>(recs, n, j, active, w, q, st->shard, cand, shard_cap);
 }
 
 __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_ccd_exact(const uint2 *__restrict__ cand, unsigned long long shard_cap, const LeafTri *__restrict__ leaf,
@@ -227,55 +215,32 @@ __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_ccd_exact(const uint2 *_
                                                                  double dist, CcdState *__restrict__ st, uint32_t *__restrict__ pairs, double *__restrict__ toi_out,
                                                                  double *__restrict__ dists, unsigned long long cap)
 {
-    __shared__ uint32_t s_cnt;
-    __shared__ unsigned long long s_base;
-    __shared__ unsigned long long s_sum[3][PROX_EXACT_THREADS / 64];
-    const uint32_t tid = threadIdx.x, sh = blockIdx.y;
-    const unsigned long long reserved = st->shard[sh * PROX_SHARD_STRIDE];
-    const unsigned long long total = reserved < shard_cap ? reserved : shard_cap;
-    const uint2 *list = cand + (size_t)sh * shard_cap;
-    unsigned long long tested = 0, evals = 0, unresolved = 0;
-    for (unsigned long long b0 = (unsigned long long)blockIdx.x * PROX_EXACT_THREADS; b0 < total; b0 += (unsigned long long)gridDim.x * PROX_EXACT_THREADS) {
-        const unsigned long long i = b0 + tid;
+    const ShardSlice sl(st->shard, cand, shard_cap);
+    unsigned long long sums[3] = {0, 0, 0};                              // tested, evals, unresolved: CcdState's order
+    for (unsigned long long b0 = sl.first(); b0 < sl.total; b0 += sl.stride()) {
+        const unsigned long long i = b0 + threadIdx.x;
         bool hit = false;
         uint32_t ida = 0, idb = 0; double toi = 0.0, d = 0.0;
-        if (i < total) {
-            const uint2 c = list[i];
+        if (i < sl.total) {
+            const uint2 c = sl.list[i];
             LeafTri A = leaf[c.x], B = leaf[c.y];
             if (neighbor_count(A.v0, A.v1, A.v2, B.v0, B.v1, B.v2) < 1) {                 // collision.cuh:38
                 if (B.id < A.id || (B.id == A.id && perm[c.y] < perm[c.x])) { const LeafTri t = A; A = B; B = t; }   // A: the smaller ID (then face index)
                 const CcdMeshSrc src{x0, x1, A.v0, A.v1, A.v2, B.v0, B.v1, B.v2};
                 if (ccd_gate(src, dist)) {
-                    ++tested;
+                    ++sums[0];
                     uint32_t ne = 0;
                     ccd_advance(src, dist, toi, d, ne);
-                    evals += ne;
+                    sums[1] += ne;
                     hit = toi <= 1.0;
-                    unresolved += (hit && !(d <= dist)) ? 1u : 0u;
+                    sums[2] += (hit && !(d <= dist)) ? 1u : 0u;
                     ida = A.id; idb = B.id;
                 }
             }
         }
-        if (tid == 0) s_cnt = 0u;
-        __syncthreads();
-        const uint32_t slot = hit ? atomicAdd(&s_cnt, 1u) : 0u;
-        __syncthreads();
-        if (tid == 0 && s_cnt) s_base = atomicAdd(&st->n_pairs, (unsigned long long)s_cnt);
-        __syncthreads();
-        if (hit) {
-            const unsigned long long at = s_base + slot;
-            if (at < cap) { pairs[2 * at] = ida; pairs[2 * at + 1] = idb; toi_out[at] = toi; dists[at] = d; }
-        }
-        __syncthreads();                                                 // (s_cnt / s_base are reused by the next round)
+        pair_append(hit, &st->n_pairs, cap, [&](unsigned long long at) { pairs[2 * at] = ida; pairs[2 * at + 1] = idb; toi_out[at] = toi; dists[at] = d; });
     }
-    tested = wave_sum_u64(tested); evals = wave_sum_u64(evals); unresolved = wave_sum_u64(unresolved);
-    if ((tid & 63) == 0) { s_sum[0][tid >> 6] = tested; s_sum[1][tid >> 6] = evals; s_sum[2][tid >> 6] = unresolved; }
-    __syncthreads();
-    if (tid < 3) {
-        unsigned long long t = 0;
-        for (int w = 0; w < PROX_EXACT_THREADS / 64; ++w) t += s_sum[tid][w];
-        if (t) atomicAdd(tid == 0 ? &st->n_tested : (tid == 1 ? &st->n_evals : &st->n_unresolved), t);
-    }
+    group_counters_add<3>(sums, &st->n_tested, &st->n_evals, &st->n_unresolved);
 }
 
 // cd_ccd_points: ccd_advance on explicit positions, n x 36 doubles

@@ -2,13 +2,13 @@
 //   k_closest_points<ANY> : one lane per query point, in the order given (neighbouring points share a wave: coherent points should be
 //       neighbours).  A point with no radius meets every box, so a pre-order walk alone would test everything before the first near
 //       leaf in Morton order; the lane therefore works in two phases, both in the one loop below (ONE inline site of pt_tri):
-//       SEED   from the root, a greedy descent: both halves of a node's record (rec_left / rec_right: the two children's boxes), on
-//              to the child whose box is nearer to the point, ties to the left, down to a leaf, whose triangle gives the first
-//              candidate and the first bound  best = min(rmax, dist).
-//       WALK   the stackless pre-order walk over the split-named records from the ROOT, with the link and `end` rules of k_cast_rays
-//              (cd_rays.h): a subtree is entered when its box's lower-bound distance does not exceed `best`, CLOSED, so that a triangle
-//              at the same distance with a smaller ID is still seen; `best` shrinks with every better candidate.  The seed leaf may
-//              be tested a second time: no bookkeeping avoids it.
+//       SEED   from the root, a greedy descent: a cursor at each child of the node (both halves of its record), on to the child
+//              whose box is nearer to the point, ties to the left, down to a leaf, whose triangle gives the first candidate and the
+//              first bound  best = min(rmax, dist).
+//       WALK   the queries' stackless pre-order walk from the ROOT (RecCursor, cd_bvh.h: the walk, its step bound and its guards are
+//              described there): a subtree is entered when its box's lower-bound distance does not exceed `best`, CLOSED, so that a
+//              triangle at the same distance with a smaller ID is still seen; `best` shrinks with every better candidate.  The seed
+//              leaf may be tested a second time: no bookkeeping avoids it.
 //       At a leaf the exact FP64 predicate pt_tri (cd_math.h) runs INLINE, for the reason k_cast_rays gives: the bound shrinks with
 //       every candidate, so a queue would carry boxes the next candidate makes pointless.  Of the triangles with dist <= rmax the
 //       smallest (dist, triangle ID, face index) wins.  ANY: the lane stops at the first triangle within rmax, often the seed.
@@ -53,59 +53,48 @@ __global__ __launch_bounds__(POINT_THREADS) void k_closest_points(const NodeRec3
     if (active) {
         const double *r = points + 4 * i;
         p = d3{r[0], r[1], r[2]}; rmax = r[3];
-        double m = 0.0;
-        for (int k = 0; k < 6; ++k) m = fmax2(m, dabs(root_box[k]));
-        m = dmax_abs3(m, p);
-        pad = m * PROX_SLACK;
+        pad = dmax_abs3(root_max_abs(root_box), p) * PROX_SLACK;
     }
     double best = rmax, best2 = rmax * rmax;                             // the bound: min(rmax, the best candidate's dist), and its square
     uint32_t bface = POINT_NONE, bid = 0u, bfeat = 0u, bside = 0u;
     double bu = 0.0, bv = 0.0;
     d3 bq{0.0, 0.0, 0.0};
     uint32_t visits = 0, tests = 0;
-    float4 h0 = make_float4(0.f, 0.f, 0.f, 0.f), h1 = h0;
-    uint32_t end = 0, root = 0, cur = 0;
+    RecCursor w{}, seed{};                                               // the WALK's cursor; of `seed` only the step count is used (SEED's moves)
+    uint32_t root = 0, cur = 0;
     bool seeding = true;
     const bool leaf_only = n == 1;                                       // no records: leaf 0 is the whole tree
     if (active && !leaf_only) {
         root = (uint32_t)*root_name;
         cur = root;
-        if (!(root < (uint32_t)(n - 1))) active = false;                 // (no tree: nothing is read; nothing is found)
+        active = rec_internal((int32_t)root, n);                         // (no tree: nothing is read; nothing is found)
     }
-    uint32_t steps = 0;
     while (active) {
         bool test = leaf_only;
         uint32_t k = 0;
         if (!leaf_only) {
-            int32_t link;
-            bool enter;
             if (seeding) {                                               // the nearer child of `cur`, ties to the left
-                const float4 *l = rec_left(recs, n, cur), *r = rec_right(recs, n, cur);
-                const float4 l0 = l[0], l1 = l[1], r0 = r[0], r1 = r[1];
+                RecCursor l, r;
+                l.at_left(recs, n, cur); r.at_right(recs, n, cur);
                 visits += 2;
-                const bool right = pt_box2(r0, r1, p, pad) < pt_box2(l0, l1, p, pad);
-                link = (int32_t)__float_as_uint(right ? r1.z : l1.z);
-                enter = true;
-                if (link >= 0 && link < n - 1) {
-                    cur = (uint32_t)link;
-                    if (++steps > 2u * (uint32_t)n) break;               // (the bound only guards against a broken tree)
+                if (pt_box2(r.h0, r.h1, p, pad) < pt_box2(l.h0, l.h1, p, pad)) l = r;
+                if (l.internal(n)) {
+                    cur = (uint32_t)l.link();
+                    if (!seed.count(n)) break;                           // (the descent's own moves, up to n - 1, under the walk's rule)
                     continue;
                 }
+                if (l.leaf(n)) { test = true; k = l.leaf_index(); }
             } else {
                 ++visits;
-                enter = !(pt_box2(h0, h1, p, pad) > best2);              // CLOSED; a NaN enters
-                link = (int32_t)__float_as_uint(h1.z);
-                if (enter && link >= 0 && link < n - 1) {                // an internal node: on to its left child, which ends at its split
-                    const float4 *l = rec_left(recs, n, (uint32_t)link);
-                    h0 = l[0]; h1 = l[1];
-                    end = (uint32_t)link;
-                    if (++steps > 2u * (uint32_t)n) break;
+                const bool enter = !(pt_box2(w.h0, w.h1, p, pad) > best2);   // CLOSED; a NaN enters
+                if (enter && w.internal(n)) {
+                    if (!w.descend(recs, n)) break;
                     continue;
                 }
+                if (enter && w.leaf(n)) { test = true; k = w.leaf_index(); }
             }
-            if (enter && link < 0) { test = true; k = ~(uint32_t)link; }
         }
-        if (test && k < (uint32_t)n) {
+        if (test) {
             ++tests;
             const LeafTri lt = leaf[k];
             const PtTri r = pt_tri(p, load_vertex(verts, lt.v0), load_vertex(verts, lt.v1), load_vertex(verts, lt.v2));
@@ -120,18 +109,12 @@ __global__ __launch_bounds__(POINT_THREADS) void k_closest_points(const NodeRec3
             }
         }
         if (leaf_only) break;
-        if (seeding) {                                                   // the walk starts: the root's left child, which ends at the root's split
+        if (seeding) {                                                   // the walk starts at the root, with 2 n moves of its own
             seeding = false;
-            steps = 0;                                                   // (the walk's own 2 n: the descent took up to n - 1)
-            const float4 *l = rec_left(recs, n, root);
-            h0 = l[0]; h1 = l[1];
-            end = root;
+            w.start_root(recs, n, root);                                 // (true: the root was checked before the loop)
             continue;
         }
-        if (end >= (uint32_t)(n - 1) || ++steps > 2u * (uint32_t)n) break;
-        const float4 *r = rec_right(recs, n, end);                       // the next subtree in pre-order: the right child of the split at `end`
-        h0 = r[0]; h1 = r[1];
-        end = __float_as_uint(h1.w) & REC_LAST_MASK;
+        if (!w.next(recs, n)) break;
     }
     if (i < np) {
         const bool found = bface != POINT_NONE;
@@ -145,13 +128,7 @@ __global__ __launch_bounds__(POINT_THREADS) void k_closest_points(const NodeRec3
             if (side) side[i] = (uint8_t)(found ? bside : 0u);
         }
     }
-    const unsigned long long nf = wave_sum_u64(i < np && bface != POINT_NONE ? 1ull : 0ull);
-    const unsigned long long nv = wave_sum_u64(visits), nt = wave_sum_u64(tests);
-    if (threadIdx.x == 0) {
-        if (nf) atomicAdd(&st->n_found, nf);
-        if (nv) atomicAdd(&st->node_visits, nv);
-        if (nt) atomicAdd(&st->tri_tests, nt);
-    }
+    item_counters_add(i < np && bface != POINT_NONE, visits, tests, &st->n_found, &st->node_visits, &st->tri_tests);
 }
 
 // cd_pt_tri_points: pt_tri on explicit operands, n x 3 doubles (p) and n x 9 (p0, p1, p2)

@@ -1,16 +1,15 @@
 // cd_proximity.h -- self-proximity: every pair of triangles of the mesh with no shared vertex index and tri_distance <= dist
 // (cd_math.h), over the tree the collision path builds.  Not reference behaviour.
-//   k_prox_descend : fp32 filter.  One lane per query leaf j (sorted order), no stack: the leaves (j, n-1] are walked in
-//       pre-order through the split-named records (cd_bvh.h), starting at the right child of recs[j] (prox_walk, shared with the
-//       CCD and between-mesh descents).  A subtree that
-//       ends at leaf e and is done (missed, or a leaf) is followed by the right child of recs[e] -- the next subtree in
-//       pre-order -- until e == n-1.  Nothing is pushed, so no depth can overflow anything.  Every stored box is taken as
-//       [lo, f32_next_up(hi)] (the records keep hi ROUNDED DOWN unless its cell is ambiguous: an upper bound only after the
-//       step; a stored +inf stays +inf, prox_hi), the query box is widened by d_pad with directed rounding, and boxes that
-//       touch count (closed intervals).
+//   k_prox_descend : fp32 filter.  One lane per query leaf j (sorted order) walks the leaves (j, n-1] with the queries' stackless
+//       pre-order walk (RecCursor, cd_bvh.h: the walk, its step bound and its guards are described there), started behind leaf j.
+//       The loop around the cursor and its candidate queue are prox_walk, shared with the CCD and between-mesh descents.  Every
+//       stored box is taken as [lo, f32_next_up(hi)] (the records keep hi ROUNDED DOWN unless its cell is ambiguous: an upper bound
+//       only after the step; a stored +inf stays +inf, prox_hi), the query box is widened by d_pad with directed rounding
+//       (QueryBox32), and boxes that touch count (closed intervals).
 //       Candidates (j, k) go through a wave-shared LDS queue to the workgroup's shard of a global buffer, 64 at a time.
 //   k_prox_exact   : FP64.  Neighbour filter (collision.cuh:38), tri_distance, append (min ID, max ID) + distance with one
-//       atomic per workgroup and round.
+//       atomic per workgroup and round.  The shard slice, the append and the counter sums around the predicate are the exact
+//       stage's scaffold below (ShardSlice, pair_append, group_counters_add), shared with k_ccd_exact and k_between_exact.
 // The filter is conservative: d_pad = dist + dist 2^-20 + M 2^-20 (M the largest |coordinate| of the root box), far above
 // tri_distance's rounding error (tests/test_proximity_ref.py bounds it), so every pair whose FP64 distance is <= dist is a
 // candidate, and the FP64 test alone decides.  A shard that overflows is detected from its counter (nothing is written past
@@ -43,51 +42,59 @@ __device__ __forceinline__ float prox_hi(float hi)
     return __float_as_uint(hi) == 0x7f800000u ? hi : f32_next_up(hi);
 }
 
-__device__ __forceinline__ float prox_pad(const double *__restrict__ root_box, double dist)
+// the largest |coordinate| of the root box: the M of every query's pad
+__device__ __forceinline__ double root_max_abs(const double *__restrict__ root_box)
 {
     double m = 0.0;
     for (int i = 0; i < 6; ++i) m = fmax2(m, dabs(root_box[i]));
-    return __double2float_ru(dist + dist * PROX_SLACK + m * PROX_SLACK);
+    return m;
+}
+__device__ __forceinline__ float prox_pad(const double *__restrict__ root_box, double dist)
+{
+    return __double2float_ru(dist + dist * PROX_SLACK + root_max_abs(root_box) * PROX_SLACK);
 }
 
 // How a walk reads a stored hi: the static records' as an upper bound (prox_hi), the swept records' as they are (true bounds).
 struct HiNextUp { __device__ static __forceinline__ float hi(float h) { return prox_hi(h); } };
 struct HiTrue { __device__ static __forceinline__ float hi(float h) { return h; } };
 
-// The stackless pre-order walk and its candidate queue, written once (k_prox_descend, k_ccd_descend, k_between_descend).  A lane starts
-// at the subtree (h0, h1) -- a record half -- whose last leaf is `end`, and walks every subtree after it in pre-order up to leaf n-1: an
-// internal node that overlaps goes on to its left child (which ends at its split); a subtree that is done (missed, or a leaf) is
-// followed by the right child of the split at `end`, until end == n-1.  The query box (ql*, qh*) meets [lo, Hi::hi(hi)] closed.
-// Leaf hits (j, k) go through a wave-shared LDS queue to `shard`, 64 at a time (nothing is written past shard_cap; *ctr counts all).
+// The pair queries' fp32 query box: an FP64 box widened by `pad` with directed rounding (lo down, hi up, at every step), and its closed overlap
+// with the subtree a walk is at, whose box is [lo, Hi::hi(hi)].  (All zeros for a lane with no query.)
+struct QueryBox32 {
+    float lx, ly, lz, hx, hy, hz;
+    template <class Hi> __device__ __forceinline__ bool meets(const RecCursor &w) const
+    {
+        return lx <= Hi::hi(w.h0.w) && w.h0.x <= hx && ly <= Hi::hi(w.h1.x) && w.h0.y <= hy && lz <= Hi::hi(w.h1.y) && w.h0.z <= hz;
+    }
+};
+__device__ __forceinline__ QueryBox32 query_box32(const Box &b, float pad)
+{
+    return QueryBox32{__ocml_sub_rtn_f32(__double2float_rd(b.x1), pad), __ocml_sub_rtn_f32(__double2float_rd(b.y1), pad), __ocml_sub_rtn_f32(__double2float_rd(b.z1), pad),
+                      __ocml_add_rtp_f32(__double2float_ru(b.x2), pad), __ocml_add_rtp_f32(__double2float_ru(b.y2), pad), __ocml_add_rtp_f32(__double2float_ru(b.z2), pad)};
+}
+
+// The pair queries' descent, written once (k_prox_descend, k_ccd_descend, k_between_descend): the walk of cd_bvh.h from where the caller
+// started the cursor `w`, entering every subtree whose box the query box `q` meets, and its candidate queue.  Leaf hits (j, k) go through a
+// wave-shared LDS queue to the workgroup's shard of `cand`, 64 at a time (nothing is written past shard_cap; the shard's counter counts all).
 // One wave per workgroup; every lane of it calls this (inactive lanes with active = false).
 template <class Hi>
-__device__ __forceinline__ void prox_walk(const NodeRec32 *__restrict__ recs, int n, uint32_t j, bool active, float4 h0, float4 h1, uint32_t end,
-                                          float qlx, float qly, float qlz, float qhx, float qhy, float qhz,
-                                          unsigned long long *__restrict__ ctr, uint2 *__restrict__ shard, unsigned long long shard_cap)
+__device__ __forceinline__ void prox_walk(const NodeRec32 *__restrict__ recs, int n, uint32_t j, bool active, RecCursor w, const QueryBox32 q,
+                                          unsigned long long *__restrict__ shard_ctr /* ProxState / CcdState ::shard */, uint2 *__restrict__ cand, unsigned long long shard_cap)
 {
     __shared__ uint2 queue[PROX_QCAP];
+    unsigned long long *ctr = &shard_ctr[(blockIdx.x & (NSHARD - 1)) * PROX_SHARD_STRIDE];
+    uint2 *shard = cand + (size_t)(blockIdx.x & (NSHARD - 1)) * shard_cap;
     const uint32_t lane = threadIdx.x;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     uint32_t qn = 0;                                                     // (wave-uniform)
-    uint32_t steps = 0;
     while (__ballot(active) != 0ull) {
         bool hit = false; uint32_t k = 0;
         if (active) {
-            // closed overlap of the widened query box with [lo, Hi::hi(hi)]
-            const bool ov = qlx <= Hi::hi(h0.w) && h0.x <= qhx && qly <= Hi::hi(h1.x) && h0.y <= qhy && qlz <= Hi::hi(h1.y) && h0.z <= qhz;
-            const int32_t link = (int32_t)__float_as_uint(h1.z);
-            if (ov && link >= 0) {                                       // an internal node: on to its left child, which ends at its split
-                const float4 *l = rec_left(recs, n, (uint32_t)link);
-                h0 = l[0]; h1 = l[1];
-                end = (uint32_t)link;
-            } else {
-                if (ov) { hit = true; k = ~(uint32_t)link; }
-                if (end >= (uint32_t)(n - 1) || ++steps > 2u * (uint32_t)n) active = false;   // (the bound only guards against a broken tree)
-                else {                                                   // the next subtree in pre-order: the right child of the split at `end`
-                    const float4 *r = rec_right(recs, n, end);
-                    h0 = r[0]; h1 = r[1];
-                    end = __float_as_uint(h1.w) & REC_LAST_MASK;
-                }
+            const bool ov = q.meets<Hi>(w);
+            if (ov && w.internal(n)) active = w.descend(recs, n);
+            else {
+                if (ov && w.leaf(n)) { hit = true; k = w.leaf_index(); }
+                active = w.next(recs, n);
             }
         }
         const unsigned long long bal = __ballot(hit);
@@ -117,27 +124,75 @@ __global__ __launch_bounds__(PROX_DESC_THREADS) void k_prox_descend(const NodeRe
                                                                     const uint32_t *__restrict__ sort_flags /* 9 words */, ProxState *__restrict__ st,
                                                                     uint2 *__restrict__ cand, unsigned long long shard_cap)
 {
-    uint32_t bad = 0;
-    for (int i = 0; i < 9; ++i) bad |= sort_flags[i];
-    if (bad) return;                                                     // the sort failed: the records are not a tree (the host redoes the build)
+    if (sort_failed(sort_flags)) return;                                 // the records are not a tree (the host redoes the build)
     const uint32_t j = blockIdx.x * PROX_DESC_THREADS + threadIdx.x;
-    unsigned long long *ctr = &st->shard[(blockIdx.x & (NSHARD - 1)) * PROX_SHARD_STRIDE];
-    uint2 *shard = cand + (size_t)(blockIdx.x & (NSHARD - 1)) * shard_cap;
     const float pad = prox_pad(root_box, dist);
-    bool active = (int)j < n - 1;
-    float qlx = 0.f, qly = 0.f, qlz = 0.f, qhx = 0.f, qhy = 0.f, qhz = 0.f;
-    float4 h0 = make_float4(0.f, 0.f, 0.f, 0.f), h1 = h0;                // the subtree at hand: its box and link, as a record half holds them
-    uint32_t end = 0;                                                    // its last leaf
+    const bool active = (int)j < n - 1;
+    QueryBox32 q{};
+    RecCursor w{};
     if (active) {
         const LeafTri lt = leaf[j];
-        const Box b = box_set(load_vertex(verts, lt.v0), load_vertex(verts, lt.v1), load_vertex(verts, lt.v2));
-        qlx = __ocml_sub_rtn_f32(__double2float_rd(b.x1), pad); qly = __ocml_sub_rtn_f32(__double2float_rd(b.y1), pad); qlz = __ocml_sub_rtn_f32(__double2float_rd(b.z1), pad);
-        qhx = __ocml_add_rtp_f32(__double2float_ru(b.x2), pad); qhy = __ocml_add_rtp_f32(__double2float_ru(b.y2), pad); qhz = __ocml_add_rtp_f32(__double2float_ru(b.z2), pad);
-        const float4 *r = rec_right(recs, n, j);                         // the walk starts at the right child of recs[j]
-        h0 = r[0]; h1 = r[1];
-        end = __float_as_uint(h1.w) & REC_LAST_MASK;
+        q = query_box32(box_set(load_vertex(verts, lt.v0), load_vertex(verts, lt.v1), load_vertex(verts, lt.v2)), pad);
+        w.start_behind(recs, n, j);
     }
-    prox_walk<HiNextUp>(recs, n, j, active, h0, h1, end, qlx, qly, qlz, qhx, qhy, qhz, ctr, shard, shard_cap);
+    prox_walk<HiNextUp>(recs, n, j, active, w, q, st->shard, cand, shard_cap);
+}
+
+// ---------------------------------------------------------------- the exact stage's scaffold
+// What k_prox_exact, k_ccd_exact and k_between_exact share around their predicates (a workgroup of PROX_EXACT_THREADS, blockIdx.y = the shard).
+// The slice of the candidates the workgroup takes: its shard's list, and the rounds of one candidate per thread, grid-stride.
+struct ShardSlice {
+    const uint2 *list; unsigned long long total;
+    __device__ __forceinline__ ShardSlice(const unsigned long long *__restrict__ shard_ctr, const uint2 *__restrict__ cand, unsigned long long shard_cap)
+    {
+        const unsigned long long reserved = shard_ctr[blockIdx.y * PROX_SHARD_STRIDE];
+        total = reserved < shard_cap ? reserved : shard_cap;             // (a shard that overflowed holds its capacity; the host sees the counter)
+        list = cand + (size_t)blockIdx.y * shard_cap;
+    }
+    __device__ __forceinline__ unsigned long long first() const { return (unsigned long long)blockIdx.x * PROX_EXACT_THREADS; }
+    __device__ __forceinline__ unsigned long long stride() const { return (unsigned long long)gridDim.x * PROX_EXACT_THREADS; }
+};
+// A round's append: a thread with a hit gets its output slot `at` and, if at < cap, stores its pair there (store(at)); slots at or beyond
+// the caller's capacity are counted and not written.  One atomic on *n_pairs per workgroup and round.  Every thread of the workgroup
+// calls this, once a round.
+template <class Store>
+__device__ __forceinline__ void pair_append(bool hit, unsigned long long *__restrict__ n_pairs, unsigned long long cap, Store store)
+{
+    __shared__ uint32_t s_cnt;
+    __shared__ unsigned long long s_base;
+    if (threadIdx.x == 0) s_cnt = 0u;
+    __syncthreads();
+    const uint32_t slot = hit ? atomicAdd(&s_cnt, 1u) : 0u;
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt) s_base = atomicAdd(n_pairs, (unsigned long long)s_cnt);
+    __syncthreads();
+    if (hit) {
+        const unsigned long long at = s_base + slot;
+        if (at < cap) store(at);
+    }
+    __syncthreads();                                                     // (s_cnt / s_base are reused by the next round)
+}
+// The workgroup's sums of K per-thread counts v[0 .. K-1], added to the counters c0, c1, c2 (the first K of them) with one atomic per
+// non-zero sum.
+template <int K>
+__device__ __forceinline__ void group_counters_add(const unsigned long long *v, unsigned long long *__restrict__ c0,
+                                                   unsigned long long *__restrict__ c1 = nullptr, unsigned long long *__restrict__ c2 = nullptr)
+{
+    __shared__ unsigned long long s_sum[K][PROX_EXACT_THREADS / 64];
+    const uint32_t tid = threadIdx.x;
+    unsigned long long t[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) t[k] = wave_sum_u64(v[k]);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) s_sum[k][tid >> 6] = t[k];
+    }
+    __syncthreads();
+    if (tid < K) {
+        unsigned long long sum = 0;
+        for (int w = 0; w < PROX_EXACT_THREADS / 64; ++w) sum += s_sum[tid][w];
+        if (sum) atomicAdd(tid == 0 ? c0 : (tid == 1 ? c1 : c2), sum);
+    }
 }
 
 __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_prox_exact(const uint2 *__restrict__ cand, unsigned long long shard_cap, const LeafTri *__restrict__ leaf,
@@ -145,20 +200,14 @@ __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_prox_exact(const uint2 *
                                                                   ProxState *__restrict__ st, uint32_t *__restrict__ pairs, double *__restrict__ dists,
                                                                   unsigned long long cap)
 {
-    __shared__ uint32_t s_cnt;
-    __shared__ unsigned long long s_base;
-    __shared__ unsigned long long s_tested[PROX_EXACT_THREADS / 64];
-    const uint32_t tid = threadIdx.x, sh = blockIdx.y;
-    const unsigned long long reserved = st->shard[sh * PROX_SHARD_STRIDE];
-    const unsigned long long total = reserved < shard_cap ? reserved : shard_cap;
-    const uint2 *list = cand + (size_t)sh * shard_cap;
+    const ShardSlice sl(st->shard, cand, shard_cap);
     unsigned long long tested = 0;
-    for (unsigned long long b0 = (unsigned long long)blockIdx.x * PROX_EXACT_THREADS; b0 < total; b0 += (unsigned long long)gridDim.x * PROX_EXACT_THREADS) {
-        const unsigned long long i = b0 + tid;
+    for (unsigned long long b0 = sl.first(); b0 < sl.total; b0 += sl.stride()) {
+        const unsigned long long i = b0 + threadIdx.x;
         bool hit = false;
         uint32_t ida = 0, idb = 0; double d = 0.0;
-        if (i < total) {
-            const uint2 c = list[i];
+        if (i < sl.total) {
+            const uint2 c = sl.list[i];
             LeafTri A = leaf[c.x], B = leaf[c.y];
             if (neighbor_count(A.v0, A.v1, A.v2, B.v0, B.v1, B.v2) < 1) {                 // collision.cuh:38
                 ++tested;
@@ -169,26 +218,9 @@ __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_prox_exact(const uint2 *
                 ida = A.id; idb = B.id;
             }
         }
-        if (tid == 0) s_cnt = 0u;
-        __syncthreads();
-        const uint32_t slot = hit ? atomicAdd(&s_cnt, 1u) : 0u;
-        __syncthreads();
-        if (tid == 0 && s_cnt) s_base = atomicAdd(&st->n_pairs, (unsigned long long)s_cnt);
-        __syncthreads();
-        if (hit) {
-            const unsigned long long at = s_base + slot;
-            if (at < cap) { pairs[2 * at] = ida; pairs[2 * at + 1] = idb; dists[at] = d; }
-        }
-        __syncthreads();                                                 // (s_cnt / s_base are reused by the next round)
+        pair_append(hit, &st->n_pairs, cap, [&](unsigned long long at) { pairs[2 * at] = ida; pairs[2 * at + 1] = idb; dists[at] = d; });
     }
-    tested = wave_sum_u64(tested);
-    if ((tid & 63) == 0) s_tested[tid >> 6] = tested;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < PROX_EXACT_THREADS / 64; ++w) t += s_tested[w];
-        if (t) atomicAdd(&st->n_tested, t);
-    }
+    group_counters_add<1>(&tested, &st->n_tested);
 }
 
 // cd_tri_distance_points: tri_distance on explicit positions, n x 18 doubles (A's three vertices, then B's)

@@ -1,9 +1,8 @@
 // cd_rays.h -- ray queries against the mesh: closest hit and occlusion.  Not reference behaviour.
 //   k_cast_rays<ANY>  : one lane per ray, in the order given (neighbouring rays share a wave: coherent rays should be neighbours).
-//       The lane walks the split-named records in pre-order from the ROOT, with no stack, as k_between_descend does: an internal node
-//       whose box the ray meets goes on to its left child (which ends at its split); a subtree that is done (missed, or a leaf) is
-//       followed by the right child of the split at its last leaf, until that leaf is n-1.  Nothing is pushed, so no depth can
-//       overflow anything; n == 1 has no records and every lane tests leaf 0.
+//       The lane walks the records from the ROOT with the queries' stackless pre-order walk (RecCursor, cd_bvh.h: the walk, its
+//       step bound and its guards are described there), entering the boxes the ray meets; n == 1 has no records and every lane
+//       tests leaf 0.
 //       At a leaf the exact FP64 test ray_tri (cd_math.h) runs INLINE -- the ray's upper end shrinks with every hit, so a candidate
 //       queue would only carry boxes the next hit makes pointless.  Closest hit: the smallest (t, triangle ID, face index) wins, and a
 //       subtree is skipped when its box is missed over [0, t_best], CLOSED, so that a triangle at the same t with a smaller ID is
@@ -48,6 +47,19 @@ __device__ __forceinline__ bool ray_box(const float4 h0, const float4 h1, const 
     return ok && tn <= tf;
 }
 
+// The per-item queries' counters (RayState, PointState: items answered, boxes visited, triangles tested): the wave's sums, one
+// atomic per non-zero sum.  One wave per workgroup; every lane calls this.
+__device__ __forceinline__ void item_counters_add(bool got, uint32_t visits, uint32_t tests, unsigned long long *__restrict__ n_got,
+                                                  unsigned long long *__restrict__ node_visits, unsigned long long *__restrict__ tri_tests)
+{
+    const unsigned long long ng = wave_sum_u64(got ? 1ull : 0ull), nv = wave_sum_u64(visits), nt = wave_sum_u64(tests);
+    if (threadIdx.x == 0) {
+        if (ng) atomicAdd(n_got, ng);
+        if (nv) atomicAdd(node_visits, nv);
+        if (nt) atomicAdd(tri_tests, nt);
+    }
+}
+
 template <bool ANY>
 __global__ __launch_bounds__(RAY_THREADS) void k_cast_rays(const NodeRec32 *__restrict__ recs, const int32_t *__restrict__ root_name, const LeafTri *__restrict__ leaf,
                                                            const uint32_t *__restrict__ perm, const double *__restrict__ verts, const double *__restrict__ root_box, int n,
@@ -62,46 +74,27 @@ __global__ __launch_bounds__(RAY_THREADS) void k_cast_rays(const NodeRec32 *__re
     if (active) {
         const double *r = rays + 7 * i;
         o = d3{r[0], r[1], r[2]}; d = d3{r[3], r[4], r[5]}; tbest = r[6];
-        double m = 0.0;
-        for (int k = 0; k < 6; ++k) m = fmax2(m, dabs(root_box[k]));
-        m = dmax_abs3(m, o);
-        pad = m * PROX_SLACK;
+        pad = dmax_abs3(root_max_abs(root_box), o) * PROX_SLACK;
     }
     uint32_t bface = RAY_MISS, bid = 0u, bside = 0u;
     double bu = 0.0, bv = 0.0;
     uint32_t visits = 0, tests = 0;
-    float4 h0 = make_float4(0.f, 0.f, 0.f, 0.f), h1 = h0;
-    uint32_t end = 0;
-    bool leaf_only = false;                                              // n == 1: no records, leaf 0 is the whole tree
-    if (active) {
-        if (n == 1) leaf_only = true;
-        else {
-            const uint32_t root = (uint32_t)*root_name;
-            if (root < (uint32_t)(n - 1)) {                              // the root's left child, which ends at the root's split
-                const float4 *l = rec_left(recs, n, root);
-                h0 = l[0]; h1 = l[1];
-                end = root;
-            } else active = false;                                       // (no tree: nothing is read; the ray misses)
-        }
-    }
-    uint32_t steps = 0;
+    RecCursor w{};
+    const bool leaf_only = n == 1;                                       // no records: leaf 0 is the whole tree
+    if (active && !leaf_only) active = w.start_root(recs, n, (uint32_t)*root_name);   // (no tree: nothing is read; the ray misses)
     while (active) {
         bool test = leaf_only;
         uint32_t k = 0;
         if (!leaf_only) {
             ++visits;
-            const bool ov = ray_box(h0, h1, o, d, pad, tbest);
-            const int32_t link = (int32_t)__float_as_uint(h1.z);
-            if (ov && link >= 0 && link < n - 1) {                       // an internal node: on to its left child, which ends at its split
-                const float4 *l = rec_left(recs, n, (uint32_t)link);
-                h0 = l[0]; h1 = l[1];
-                end = (uint32_t)link;
-                if (++steps > 2u * (uint32_t)n) break;                   // (the bound only guards against a broken tree)
+            const bool ov = ray_box(w.h0, w.h1, o, d, pad, tbest);
+            if (ov && w.internal(n)) {
+                if (!w.descend(recs, n)) break;
                 continue;
             }
-            if (ov && link < 0) { test = true; k = ~(uint32_t)link; }
+            if (ov && w.leaf(n)) { test = true; k = w.leaf_index(); }
         }
-        if (test && k < (uint32_t)n) {
+        if (test) {
             ++tests;
             const LeafTri lt = leaf[k];
             const RayHit h = ray_tri(o, d, tbest, load_vertex(verts, lt.v0), load_vertex(verts, lt.v1), load_vertex(verts, lt.v2));
@@ -114,10 +107,7 @@ __global__ __launch_bounds__(RAY_THREADS) void k_cast_rays(const NodeRec32 *__re
                 }
             }
         }
-        if (leaf_only || end >= (uint32_t)(n - 1) || ++steps > 2u * (uint32_t)n) break;   // (the bound only guards against a broken tree)
-        const float4 *r = rec_right(recs, n, end);                       // the next subtree in pre-order: the right child of the split at `end`
-        h0 = r[0]; h1 = r[1];
-        end = __float_as_uint(h1.w) & REC_LAST_MASK;
+        if (leaf_only || !w.next(recs, n)) break;
     }
     if (i < nr) {
         const bool hit = bface != RAY_MISS;
@@ -129,13 +119,7 @@ __global__ __launch_bounds__(RAY_THREADS) void k_cast_rays(const NodeRec32 *__re
             if (side) side[i] = (uint8_t)(hit ? bside : 0u);
         }
     }
-    const unsigned long long nh = wave_sum_u64(i < nr && bface != RAY_MISS ? 1ull : 0ull);
-    const unsigned long long nv = wave_sum_u64(visits), nt = wave_sum_u64(tests);
-    if (threadIdx.x == 0) {
-        if (nh) atomicAdd(&st->n_hits, nh);
-        if (nv) atomicAdd(&st->node_visits, nv);
-        if (nt) atomicAdd(&st->tri_tests, nt);
-    }
+    item_counters_add(i < nr && bface != RAY_MISS, visits, tests, &st->n_hits, &st->node_visits, &st->tri_tests);
 }
 
 // cd_ray_tri_points: ray_tri on explicit operands, n x 7 doubles (o, d, tmax) and n x 9 (p0, p1, p2)

@@ -138,6 +138,13 @@ __device__ __forceinline__ bool sort_failed(const QuerySrc &src)
     for (int i = 0; i < 9; ++i) any |= src.sort_flags[i];
     return any != 0;
 }
+// the same on the context's 9 flag words themselves: what the queries' kernels (cd_proximity.h and the headers after it) start with
+__device__ __forceinline__ bool sort_failed(const uint32_t *__restrict__ sort_flags)
+{
+    uint32_t bad = 0;
+    for (int i = 0; i < 9; ++i) bad |= sort_flags[i];
+    return bad != 0u;
+}
 
 struct ExtQuery { double v[9]; uint32_t id; uint32_t vidx[3]; };
 static_assert(sizeof(ExtQuery) == 88, "cd_query layout");

@@ -362,6 +362,29 @@ def test_the_walk_prunes():
     assert info.tri_tests <= n * nt // 100
 
 
+@pytest.mark.parametrize("n", [2, 3, 65])
+def test_a_walk_that_must_visit_every_node(n):
+    """n coincident triangles, each on vertices of its own, default IDs: all boxes of the tree are one box, so a point that enters
+    one subtree enters all.  Nearest-triangle queries above the interior with rmax = +inf: the seed descent looks at both children
+    of D nodes (ties to the left: the same path, of depth D, for every point) and tests its leaf; the walk's bound is then the
+    common distance, the box test is closed at it, so the walk visits every node but the root once -- 2 n - 2 boxes, the most a
+    walk over a tree makes -- and tests all n triangles, the seed leaf a second time.  Every point reports the smallest ID."""
+    v = np.tile(np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), (n, 1))
+    i = np.arange(3 * n, dtype=np.uint32).reshape(n, 3)
+    g = np.linspace(0.125, 0.375, 8)
+    pts = np.array([[x, y, 0.5] for x in g for y in g])
+    p = pts.shape[0]
+    with _ctx(v, i) as cd:
+        got = cd.closest_points(pts)
+    face, ids, dist, info = got[0], got[1], got[2], got[7]
+    print(f"{n} coincident triangles, {p} points: {info.node_visits / p:.1f} boxes and {info.tri_tests / p:.2f} pt_tri a point")
+    assert (face == 0).all() and (ids == 0).all() and (dist == 0.5).all() and info.n_found == p
+    assert info.tri_tests == p * (n + 1)
+    seed = info.node_visits - p * (2 * n - 2)                                   # 2 D boxes a point
+    assert seed % (2 * p) == 0 and 1 <= seed // (2 * p) <= n - 1, (info.node_visits, seed)
+    assert n != 2 or seed == 2 * p
+
+
 def test_project_one_cloth_sheet_onto_the_other():
     """The usage the query is for: every vertex of one sheet of cloth_pair(100) projected onto the other sheet's mesh (two contexts,
     one per sheet), against the restatement."""

@@ -116,6 +116,25 @@ def test_closest_hit_on_large_meshes_against_all_pairs(name):
     assert int((got[0] != MISS).sum()) > NRAYS // 8
 
 
+@pytest.mark.parametrize("n", [2, 3, 65])
+def test_a_walk_that_must_visit_every_node(n):
+    """n coincident triangles, each on vertices of its own, default IDs: all boxes of the tree are one box, so a ray that enters one
+    subtree enters all.  Closest-hit rays straight down through the interior: every triangle is hit at the same t, the box test is
+    closed at t_best, so every ray tests all n triangles, visits every node but the root once -- 2 n - 2 boxes, the most a walk over
+    a tree makes -- and reports the smallest ID."""
+    v = np.tile(np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), (n, 1))
+    i = np.arange(3 * n, dtype=np.uint32).reshape(n, 3)
+    g = np.linspace(0.125, 0.375, 8)
+    o = np.array([[x, y, 1.0] for x in g for y in g])
+    r = o.shape[0]
+    with _ctx(v, i) as cd:
+        face, ids, t, uv, side, info = cd.cast_rays(o, np.tile([0.0, 0.0, -1.0], (r, 1)))
+    print(f"{n} coincident triangles, {r} rays: {info.node_visits / r:.1f} boxes and {info.tri_tests / r:.2f} ray_tri a ray")
+    assert (face == 0).all() and (ids == 0).all() and (t == 1.0).all() and info.n_hits == r
+    assert info.tri_tests == r * n
+    assert info.node_visits == r * (2 * n - 2)
+
+
 def _frame(cd, mode):
     if mode == mi355cd.CD_FRAME_CUSTOM:
         cd.set_morton_frame(mode, np.array([-0.3, -0.2, -0.25]), np.array([1.7, 1.5, 1.6]))
