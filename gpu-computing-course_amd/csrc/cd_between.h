@@ -84,12 +84,13 @@ __global__ __launch_bounds__(PROX_DESC_THREADS) void k_between_descend(const Nod
     else prox_walk<HiNextUp>(recs_b, nb, j, active, w, q, st->shard, cand, shard_cap);
 }
 
-template <int KIND>
+template <int KIND, bool WIT>                          // (WIT, the witness calls: wleaf[at] = (leaf of a, leaf of b) of the hit, as k_prox_exact)
 __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_between_exact(const uint2 *__restrict__ cand, unsigned long long shard_cap,
                                                                      const LeafTri *__restrict__ leaf_a, const double *__restrict__ ax0, const double *__restrict__ ax1,
                                                                      const LeafTri *__restrict__ leaf_b, const double *__restrict__ bx0, const double *__restrict__ bx1,
                                                                      double dist, CcdState *__restrict__ st, uint32_t *__restrict__ pairs,
-                                                                     double *__restrict__ toi_out, double *__restrict__ dists, unsigned long long cap)
+                                                                     double *__restrict__ toi_out, double *__restrict__ dists, unsigned long long cap,
+                                                                     uint2 *__restrict__ wleaf)
 {
     const ShardSlice sl(st->shard, cand, shard_cap);
     unsigned long long sums[3] = {0, 0, 0};                              // tested, evals, unresolved: CcdState's order
@@ -97,9 +98,11 @@ __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_between_exact(const uint
         const unsigned long long i = b0 + threadIdx.x;
         bool hit = false;
         uint32_t ida = 0, idb = 0; double toi = 0.0, d = 0.0;
+        uint2 lv = make_uint2(0u, 0u);
         if (i < sl.total) {
             const uint2 c = sl.list[i];
             const LeafTri A = leaf_a[c.x], B = leaf_b[c.y];
+            lv = c;
             ida = A.id; idb = B.id;
             if (KIND == BW_CONTACT) {
                 const d3 P1 = load_vertex(ax0, A.v0), P2 = load_vertex(ax0, A.v1), P3 = load_vertex(ax0, A.v2);
@@ -129,6 +132,7 @@ __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_between_exact(const uint
             pairs[2 * at] = ida; pairs[2 * at + 1] = idb;
             if (KIND == BW_PROXIMITY) dists[at] = d;
             if (KIND == BW_CCD) { toi_out[at] = toi; dists[at] = d; }
+            if (WIT) wleaf[at] = lv;
         });
     }
     group_counters_add<KIND == BW_CCD ? 3 : 1>(sums, &st->n_tested, &st->n_evals, &st->n_unresolved);     // (only CCD counts evaluations and unresolved pairs)

@@ -210,10 +210,11 @@ __global__ __launch_bounds__(PROX_DESC_THREADS) void k_ccd_descend(const NodeRec
     prox_walk<HiTrue>(recs, n, j, active, w, q, st->shard, cand, shard_cap);
 }
 
+template <bool WIT>                                    // (the witness calls: wleaf[at] = the hit's leaf positions, A's first, as k_prox_exact)
 __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_ccd_exact(const uint2 *__restrict__ cand, unsigned long long shard_cap, const LeafTri *__restrict__ leaf,
                                                                  const uint32_t *__restrict__ perm, const double *__restrict__ x0, const double *__restrict__ x1,
                                                                  double dist, CcdState *__restrict__ st, uint32_t *__restrict__ pairs, double *__restrict__ toi_out,
-                                                                 double *__restrict__ dists, unsigned long long cap)
+                                                                 double *__restrict__ dists, unsigned long long cap, uint2 *__restrict__ wleaf)
 {
     const ShardSlice sl(st->shard, cand, shard_cap);
     unsigned long long sums[3] = {0, 0, 0};                              // tested, evals, unresolved: CcdState's order
@@ -221,11 +222,13 @@ __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_ccd_exact(const uint2 *_
         const unsigned long long i = b0 + threadIdx.x;
         bool hit = false;
         uint32_t ida = 0, idb = 0; double toi = 0.0, d = 0.0;
+        uint2 lv = make_uint2(0u, 0u);
         if (i < sl.total) {
             const uint2 c = sl.list[i];
             LeafTri A = leaf[c.x], B = leaf[c.y];
+            lv = c;
             if (neighbor_count(A.v0, A.v1, A.v2, B.v0, B.v1, B.v2) < 1) {                 // collision.cuh:38
-                if (B.id < A.id || (B.id == A.id && perm[c.y] < perm[c.x])) { const LeafTri t = A; A = B; B = t; }   // A: the smaller ID (then face index)
+                if (B.id < A.id || (B.id == A.id && perm[c.y] < perm[c.x])) { const LeafTri t = A; A = B; B = t; lv = make_uint2(c.y, c.x); }   // A: the smaller ID (then face index)
                 const CcdMeshSrc src{x0, x1, A.v0, A.v1, A.v2, B.v0, B.v1, B.v2};
                 if (ccd_gate(src, dist)) {
                     ++sums[0];
@@ -238,7 +241,7 @@ __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_ccd_exact(const uint2 *_
                 }
             }
         }
-        pair_append(hit, &st->n_pairs, cap, [&](unsigned long long at) { pairs[2 * at] = ida; pairs[2 * at + 1] = idb; toi_out[at] = toi; dists[at] = d; });
+        pair_append(hit, &st->n_pairs, cap, [&](unsigned long long at) { pairs[2 * at] = ida; pairs[2 * at + 1] = idb; toi_out[at] = toi; dists[at] = d; if (WIT) wleaf[at] = lv; });
     }
     group_counters_add<3>(sums, &st->n_tested, &st->n_evals, &st->n_unresolved);
 }

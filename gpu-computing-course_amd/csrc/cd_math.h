@@ -222,19 +222,22 @@ __device__ __forceinline__ double pt_face2_vw(const d3 p, const d3 a, const d3 b
 }
 __device__ __forceinline__ double pt_face2(const d3 p, const d3 a, const d3 b, const d3 c) { double v, w; return pt_face2_vw(p, a, b, c, v, w); }
 // squared distance between the segments [p1, q1], [p2, q2] at their interior critical point when it lies on both, else +inf
-// (the endpoints' terms are pt_seg2's)
-__device__ __forceinline__ double seg_seg2(const d3 p1, const d3 q1, const d3 p2, const d3 q2)
+// (the endpoints' terms are pt_seg2's); s, t: the parameters of the two points p1 + s (q1 - p1), p2 + t (q2 - p2) (0 with +inf)
+__device__ __forceinline__ double seg_seg2_st(const d3 p1, const d3 q1, const d3 p2, const d3 q2, double &s, double &t)
 {
+    s = 0.0; t = 0.0;
     const d3 d1 = sub(q1, p1), d2 = sub(q2, p2), r = sub(p1, p2);
     const double a = dot(d1, d1), e = dot(d2, d2), b = dot(d1, d2), c = dot(d1, r), f = dot(d2, r);
     const double den = a * e - b * b;
     if (!(den > 0.0)) return __builtin_inf();
-    const double s = (b * f - c * e) / den, t = (a * f - b * c) / den;
-    if (!(s >= 0.0 && s <= 1.0 && t >= 0.0 && t <= 1.0)) return __builtin_inf();
-    const d3 P = d3{p1.x + s * d1.x, p1.y + s * d1.y, p1.z + s * d1.z}, Q = d3{p2.x + t * d2.x, p2.y + t * d2.y, p2.z + t * d2.z};
+    const double fs = (b * f - c * e) / den, ft = (a * f - b * c) / den;
+    if (!(fs >= 0.0 && fs <= 1.0 && ft >= 0.0 && ft <= 1.0)) return __builtin_inf();
+    const d3 P = d3{p1.x + fs * d1.x, p1.y + fs * d1.y, p1.z + fs * d1.z}, Q = d3{p2.x + ft * d2.x, p2.y + ft * d2.y, p2.z + ft * d2.z};
     const d3 d = sub(P, Q);
+    s = fs; t = ft;
     return dot(d, d);
 }
+__device__ __forceinline__ double seg_seg2(const d3 p1, const d3 q1, const d3 p2, const d3 q2) { double s, t; return seg_seg2_st(p1, q1, p2, q2, s, t); }
 constexpr int TRI_DIST_EXP_MAX = 1000;                  // |scale exponent| clamp: 2^+-1000 are normal numbers
 __device__ __forceinline__ double dabs(double x) { return x < 0.0 ? -x : x; }
 __device__ __forceinline__ double dmax_abs3(double m, const d3 v) { m = fmax2(m, dabs(v.x)); m = fmax2(m, dabs(v.y)); return fmax2(m, dabs(v.z)); }
@@ -265,6 +268,90 @@ __device__ inline double tri_distance(const d3 P1, const d3 P2, const d3 P3, con
         best = dmin2(best, seg_seg2(pi, pn, q1, q2)); best = dmin2(best, seg_seg2(pi, pn, q2, q3)); best = dmin2(best, seg_seg2(pi, pn, q3, q1));
     }
     return __builtin_sqrt(best) * pow2(ex);
+}
+
+// ---------------------------------------------------------------- where tri_distance is attained (not reference behaviour)
+// tri_witness(A, B) -> (dist, feature_a, feature_b, ua, va, ub, vb, qa, qb): tri_distance's value, bit for bit, and the two points it is
+// the distance of.  tri_distance's frame (translate to A's first vertex, scale by 2^-ex, |ex| clamped at TRI_DIST_EXP_MAX), its blocks and
+// its operation order; no contraction, IEEE divide and sqrt.
+//   dist = tri_distance(A, B) = sqrt(best) 2^ex -- NOT |qa - qb| recomputed.
+//   Early-outs: a pair tri_distance puts at 0 through its early-outs -- strict FP64 box overlap and tri_contact, or six coincident points --
+//   has NO witness: feature_a = feature_b = 7 and every other output except dist is 0.  (Interpenetration is CCD's to prevent; a pair in
+//   contact has no closest points.)
+//   Otherwise the 33 terms are taken in tri_distance's loop order, term 11 i + k for i = 0, 1, 2 (P = A, Q = B, scaled):
+//     k = 0        pt_face2(P_i; Q)                           A: vertex i          B: the face
+//     k = 1        pt_face2(Q_i; P)                           A: the face          B: vertex i
+//     k = 2, 3, 4  pt_seg2(P_i; Q's edges 01, 12, 20)         A: vertex i          B: edge k - 2
+//     k = 5, 6, 7  pt_seg2(Q_i; P's edges 01, 12, 20)         A: edge k - 5        B: vertex i
+//     k = 8, 9, 10 seg_seg2(P's edge (i, i+1); Q's edges)     A: edge i            B: edge k - 8
+//   and a later term replaces the running minimum only when it is STRICTLY smaller: an earlier term keeps a tie.  The distance does not
+//   depend on that order; the witness does, so the order and the tie rule are part of the contract.  The winning term is evaluated
+//   once more for its parameters, which give, in pt_tri's coding (0 face, 1 / 2 / 3 edge 01 / 12 / 20, 4 / 5 / 6 vertex 0 / 1 / 2):
+//     vertex i          (u, v) = (0, 0), (1, 0), (0, 1)                          feature 4 + i
+//     the face          (u, v) = (fv, fw) of pt_face2_vw                         feature 0
+//     edge e, t from vertex e (pt_seg2_t's t; seg_seg2_st's s on A's edge (i, i+1) from vertex i, its t on B's edge):
+//       edge 01: (t, 0);  edge 12: (1 - t, t);  edge 20: (0, 1 - t)              feature 1 + e; t == 0: vertex e; t == 1: vertex e + 1
+//   q = (w X0 + u X1) + v X2 per coordinate with w = (1 - u) - v, on the ORIGINAL vertices, as pt_tri forms its q.
+// Finite input gives no NaN.  Both points lie on their triangles: u, v >= 0 and u + v <= 1 up to the rounding of 1 - t.
+// | |qa - qb| - dist | <= 2^-48 M, M the largest |coordinate| of the six vertices (measured: at most 2^-50.4 M over 1.2 M pairs --
+// unit soups, near pairs, pairs offset by 1e6 and 2^40, integer-grid ties, slivers; tests/test_witness_ref.py re-checks it on every
+// input the tests use).  Scaling all six vertices by 2^k scales dist, qa and qb exactly and changes nothing in the features or (u, v)
+// over cd_find_proximity's band.  Restated in tests/witness_ref.py bit for bit.
+struct TriWitness { double dist, ua, va, ub, vb; d3 qa, qb; uint32_t fa, fb; };
+__device__ __forceinline__ d3 sel3(int i, const d3 a, const d3 b, const d3 c) { return i == 0 ? a : (i == 1 ? b : c); }
+__device__ __forceinline__ void vertex_bary(int i, double &u, double &v, uint32_t &f) { u = i == 1 ? 1.0 : 0.0; v = i == 2 ? 1.0 : 0.0; f = 4u + (uint32_t)i; }
+__device__ __forceinline__ void edge_bary(int e, double t, double &u, double &v, uint32_t &f)
+{
+    f = t > 0.0 ? (t < 1.0 ? 1u + (uint32_t)e : 4u + (uint32_t)(e == 2 ? 0 : e + 1)) : 4u + (uint32_t)e;
+    u = e == 0 ? t : (e == 1 ? 1.0 - t : 0.0);
+    v = e == 0 ? 0.0 : (e == 1 ? t : 1.0 - t);
+}
+__device__ __forceinline__ d3 bary_point(double u, double v, const d3 x0, const d3 x1, const d3 x2)
+{
+    const double w = (1.0 - u) - v;
+    return d3{(w * x0.x + u * x1.x) + v * x2.x, (w * x0.y + u * x1.y) + v * x2.y, (w * x0.z + u * x1.z) + v * x2.z};
+}
+__device__ inline TriWitness tri_witness(const d3 P1, const d3 P2, const d3 P3, const d3 Q1, const d3 Q2, const d3 Q3)
+{
+    const d3 zero = d3{0.0, 0.0, 0.0};
+    TriWitness r{0.0, 0.0, 0.0, 0.0, 0.0, zero, zero, 7u, 7u};
+    if (box_overlap(box_set(P1, P2, P3), box_set(Q1, Q2, Q3)) && tri_contact_fast(P1, P2, P3, Q1, Q2, Q3)) return r;   // in contact: no witness
+    d3 p2 = sub(P2, P1), p3 = sub(P3, P1), q1 = sub(Q1, P1), q2 = sub(Q2, P1), q3 = sub(Q3, P1);
+    double m = 0.0;
+    m = dmax_abs3(m, p2); m = dmax_abs3(m, p3); m = dmax_abs3(m, q1); m = dmax_abs3(m, q2); m = dmax_abs3(m, q3);
+    if (!(m > 0.0)) return r;                                             // six coincident points
+    int ex = (int)((__double_as_longlong(m) >> 52) & 0x7ff) - 1022;     // (as tri_distance)
+    ex = ex < -TRI_DIST_EXP_MAX ? -TRI_DIST_EXP_MAX : (ex > TRI_DIST_EXP_MAX ? TRI_DIST_EXP_MAX : ex);
+    const double sc = pow2(-ex);
+    const d3 p1 = zero;
+    p2 = dscale(p2, sc); p3 = dscale(p3, sc); q1 = dscale(q1, sc); q2 = dscale(q2, sc); q3 = dscale(q3, sc);
+    // tri_distance's loop, keeping only which term won (the parameters of the other 32 are never formed)
+    double best = __builtin_inf();
+    int win = 0;
+    auto take = [&](double d, int idx) { if (d < best) { best = d; win = idx; } };
+#pragma unroll 1
+    for (int i = 0; i < 3; ++i) {
+        const d3 pi = sel3(i, p1, p2, p3), pn = sel3(i, p2, p3, p1), qi = sel3(i, q1, q2, q3);
+        const int b = 11 * i;
+        take(pt_face2(pi, q1, q2, q3), b);
+        take(pt_face2(qi, p1, p2, p3), b + 1);
+        take(pt_seg2(pi, q1, q2), b + 2); take(pt_seg2(pi, q2, q3), b + 3); take(pt_seg2(pi, q3, q1), b + 4);
+        take(pt_seg2(qi, p1, p2), b + 5); take(pt_seg2(qi, p2, p3), b + 6); take(pt_seg2(qi, p3, p1), b + 7);
+        take(seg_seg2(pi, pn, q1, q2), b + 8); take(seg_seg2(pi, pn, q2, q3), b + 9); take(seg_seg2(pi, pn, q3, q1), b + 10);
+    }
+    // the winning term once more, for its parameters
+    const int i = win / 11, k = win - 11 * i;
+    const d3 pi = sel3(i, p1, p2, p3), pn = sel3(i, p2, p3, p1), qi = sel3(i, q1, q2, q3);
+    double t = 0.0, s = 0.0;
+    if (k == 0) { vertex_bary(i, r.ua, r.va, r.fa); pt_face2_vw(pi, q1, q2, q3, r.ub, r.vb); r.fb = 0u; }
+    else if (k == 1) { vertex_bary(i, r.ub, r.vb, r.fb); pt_face2_vw(qi, p1, p2, p3, r.ua, r.va); r.fa = 0u; }
+    else if (k < 5) { const int e = k - 2; vertex_bary(i, r.ua, r.va, r.fa); pt_seg2_t(pi, sel3(e, q1, q2, q3), sel3(e, q2, q3, q1), t); edge_bary(e, t, r.ub, r.vb, r.fb); }
+    else if (k < 8) { const int e = k - 5; vertex_bary(i, r.ub, r.vb, r.fb); pt_seg2_t(qi, sel3(e, p1, p2, p3), sel3(e, p2, p3, p1), t); edge_bary(e, t, r.ua, r.va, r.fa); }
+    else { const int e = k - 8; seg_seg2_st(pi, pn, sel3(e, q1, q2, q3), sel3(e, q2, q3, q1), s, t); edge_bary(i, s, r.ua, r.va, r.fa); edge_bary(e, t, r.ub, r.vb, r.fb); }
+    r.dist = __builtin_sqrt(best) * pow2(ex);
+    r.qa = bary_point(r.ua, r.va, P1, P2, P3);
+    r.qb = bary_point(r.ub, r.vb, Q1, Q2, Q3);
+    return r;
 }
 
 __device__ __forceinline__ d3 load_vertex(const double *__restrict__ verts, uint32_t i)

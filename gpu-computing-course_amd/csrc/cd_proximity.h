@@ -10,6 +10,7 @@
 //   k_prox_exact   : FP64.  Neighbour filter (collision.cuh:38), tri_distance, append (min ID, max ID) + distance with one
 //       atomic per workgroup and round.  The shard slice, the append and the counter sums around the predicate are the exact
 //       stage's scaffold below (ShardSlice, pair_append, group_counters_add), shared with k_ccd_exact and k_between_exact.
+//       Its WIT instance (the witness calls, cd_witness.h) also notes the two leaf positions of every hit; the plain calls launch WIT = false.
 // The filter is conservative: d_pad = dist + dist 2^-20 + M 2^-20 (M the largest |coordinate| of the root box), far above
 // tri_distance's rounding error (tests/test_proximity_ref.py bounds it), so every pair whose FP64 distance is <= dist is a
 // candidate, and the FP64 test alone decides.  A shard that overflows is detected from its counter (nothing is written past
@@ -195,10 +196,12 @@ __device__ __forceinline__ void group_counters_add(const unsigned long long *v, 
     }
 }
 
+// WIT (the witness calls, cd_witness.h): the append also notes the two leaf positions of the hit, A's first, in wleaf[at].
+template <bool WIT>
 __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_prox_exact(const uint2 *__restrict__ cand, unsigned long long shard_cap, const LeafTri *__restrict__ leaf,
                                                                   const uint32_t *__restrict__ perm, const double *__restrict__ verts, double dist,
                                                                   ProxState *__restrict__ st, uint32_t *__restrict__ pairs, double *__restrict__ dists,
-                                                                  unsigned long long cap)
+                                                                  unsigned long long cap, uint2 *__restrict__ wleaf)
 {
     const ShardSlice sl(st->shard, cand, shard_cap);
     unsigned long long tested = 0;
@@ -206,19 +209,21 @@ __global__ __launch_bounds__(PROX_EXACT_THREADS) void k_prox_exact(const uint2 *
         const unsigned long long i = b0 + threadIdx.x;
         bool hit = false;
         uint32_t ida = 0, idb = 0; double d = 0.0;
+        uint2 lv = make_uint2(0u, 0u);
         if (i < sl.total) {
             const uint2 c = sl.list[i];
             LeafTri A = leaf[c.x], B = leaf[c.y];
+            lv = c;
             if (neighbor_count(A.v0, A.v1, A.v2, B.v0, B.v1, B.v2) < 1) {                 // collision.cuh:38
                 ++tested;
-                if (B.id < A.id || (B.id == A.id && perm[c.y] < perm[c.x])) { const LeafTri t = A; A = B; B = t; }   // A: the smaller ID (then face index)
+                if (B.id < A.id || (B.id == A.id && perm[c.y] < perm[c.x])) { const LeafTri t = A; A = B; B = t; lv = make_uint2(c.y, c.x); }   // A: the smaller ID (then face index)
                 d = tri_distance(load_vertex(verts, A.v0), load_vertex(verts, A.v1), load_vertex(verts, A.v2),
                                  load_vertex(verts, B.v0), load_vertex(verts, B.v1), load_vertex(verts, B.v2));
                 hit = d <= dist;
                 ida = A.id; idb = B.id;
             }
         }
-        pair_append(hit, &st->n_pairs, cap, [&](unsigned long long at) { pairs[2 * at] = ida; pairs[2 * at + 1] = idb; dists[at] = d; });
+        pair_append(hit, &st->n_pairs, cap, [&](unsigned long long at) { pairs[2 * at] = ida; pairs[2 * at + 1] = idb; dists[at] = d; if (WIT) wleaf[at] = lv; });
     }
     group_counters_add<1>(&tested, &st->n_tested);
 }

@@ -10,6 +10,7 @@
 #include "cd_proximity.h"
 #include "cd_ccd.h"
 #include "cd_between.h"
+#include "cd_witness.h"
 #include "cd_rays.h"
 #include "cd_points.h"
 
@@ -88,6 +89,28 @@ struct StateWords {
     void release() { dev_free(d); if (h) hipHostFree(h); h = nullptr; }
 };
 
+// What the witness form of a pair query (cd_find_*_witness, cd_witness.h) adds to its PairBuf, allocated on the first such call: per
+// reported pair the two leaf positions the exact stage notes, and the witness kernel's outputs
+struct WitnessBuf {
+    uint2 *d_leaf = nullptr; uint32_t *d_faces = nullptr; double *d_points = nullptr, *d_bary = nullptr; uint8_t *d_feat = nullptr; uint64_t cap = 0;
+    void release() { dev_free(d_leaf); dev_free(d_faces); dev_free(d_points); dev_free(d_bary); dev_free(d_feat); cap = 0; }
+    int ensure(uint64_t cap_pairs)
+    {
+        const uint64_t want = cap_pairs > 0 ? cap_pairs : 1;
+        if (want <= cap) return CD_OK;
+        release();
+        hipError_t e = hipSuccess;
+        dev_alloc(e, d_leaf, sizeof(uint2) * want);
+        dev_alloc(e, d_faces, sizeof(uint32_t) * 2 * want);
+        dev_alloc(e, d_points, sizeof(double) * 6 * want);
+        dev_alloc(e, d_bary, sizeof(double) * 4 * want);
+        dev_alloc(e, d_feat, sizeof(uint8_t) * 2 * want);
+        if (e != hipSuccess) { release(); return -(int)e; }
+        cap = want;
+        return CD_OK;
+    }
+};
+
 // What a pair query (self-proximity, self-CCD, between two meshes) owns: counters, NSHARD shards of candidates, the result arrays
 template <typename State>
 struct PairBuf {
@@ -95,6 +118,7 @@ struct PairBuf {
     StateWords<State> state;
     uint2 *d_cand = nullptr; uint64_t shard_cap = 0;                        // candidates a shard
     uint32_t *d_pairs = nullptr; double *d_toi = nullptr, *d_dists = nullptr; uint64_t pairs_cap = 0;
+    WitnessBuf wit;
 
     int alloc_cand(uint64_t per)
     {
@@ -104,7 +128,7 @@ struct PairBuf {
         return e == hipSuccess ? CD_OK : -(int)e;
     }
     void release_results() { dev_free(d_pairs); dev_free(d_toi); dev_free(d_dists); pairs_cap = 0; }
-    void release() { state.release(); dev_free(d_cand); shard_cap = 0; release_results(); }
+    void release() { state.release(); dev_free(d_cand); shard_cap = 0; release_results(); wit.release(); }
     // nt: the triangles whose candidates the shards take (16 a triangle to start with; grown on overflow)
     int ensure(uint32_t nt, uint64_t cap_pairs)
     {
@@ -2008,11 +2032,39 @@ int cd_find_collisions_queries(cd_ctx *c, const void *d_queries, uint64_t nq, ui
     return run_traversal(c, c->tb[0], d_queries, nq, pairs, cap_pairs, n_pairs);
 }
 
+// ---- the witness of the pair queries (cd_witness.h) ---------------------------------------------------------------------------------
+// NULL, or every member NULL: the plain call
+static bool witness_wanted(const cd_witness_out *w) { return w && (w->faces || w->points || w->bary || w->feature); }
+// Behind a pass that is finished and read back (np = its pair count): the witness kernel over the rows the caller gets, on stream s, and
+// the copies into w's arrays.  a, b: the contexts A's and B's triangles come from (the self calls: the same one); ax1 / bx1 / d_toi: the
+// end positions and the rows' times on the device (CCD), NULL for proximity.
+static int witness_results(hipStream_t s, const WitnessBuf &wb, uint64_t np, uint64_t cap_pairs, const cd_ctx *a, const double *ax1, const cd_ctx *b,
+                           const double *bx1, const double *d_toi, const cd_witness_out *w)
+{
+    const uint64_t take = std::min(np, cap_pairs);
+    if (!take) return CD_OK;
+    uint32_t *faces = w->faces ? wb.d_faces : nullptr;
+    double *points = w->points ? wb.d_points : nullptr, *bary = w->bary ? wb.d_bary : nullptr;
+    uint8_t *feat = w->feature ? wb.d_feat : nullptr;
+    const uint32_t grid = cdiv(take, WITNESS_THREADS);
+    if (d_toi) k_pair_witness<true><<<grid, WITNESS_THREADS, 0, s>>>(wb.d_leaf, take, a->d_leaf, a->d_perm[0], a->d_verts, ax1, b->d_leaf, b->d_perm[0], b->d_verts, bx1,
+                                                                    d_toi, faces, points, bary, feat);
+    else k_pair_witness<false><<<grid, WITNESS_THREADS, 0, s>>>(wb.d_leaf, take, a->d_leaf, a->d_perm[0], a->d_verts, nullptr, b->d_leaf, b->d_perm[0], b->d_verts, nullptr,
+                                                               nullptr, faces, points, bary, feat);
+    HIPCHK(hipGetLastError());
+    if (faces) HIPCHK(hipMemcpyAsync(w->faces, faces, sizeof(uint32_t) * 2 * take, hipMemcpyDeviceToHost, s));
+    if (points) HIPCHK(hipMemcpyAsync(w->points, points, sizeof(double) * 6 * take, hipMemcpyDeviceToHost, s));
+    if (bary) HIPCHK(hipMemcpyAsync(w->bary, bary, sizeof(double) * 4 * take, hipMemcpyDeviceToHost, s));
+    if (feat) HIPCHK(hipMemcpyAsync(w->feature, feat, sizeof(uint8_t) * 2 * take, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return CD_OK;
+}
+
 // ---- self-proximity (cd_proximity.h) ------------------------------------------------------------------------------------------------
 // Own buffers (state, candidates, pairs, distances): the collision path's counters, pair list, statistics and captured step stay as they were.
 static bool prox_dist_ok(double dist) { return dist >= 0.0 && dist <= 1.7976931348623157e308; }      // (NaN fails both)
 // the two kernels of one pass and the read-back of the counters (no synchronisation)
-static int prox_enqueue(cd_ctx *c, double dist, uint64_t cap_pairs)
+static int prox_enqueue(cd_ctx *c, double dist, uint64_t cap_pairs, uint2 *wleaf = nullptr /* the witness calls: the hits' leaf positions */)
 {
     hipStream_t s = c->stream;
     const uint32_t n = c->nt;
@@ -2020,8 +2072,10 @@ static int prox_enqueue(cd_ctx *c, double dist, uint64_t cap_pairs)
     HIPCHK(hipMemsetAsync(q.state.d, 0, sizeof(ProxState), s));
     k_prox_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(c->d_recs32, c->d_leaf, c->d_verts, c->d_boxes, (int)n, dist,
                                                                              c->d_os_ticket + 8, q.state.d, q.d_cand, q.shard_cap);
-    k_prox_exact<<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, dist,
-                                                                              q.state.d, q.d_pairs, q.d_dists, cap_pairs);
+    if (wleaf) k_prox_exact<true><<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, dist,
+                                                                                               q.state.d, q.d_pairs, q.d_dists, cap_pairs, wleaf);
+    else k_prox_exact<false><<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, dist,
+                                                                                          q.state.d, q.d_pairs, q.d_dists, cap_pairs, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(q.state.h, q.state.d, sizeof(ProxState), hipMemcpyDeviceToHost, s));
     return CD_OK;
@@ -2031,10 +2085,10 @@ static int prox_results(cd_ctx *c, uint32_t *pairs, double *dists, uint64_t cap_
     if (n_tested) *n_tested = c->prox.state.h->n_tested;
     return c->prox.results(pairs, nullptr, dists, cap_pairs, n_pairs);
 }
-static int prox_pass(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
+static int prox_pass(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested, uint2 *wleaf = nullptr)
 {
     for (;;) {
-        int rc = prox_enqueue(c, dist, cap_pairs);
+        int rc = prox_enqueue(c, dist, cap_pairs, wleaf);
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
         if (!c->prox.overflowed(rc)) { if (rc) return rc; break; }
@@ -2053,6 +2107,19 @@ int cd_find_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, ui
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if ((rc = c->prox.ensure(c->nt, cap_pairs))) return rc;
     return prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
+}
+int cd_find_proximity_witness(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested,
+                              const cd_witness_out *w)
+{
+    if (!witness_wanted(w)) return cd_find_proximity(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
+    int rc = prox_args(c, dist, pairs, cap_pairs);
+    if (rc) return rc;
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if ((rc = c->prox.ensure(c->nt, cap_pairs)) || (rc = c->prox.wit.ensure(cap_pairs))) return rc;
+    rc = prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested, c->prox.wit.d_leaf);
+    if (rc != CD_OK && rc != CD_OVERFLOW) return rc;
+    const int rw = witness_results(c->stream, c->prox.wit, c->prox.state.h->n_pairs, cap_pairs, c, nullptr, c, nullptr, nullptr, w);
+    return rw ? rw : rc;
 }
 int cd_self_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
 {
@@ -2085,6 +2152,26 @@ int cd_tri_distance_points(const double *tri, uint64_t n, double *dist)
     return dev.rc();
 }
 
+int cd_tri_witness_points(const double *tri, uint64_t n, double *dist, double *points, double *bary, uint8_t *feature)
+{
+    if (!tri || !dist) return CD_ERR_ARG;
+    if (n == 0) return CD_OK;
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_t = dev.in(tri, 18 * n);
+    double *d_d = dev.out<double>(n), *d_q = dev.out<double>(6 * n), *d_b = dev.out<double>(4 * n);
+    uint8_t *d_f = dev.out<uint8_t>(2 * n);
+    if (dev.e == hipSuccess) {
+        k_tri_witness_points<<<strided_grid(n, WITNESS_THREADS), WITNESS_THREADS>>>(d_t, n, d_d, d_q, d_b, d_f);
+        dev.e = hipGetLastError();
+    }
+    dev.back(dist, d_d, n);
+    dev.back(points, d_q, 6 * n);
+    dev.back(bary, d_b, 4 * n);
+    dev.back(feature, d_f, 2 * n);
+    return dev.rc();
+}
+
 // ---- continuous collision queries (cd_ccd.h) ------------------------------------------------------------------------------------
 // Own buffers (x1, swept records, parent links, arrival counters, state, candidates, pairs, times, distances): the context's vertices,
 // the collision path's counters, pair list, statistics and captured step, and the proximity buffers stay as they were.
@@ -2107,7 +2194,7 @@ static int enqueue_swept_refit(hipStream_t s, const cd_ctx *src, const double *x
     return CD_OK;
 }
 // x1 upload, swept refit, descent, exact pass and the read-back of the counters (no synchronisation)
-static int ccd_enqueue(cd_ctx *c, const double *verts_end /* NULL: a redo, x1 is there */, double dist, uint64_t cap_pairs)
+static int ccd_enqueue(cd_ctx *c, const double *verts_end /* NULL: a redo, x1 is there */, double dist, uint64_t cap_pairs, uint2 *wleaf = nullptr)
 {
     hipStream_t s = c->stream;
     const uint32_t n = c->nt;
@@ -2120,19 +2207,22 @@ static int ccd_enqueue(cd_ctx *c, const double *verts_end /* NULL: a redo, x1 is
         if (rc) return rc;
         k_ccd_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(c->swept[0].d_recs, c->d_leaf, c->d_verts, x1, (int)n, dist,
                                                                                c->d_os_ticket + 8, q.state.d, q.d_cand, q.shard_cap);
-        k_ccd_exact<<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, x1, dist,
-                                                                                 q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs);
+        if (wleaf) k_ccd_exact<true><<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, x1, dist,
+                                                                                                  q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, wleaf);
+        else k_ccd_exact<false><<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, x1, dist,
+                                                                                             q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, nullptr);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(q.state.h, q.state.d, sizeof(CcdState), hipMemcpyDeviceToHost, s));
     return CD_OK;
 }
 // after a pass that is already enqueued and synchronised: redo it while a shard overflows, then the results
-static int ccd_finish(cd_ctx *c, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info)
+static int ccd_finish(cd_ctx *c, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info,
+                      uint2 *wleaf = nullptr)
 {
     int rc;
     while (c->ccd.overflowed(rc)) {
-        if ((rc = ccd_enqueue(c, nullptr, dist, cap_pairs))) return rc;
+        if ((rc = ccd_enqueue(c, nullptr, dist, cap_pairs, wleaf))) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     if (rc) return rc;
@@ -2155,6 +2245,21 @@ int cd_find_ccd(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs
     if ((rc = ccd_enqueue(c, verts_end, dist, cap_pairs))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return ccd_finish(c, dist, pairs, toi, dists, cap_pairs, n_pairs, info);
+}
+int cd_find_ccd_witness(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
+                        cd_ccd_info *info, const cd_witness_out *w)
+{
+    if (!witness_wanted(w)) return cd_find_ccd(c, verts_end, dist, pairs, toi, dists, cap_pairs, n_pairs, info);
+    int rc = ccd_args(c, verts_end, dist, pairs, cap_pairs);
+    if (rc) return rc;
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if ((rc = ccd_buffers(c, cap_pairs)) || (rc = c->ccd.wit.ensure(cap_pairs))) return rc;
+    if ((rc = ccd_enqueue(c, verts_end, dist, cap_pairs, c->ccd.wit.d_leaf))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    rc = ccd_finish(c, dist, pairs, toi, dists, cap_pairs, n_pairs, info, c->ccd.wit.d_leaf);
+    if (rc != CD_OK && rc != CD_OVERFLOW) return rc;
+    const int rw = witness_results(c->stream, c->ccd.wit, c->ccd.state.h->n_pairs, cap_pairs, c, c->ccd_x1.d, c, c->ccd_x1.d, c->ccd.d_toi, w);
+    return rw ? rw : rc;
 }
 int cd_self_ccd(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
                 cd_ccd_info *info)
@@ -2206,7 +2311,7 @@ static int bw_buffers(cd_ctx *a, const cd_ctx *b, uint64_t cap_pairs, bool ccd)
 }
 // one pass (CCD: a's M, b's swept refit; descent; exact stage) and the read-back of the counters (no synchronisation).  ax1 / bx1: device
 // pointers to the end positions (CCD only).
-static int bw_enqueue(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_pairs, const double *ax1, const double *bx1)
+static int bw_enqueue(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_pairs, const double *ax1, const double *bx1, uint2 *wleaf = nullptr)
 {
     hipStream_t s = a->stream;
     const uint32_t na = a->nt, nb = b->nt;
@@ -2224,23 +2329,29 @@ static int bw_enqueue(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_
     }
     const dim3 grid(shard_blocks(na), NSHARD);
     if (kind == BW_CONTACT)
-        k_between_exact<BW_CONTACT><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
-                                                                        dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs);
+        k_between_exact<BW_CONTACT, false><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
+                                                                               dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, nullptr);
+    else if (kind == BW_PROXIMITY && wleaf)
+        k_between_exact<BW_PROXIMITY, true><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
+                                                                                dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, wleaf);
     else if (kind == BW_PROXIMITY)
-        k_between_exact<BW_PROXIMITY><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
-                                                                          dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs);
+        k_between_exact<BW_PROXIMITY, false><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
+                                                                                 dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, nullptr);
+    else if (wleaf)
+        k_between_exact<BW_CCD, true><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, ax1, b->d_leaf, b->d_verts, bx1,
+                                                                          dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, wleaf);
     else
-        k_between_exact<BW_CCD><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, ax1, b->d_leaf, b->d_verts, bx1,
-                                                                    dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs);
+        k_between_exact<BW_CCD, false><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, ax1, b->d_leaf, b->d_verts, bx1,
+                                                                           dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(q.state.h, q.state.d, sizeof(CcdState), hipMemcpyDeviceToHost, s));
     return CD_OK;
 }
 // enqueue, synchronise, and again with a grown candidate buffer while a shard overflowed
-static int bw_pass(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_pairs, const double *ax1, const double *bx1)
+static int bw_pass(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_pairs, const double *ax1, const double *bx1, uint2 *wleaf = nullptr)
 {
     for (;;) {
-        int rc = bw_enqueue(a, b, kind, dist, cap_pairs, ax1, bx1);
+        int rc = bw_enqueue(a, b, kind, dist, cap_pairs, ax1, bx1, wleaf);
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(a->stream));
         if (!a->bw.overflowed(rc)) return rc;
@@ -2286,6 +2397,40 @@ int cd_find_ccd_between(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const d
     a->swept[1].seen = {true, b->nt, a->bw.state.h->m_bits, dist};
     a->bw.fill_info(info);
     return a->bw.results(pairs, toi, dists, cap_pairs, n_pairs);
+}
+int cd_find_proximity_between_witness(cd_ctx *a, cd_ctx *b, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
+                                      uint64_t *n_tested, const cd_witness_out *w)
+{
+    if (!witness_wanted(w)) return cd_find_proximity_between(a, b, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
+    int rc = bw_args(a, b, pairs, cap_pairs);
+    if (rc) return rc;
+    if (!prox_dist_ok(dist)) return CD_ERR_ARG;
+    if ((rc = bw_start(a, b, cap_pairs, false)) || (rc = a->bw.wit.ensure(cap_pairs))) return rc;
+    if ((rc = bw_pass(a, b, BW_PROXIMITY, dist, cap_pairs, nullptr, nullptr, a->bw.wit.d_leaf))) return rc;
+    if (n_tested) *n_tested = a->bw.state.h->n_tested;
+    rc = a->bw.results(pairs, nullptr, dists, cap_pairs, n_pairs);
+    if (rc != CD_OK && rc != CD_OVERFLOW) return rc;
+    const int rw = witness_results(a->stream, a->bw.wit, a->bw.state.h->n_pairs, cap_pairs, a, nullptr, b, nullptr, nullptr, w);
+    return rw ? rw : rc;
+}
+int cd_find_ccd_between_witness(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const double *verts_end_b, double dist, uint32_t *pairs, double *toi,
+                                double *dists, uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info, const cd_witness_out *w)
+{
+    if (!witness_wanted(w)) return cd_find_ccd_between(a, verts_end_a, b, verts_end_b, dist, pairs, toi, dists, cap_pairs, n_pairs, info);
+    int rc = bw_args(a, b, pairs, cap_pairs);
+    if (rc) return rc;
+    if (!ccd_dist_ok(dist)) return CD_ERR_ARG;
+    if ((rc = bw_start(a, b, cap_pairs, true)) || (rc = a->bw.wit.ensure(cap_pairs))) return rc;
+    const double *ax1 = a->d_verts, *bx1 = b->d_verts;                     // NULL: that mesh does not move (x1 = x0)
+    if (verts_end_a) { HIPCHK(hipMemcpyAsync(a->bw_x1a.d, verts_end_a, sizeof(double) * 3 * (size_t)a->nv, hipMemcpyHostToDevice, a->stream)); ax1 = a->bw_x1a.d; }
+    if (verts_end_b) { HIPCHK(hipMemcpyAsync(a->bw_x1b.d, verts_end_b, sizeof(double) * 3 * (size_t)b->nv, hipMemcpyHostToDevice, a->stream)); bx1 = a->bw_x1b.d; }
+    if ((rc = bw_pass(a, b, BW_CCD, dist, cap_pairs, ax1, bx1, a->bw.wit.d_leaf))) return rc;
+    a->swept[1].seen = {true, b->nt, a->bw.state.h->m_bits, dist};
+    a->bw.fill_info(info);
+    rc = a->bw.results(pairs, toi, dists, cap_pairs, n_pairs);
+    if (rc != CD_OK && rc != CD_OVERFLOW) return rc;
+    const int rw = witness_results(a->stream, a->bw.wit, a->bw.state.h->n_pairs, cap_pairs, a, ax1, b, bx1, a->bw.d_toi, w);
+    return rw ? rw : rc;
 }
 // ---- ray queries (cd_rays.h) ------------------------------------------------------------------------------------------------------
 // Own buffers (rays, results, counters): nothing any other call keeps is touched.

@@ -5,6 +5,7 @@ fallback; if the shared library is missing or no HIP device is present the const
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -71,6 +72,35 @@ CD_POINT_ANY = 1
 POINT_NONE = 0xFFFFFFFF
 
 
+class CdWitnessOut(C.Structure):
+    _fields_ = [("faces", C.c_void_p), ("points", C.c_void_p), ("bary", C.c_void_p), ("feature", C.c_void_p)]
+
+
+FEATURE_NONE = 7                    # tri_witness: a pair in contact (or six coincident points) has no closest points
+
+
+class Witness(collections.namedtuple("Witness", "faces points bary feature")):
+    """Where the distances of the reported pairs are attained (cd_witness_out), row k for pairs[k]: faces u32[n, 2] (indices in the
+    face list of the triangles that played A and B), points f64[n, 2, 3] (qa, qb), bary f64[n, 2, 2] ((ua, va), (ub, vb)),
+    feature u8[n, 2] (0 face, 1-3 edge 01 / 12 / 20, 4-6 vertex 0 / 1 / 2, 7 none: the pair is in contact)."""
+    __slots__ = ()
+
+
+class _WitnessArrays:
+    """The four arrays of a witness call with room for cap rows, and the cd_witness_out that points at them."""
+
+    def __init__(self, cap):
+        n = max(cap, 1)
+        self.faces = np.empty((n, 2), dtype=np.uint32)
+        self.points = np.empty((n, 2, 3), dtype=np.float64)
+        self.bary = np.empty((n, 2, 2), dtype=np.float64)
+        self.feature = np.empty((n, 2), dtype=np.uint8)
+        self.out = CdWitnessOut(self.faces.ctypes.data, self.points.ctypes.data, self.bary.ctypes.data, self.feature.ctypes.data)
+
+    def take(self, got):
+        return Witness(self.faces[:got].copy(), self.points[:got].copy(), self.bary[:got].copy(), self.feature[:got].copy())
+
+
 class CdMultiInfo(C.Structure):
     _fields_ = [("world", C.c_uint32), ("rank", C.c_uint32), ("n_peers", C.c_uint32), ("host_syncs", C.c_uint32), ("attempts", C.c_uint32),
                 ("failed_rank_plus1", C.c_uint32), ("sent_queries", C.c_uint64), ("recv_queries", C.c_uint64), ("local_pairs", C.c_uint64),
@@ -92,6 +122,7 @@ EXPORTS = [
     "cd_find_collisions_between", "cd_find_proximity_between", "cd_find_ccd_between",
     "cd_cast_rays", "cd_ray_tri_points",
     "cd_closest_points", "cd_pt_tri_points",
+    "cd_find_proximity_witness", "cd_find_proximity_between_witness", "cd_find_ccd_witness", "cd_find_ccd_between_witness", "cd_tri_witness_points",
 ]
 
 _lib = None
@@ -174,6 +205,12 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_ray_tri_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp]
     lib.cd_closest_points.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cd_pt_tri_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, vp]
+    wp = C.POINTER(CdWitnessOut)
+    lib.cd_find_proximity_witness.argtypes = lib.cd_find_proximity.argtypes + [wp]
+    lib.cd_find_proximity_between_witness.argtypes = lib.cd_find_proximity_between.argtypes + [wp]
+    lib.cd_find_ccd_witness.argtypes = lib.cd_find_ccd.argtypes + [wp]
+    lib.cd_find_ccd_between_witness.argtypes = lib.cd_find_ccd_between.argtypes + [wp]
+    lib.cd_tri_witness_points.argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -339,6 +376,73 @@ class CollisionDetector:
     def self_proximity(self, dist: float, cap: int = 1 << 20):
         """cd_self_proximity: build the tree, then find_proximity, with one host synchronisation."""
         return self._proximity_call(self.lib.cd_self_proximity, "cd_self_proximity", dist, cap)
+
+    def find_proximity_witness(self, dist: float, cap: int = 1 << 20):
+        """cd_find_proximity_witness: find_proximity's (pairs, dists, n, rc) and a Witness whose row k says where dists[k] is attained."""
+        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        dists = np.empty(max(cap, 1), dtype=np.float64)
+        wa = _WitnessArrays(cap)
+        n, tested = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.cd_find_proximity_witness(self._ctx, float(dist), _ptr(pairs) if cap else None, _ptr(dists), cap, C.byref(n), C.byref(tested),
+                                                C.byref(wa.out))
+        self._chk("cd_find_proximity_witness", rc, allow=(CD_OK, CD_OVERFLOW))
+        self.proximity_tested = tested.value
+        got = min(n.value, cap)
+        return pairs[:got].copy(), dists[:got].copy(), n.value, rc, wa.take(got)
+
+    def find_ccd_witness(self, verts_end, dist: float, cap: int = 1 << 20):
+        """cd_find_ccd_witness: find_ccd's (pairs, toi, dists, n, rc) and a Witness taken at the evaluation that reported each pair."""
+        v = np.ascontiguousarray(verts_end, dtype=np.float64)
+        if v.shape != (self.nv, 3):
+            raise ValueError(f"verts_end must be [{self.nv}, 3], got {v.shape}")
+        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        toi = np.empty(max(cap, 1), dtype=np.float64)
+        dists = np.empty(max(cap, 1), dtype=np.float64)
+        wa = _WitnessArrays(cap)
+        n, info = C.c_uint64(0), CdCcdInfo()
+        rc = self.lib.cd_find_ccd_witness(self._ctx, _ptr(v), float(dist), _ptr(pairs) if cap else None, _ptr(toi), _ptr(dists), cap, C.byref(n),
+                                          C.byref(info), C.byref(wa.out))
+        self._chk("cd_find_ccd_witness", rc, allow=(CD_OK, CD_OVERFLOW))
+        self.ccd_info = info
+        got = min(n.value, cap)
+        return pairs[:got].copy(), toi[:got].copy(), dists[:got].copy(), n.value, rc, wa.take(got)
+
+    def find_proximity_between_witness(self, other, dist: float, cap: int = 1 << 20):
+        """cd_find_proximity_between_witness: find_proximity_between's (pairs, dists, n, rc) and a Witness (A: self's triangle; faces
+        index each context's own face list)."""
+        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        dists = np.empty(max(cap, 1), dtype=np.float64)
+        wa = _WitnessArrays(cap)
+        n, tested = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.cd_find_proximity_between_witness(self._ctx, other._ctx, float(dist), _ptr(pairs) if cap else None, _ptr(dists), cap,
+                                                        C.byref(n), C.byref(tested), C.byref(wa.out))
+        self._chk("cd_find_proximity_between_witness", rc, allow=(CD_OK, CD_OVERFLOW))
+        self.between_tested = tested.value
+        got = min(n.value, cap)
+        return pairs[:got].copy(), dists[:got].copy(), n.value, rc, wa.take(got)
+
+    def find_ccd_between_witness(self, other, dist: float, verts_end=None, other_verts_end=None, cap: int = 1 << 20):
+        """cd_find_ccd_between_witness: find_ccd_between's (pairs, toi, dists, n, rc) and a Witness."""
+        def end(v, nv, what):
+            if v is None:
+                return None
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            if v.shape != (nv, 3):
+                raise ValueError(f"{what} must be [{nv}, 3], got {v.shape}")
+            return v
+        va = end(verts_end, self.nv, "verts_end")
+        vb = end(other_verts_end, other.nv, "other_verts_end")
+        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        toi = np.empty(max(cap, 1), dtype=np.float64)
+        dists = np.empty(max(cap, 1), dtype=np.float64)
+        wa = _WitnessArrays(cap)
+        n, info = C.c_uint64(0), CdCcdInfo()
+        rc = self.lib.cd_find_ccd_between_witness(self._ctx, _ptr(va), other._ctx, _ptr(vb), float(dist), _ptr(pairs) if cap else None,
+                                                  _ptr(toi), _ptr(dists), cap, C.byref(n), C.byref(info), C.byref(wa.out))
+        self._chk("cd_find_ccd_between_witness", rc, allow=(CD_OK, CD_OVERFLOW))
+        self.ccd_info = info
+        got = min(n.value, cap)
+        return pairs[:got].copy(), toi[:got].copy(), dists[:got].copy(), n.value, rc, wa.take(got)
 
     def _ccd_call(self, fn, name, verts_end, dist, cap):
         v = np.ascontiguousarray(verts_end, dtype=np.float64)
@@ -698,6 +802,21 @@ def tri_distance_points(tri) -> np.ndarray:
     if rc != CD_OK:
         raise CdError("cd_tri_distance_points", rc)
     return out
+
+
+def tri_witness_points(tri):
+    """tri_witness (where tri_distance is attained) on explicit vertex positions [n, 6, 3], on the device (cd_tri_witness_points):
+    (dist[n], points[n, 2, 3] (qa, qb), bary[n, 2, 2] ((ua, va), (ub, vb)), feature[n, 2])."""
+    t = np.ascontiguousarray(tri, dtype=np.float64).reshape(-1, 18)
+    n = t.shape[0]
+    dist = np.zeros(n, dtype=np.float64)
+    points = np.zeros((n, 2, 3), dtype=np.float64)
+    bary = np.zeros((n, 2, 2), dtype=np.float64)
+    feature = np.zeros((n, 2), dtype=np.uint8)
+    rc = load_library().cd_tri_witness_points(_ptr(t), n, _ptr(dist), _ptr(points), _ptr(bary), _ptr(feature))
+    if rc != CD_OK:
+        raise CdError("cd_tri_witness_points", rc)
+    return dist, points, bary, feature
 
 
 def pack_rays(origins, dirs, tmax=np.inf) -> np.ndarray:

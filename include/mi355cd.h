@@ -493,6 +493,64 @@ int cd_find_ccd_between(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const d
                         uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
                         cd_ccd_info *info);
 
+/* ---- the closest points of proximity and CCD pairs: the witness (not reference behaviour) ----
+ * tri_witness(A, B) -> (dist, feature_a, feature_b, ua, va, ub, vb, qa, qb): WHERE on the two triangles tri_distance(A, B) is attained.
+ * FP64 in tri_distance's frame (translate to A's first vertex, scale by 2^-ex with |ex| clamped at 1000), with tri_distance's blocks and
+ * operation order, IEEE divide and sqrt, no contraction (csrc/cd_math.h):
+ *   dist = tri_distance(A, B), bit for bit: sqrt(best) 2^ex -- not |qa - qb| recomputed.
+ *   A pair tri_distance puts at 0 through its early-outs -- the FP64 boxes overlap strictly and tri_contact holds, or the six points
+ *   coincide -- has NO witness: feature_a = feature_b = 7 and every other output except dist is 0.  Interpenetration is CCD's to
+ *   prevent; a pair in contact has no closest points.
+ *   Otherwise the 33 terms of tri_distance are taken in this order, term 11 i + k for i = 0, 1, 2 (P = A, Q = B):
+ *     k = 0         pt_face2(P_i; Q)      vertex i of A against B's face interior
+ *     k = 1         pt_face2(Q_i; P)      vertex i of B against A's face interior
+ *     k = 2, 3, 4   pt_seg2(P_i; Q's edges 01, 12, 20)
+ *     k = 5, 6, 7   pt_seg2(Q_i; P's edges 01, 12, 20)
+ *     k = 8, 9, 10  seg_seg2(P's edge (i, i+1); Q's edges 01, 12, 20), the interior critical point of the two segments
+ *   and a later term replaces the running minimum only when it is STRICTLY smaller (an earlier term keeps a tie).  The distance does
+ *   not depend on that order; the witness does, so the order and the tie rule are part of this contract.
+ *   What the winning term gives, in pt_tri's coding (0 face, 1 / 2 / 3 edge 01 / 12 / 20, 4 / 5 / 6 vertex 0 / 1 / 2):
+ *     a vertex i:  (u, v) = (0, 0), (1, 0), (0, 1);  feature 4 + i
+ *     a face:      (u, v) = (fv, fw) of the face block (as pt_tri's);  feature 0
+ *     an edge e with parameter t measured from vertex e (the clamped t of the segment block; for seg_seg2 its s on A's edge (i, i+1)
+ *     from vertex i and its t on B's edge), exactly pt_tri's table:
+ *       edge 01: (t, 0);  edge 12: (1 - t, t);  edge 20: (0, 1 - t);  feature 1 + e, or the vertex's code when t == 0 or t == 1
+ *   qa = (wa A0 + ua A1) + va A2 per coordinate with wa = (1 - ua) - va, on the ORIGINAL vertices, as pt_tri forms q; qb likewise on B.
+ * Finite input gives no NaN.  Both points lie on their triangles: u, v >= 0 and u + v <= 1 up to the rounding of 1 - t.
+ * | |qa - qb| - dist | <= 2^-48 M with M the largest |coordinate| of the six vertices (a numpy prototype measured at most 2^-50.4 M
+ * over 1.2 M pairs: unit soups, near pairs, pairs offset by 1e6 and by 2^40, integer-grid ties, slivers; tests/test_witness_ref.py
+ * re-checks it on every input the tests use).  Scaling all six vertices by 2^k scales dist, qa and qb exactly and changes nothing in
+ * the features or (u, v) over cd_find_proximity's band.
+ *
+ * The four calls below are cd_find_proximity, cd_find_proximity_between, cd_find_ccd and cd_find_ccd_between with one trailing
+ * argument.  Each member of w holds cap_pairs rows -- faces 2, points 6 (qa, then qb), bary 4 (ua va ub vb), feature 2 elements a row
+ * -- and may be NULL; a NULL w (or one whose members are all NULL) makes the call the plain one.  Row k describes pairs[k]:
+ *   faces[2 k], faces[2 k + 1]: the indices in cd_create's face list of the triangles that played A and B.  Self calls: A is the
+ *   smaller ID, then the smaller face index.  Between calls: A is a's triangle, and each index is into its own context's list.  (With
+ *   custom or repeated IDs this is what tells which face a reported ID is.)
+ *   The rest is tri_witness(A, B), evaluated with the arguments of the row's distance: dists[k] is the witness's dist, bit for bit.
+ *   CCD: the witness is taken at the evaluation that reported the pair -- also for an unresolved pair, at its last evaluation, with
+ *   d > dist.  The positions are x1 itself when toi[k] == 1, otherwise a + toi (b - a) per coordinate as the advancement forms p(t)
+ *   (x0's values at toi == 0).
+ * Everything else follows the plain calls: the errors, CD_OVERFLOW with the true *n_pairs and nothing written past cap_pairs in any
+ * array, the "depends on the meshes and dist only" guarantee (per row: the order of the rows is as free as the plain calls'), the
+ * context state the call leaves as it was.  The calls keep device buffers of their own (grown on demand; cd_destroy frees them) and
+ * cost one more kernel over the reported pairs and one more host synchronisation. */
+typedef struct cd_witness_out { uint32_t *faces; double *points; double *bary; uint8_t *feature; } cd_witness_out;
+int cd_find_proximity_witness(cd_ctx *ctx, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs,
+                              uint64_t *n_pairs, uint64_t *n_tested, const cd_witness_out *w);
+int cd_find_proximity_between_witness(cd_ctx *a, cd_ctx *b, double dist, uint32_t *pairs, double *dists,
+                                      uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested, const cd_witness_out *w);
+int cd_find_ccd_witness(cd_ctx *ctx, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists,
+                        uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info, const cd_witness_out *w);
+int cd_find_ccd_between_witness(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const double *verts_end_b, double dist,
+                                uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
+                                cd_ccd_info *info, const cd_witness_out *w);
+/* tri_witness on explicit positions (host pointers; no context): tri is n x 18 doubles as for cd_tri_distance_points.  dist[k];
+ * points[6 k ..]: qa, then qb; bary[4 k ..]: ua va ub vb; feature[2 k], feature[2 k + 1].  Every output except dist may be NULL.  The
+ * pin of the device function. */
+int cd_tri_witness_points(const double *tri, uint64_t n, double *dist, double *points, double *bary, uint8_t *feature);
+
 /* ---- ray queries: closest hit and occlusion (not reference behaviour) ----
  * A ray is seven doubles: an origin o, a direction d and an upper end tmax.  o and d are finite and d is not all zero; d is NOT
  * normalised, so t is in units of d; 0 <= tmax <= +inf and the ray's parameter range is [0, tmax] (a segment from a to b: o = a,
