@@ -404,6 +404,83 @@ __device__ __forceinline__ RayHit ray_tri(const d3 o, const d3 d, const double t
     return r;
 }
 
+// ---------------------------------------------------------------- the segment two triangles cut each other in (not reference behaviour)
+// tri_isect(A, B): six ray_tri evaluations in a fixed order and a selection rule -- no arithmetic of its own beyond d = end - start,
+// x = o + t d and the squared distance of two such points, all FP64, this operation order, no contraction; a NaN fails every comparison.
+//   term k = 0, 1, 2: A's edge from A_k to A_(k+1 mod 3) against B's face (B0, B1, B2);
+//   term k = 3, 4, 5: B's edge from B_(k-3) to B_(k-2 mod 3) against A's face (A0, A1, A2);
+//   r_k = ray_tri(o, d, 1.0, p0, p1, p2) with o the edge's start and d = end - start per coordinate (one rounding); on a hit
+//   x_k = o + t d per coordinate, the product rounded and then the sum: the P of ray_tri's gate.
+//   mask: bit k set when term k hit.
+//   No hit: n = 0, both terms 7, everything else 0 (coplanar pairs; touching pairs the gate or the range checks reject; degenerate triangles).
+//   One hit: n = 1, endpoint 0 is that term, endpoint 1 has term 7 and zeros.
+//   Two or more: n = 2.  The pairs (i, j), i < j, of hit terms are taken in lexicographic order with D = (dx dx + dy dy) + dz dz of
+//   x_i - x_j; a later pair replaces the kept one only when its D is STRICTLY larger (an earlier pair keeps a tie; a NaN D never replaces).
+//   Endpoint 0 is i, endpoint 1 is j.  With exactly two hits these are the two hits in term order.
+//   Per endpoint: the term (0..5), ray_tri's t (along the piercing edge from its start), (u, v) (barycentrics on the pierced face), side, x.
+// Properties (tests/test_isect_ref.py on the numpy restatement, tests/test_contour_gpu.py bit for bit on this code):
+//   Finite input gives no NaN in any output (a hit has passed ray_tri's comparisons, so t, u, v are numbers and t is in [0, 1]).
+//   Scaling all six vertices by 2^k scales x exactly and changes nothing else while the coordinates stay inside ray_tri's band.
+//   tri_isect(B, A) hits exactly the terms (k + 3) mod 6 with bit-identical t, u, v, side, x -- each term is the same ray_tri call; only
+//   the order of the two endpoints may differ.
+//   Both endpoints lie on both triangles within 2^-42 M, M the pair's largest |coordinate| -- a condition on the inputs, as the witness's
+//   bound: measured on the restatement over every input the tests use (worst 2^-44.58 M, on a sliver).
+// The six terms are evaluated once for their points and the two winners once more for their parameters (the same call on the same
+// operands: the same bits), which keeps the six terms' t, u, v out of the registers.
+constexpr uint32_t ISECT_NONE = 7u;
+struct IsectEnd { uint32_t term, side; double t, u, v; d3 x; };
+struct TriIsect { uint32_t n, mask; IsectEnd e[2]; };
+__device__ __forceinline__ d3 isect_sel3(int i, const d3 a, const d3 b, const d3 c) { return i == 0 ? a : (i == 1 ? b : c); }
+// term k of tri_isect: hit, t, u, v, side from ray_tri; x = o + t d (zeros on a miss).  (One ray_tri for both sides: the operands are
+// picked by k, a constant in tri_isect's unrolled loop and a run-time value for the two winners.)
+__device__ __forceinline__ RayHit isect_term(uint32_t k, const d3 A0, const d3 A1, const d3 A2, const d3 B0, const d3 B1, const d3 B2, d3 &x)
+{
+    const bool ea = k < 3u;
+    const int i = (int)(ea ? k : k - 3u), j = i == 2 ? 0 : i + 1;
+    const d3 o = ea ? isect_sel3(i, A0, A1, A2) : isect_sel3(i, B0, B1, B2);
+    const d3 e = ea ? isect_sel3(j, A0, A1, A2) : isect_sel3(j, B0, B1, B2);
+    const d3 d = sub(e, o);
+    const RayHit r = ray_tri(o, d, 1.0, ea ? B0 : A0, ea ? B1 : A1, ea ? B2 : A2);
+    x = r.hit ? d3{o.x + r.t * d.x, o.y + r.t * d.y, o.z + r.t * d.z} : d3{0.0, 0.0, 0.0};
+    return r;
+}
+__device__ __forceinline__ IsectEnd isect_end(uint32_t k, const d3 A0, const d3 A1, const d3 A2, const d3 B0, const d3 B1, const d3 B2)
+{
+    IsectEnd e{ISECT_NONE, 0u, 0.0, 0.0, 0.0, d3{0.0, 0.0, 0.0}};
+    if (k == ISECT_NONE) return e;
+    const RayHit r = isect_term(k, A0, A1, A2, B0, B1, B2, e.x);
+    e.term = k; e.side = r.side; e.t = r.t; e.u = r.u; e.v = r.v;
+    return e;
+}
+__device__ __forceinline__ TriIsect tri_isect(const d3 A0, const d3 A1, const d3 A2, const d3 B0, const d3 B1, const d3 B2)
+{
+    d3 x[6];
+    uint32_t mask = 0u;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) mask |= isect_term((uint32_t)k, A0, A1, A2, B0, B1, B2, x[k]).hit ? 1u << k : 0u;
+    uint32_t e0 = ISECT_NONE, e1 = ISECT_NONE;
+    bool have = false;
+    double best = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = i + 1; j < 6; ++j) {
+            const bool both = ((mask >> i) & (mask >> j) & 1u) != 0u;
+            const double dx = x[i].x - x[j].x, dy = x[i].y - x[j].y, dz = x[i].z - x[j].z;
+            const double D = (dx * dx + dy * dy) + dz * dz;
+            if (both && (!have || D > best)) { best = D; e0 = (uint32_t)i; e1 = (uint32_t)j; }
+            have = have || both;
+        }
+    }
+    const uint32_t nh = (uint32_t)__popc(mask);
+    if (nh == 1u) e0 = (uint32_t)__ffs((int)mask) - 1u;
+    TriIsect r;
+    r.n = nh < 2u ? nh : 2u; r.mask = mask;
+    r.e[0] = isect_end(e0, A0, A1, A2, B0, B1, B2);
+    r.e[1] = isect_end(e1, A0, A1, A2, B0, B1, B2);
+    return r;
+}
+
 // ---------------------------------------------------------------- point against triangle (not reference behaviour)
 // pt_tri(p; p0, p1, p2): the distance from p to the triangle, the closest point q on it and where on the triangle q lies, in FP64 with
 // this operation order, IEEE divide and sqrt, no contraction; tri_distance's blocks and tri_distance's frame, so its band (above):

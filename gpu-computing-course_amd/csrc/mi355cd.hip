@@ -11,6 +11,7 @@
 #include "cd_ccd.h"
 #include "cd_between.h"
 #include "cd_witness.h"
+#include "cd_contour.h"
 #include "cd_rays.h"
 #include "cd_points.h"
 
@@ -111,7 +112,29 @@ struct WitnessBuf {
     }
 };
 
-// What a pair query (self-proximity, self-CCD, between two meshes) owns: counters, NSHARD shards of candidates, the result arrays
+// What the contour form of a contact query (cd_find_collisions_contour, cd_find_collisions_between_contour, cd_contour.h) adds to its
+// PairBuf, allocated on the first such call that asks for an output: the leaf positions of the reported pairs and the contour kernel's outputs
+struct ContourBuf {
+    uint2 *d_leaf = nullptr; uint32_t *d_faces = nullptr; uint8_t *d_code = nullptr; double *d_param = nullptr, *d_points = nullptr; uint64_t cap = 0;
+    void release() { dev_free(d_leaf); dev_free(d_faces); dev_free(d_code); dev_free(d_param); dev_free(d_points); cap = 0; }
+    int ensure(uint64_t cap_pairs)
+    {
+        const uint64_t want = cap_pairs > 0 ? cap_pairs : 1;
+        if (want <= cap) return CD_OK;
+        release();
+        hipError_t e = hipSuccess;
+        dev_alloc(e, d_leaf, sizeof(uint2) * want);
+        dev_alloc(e, d_faces, sizeof(uint32_t) * 2 * want);
+        dev_alloc(e, d_code, sizeof(uint8_t) * 3 * want);
+        dev_alloc(e, d_param, sizeof(double) * 6 * want);
+        dev_alloc(e, d_points, sizeof(double) * 6 * want);
+        if (e != hipSuccess) { release(); return -(int)e; }
+        cap = want;
+        return CD_OK;
+    }
+};
+
+// What a pair query (self-proximity, self-CCD, between two meshes, the self contour) owns: counters, NSHARD shards of candidates, the result arrays
 template <typename State>
 struct PairBuf {
     static constexpr bool HAS_TOI = std::is_same<State, CcdState>::value;   // (proximity reports no times; between-mesh always has the array)
@@ -119,6 +142,7 @@ struct PairBuf {
     uint2 *d_cand = nullptr; uint64_t shard_cap = 0;                        // candidates a shard
     uint32_t *d_pairs = nullptr; double *d_toi = nullptr, *d_dists = nullptr; uint64_t pairs_cap = 0;
     WitnessBuf wit;
+    ContourBuf con;
 
     int alloc_cand(uint64_t per)
     {
@@ -128,7 +152,7 @@ struct PairBuf {
         return e == hipSuccess ? CD_OK : -(int)e;
     }
     void release_results() { dev_free(d_pairs); dev_free(d_toi); dev_free(d_dists); pairs_cap = 0; }
-    void release() { state.release(); dev_free(d_cand); shard_cap = 0; release_results(); wit.release(); }
+    void release() { state.release(); dev_free(d_cand); shard_cap = 0; release_results(); wit.release(); con.release(); }
     // nt: the triangles whose candidates the shards take (16 a triangle to start with; grown on overflow)
     int ensure(uint32_t nt, uint64_t cap_pairs)
     {
@@ -331,6 +355,8 @@ struct cd_ctx {
     bool root_box_valid = false;
     // self-proximity (cd_find_proximity, cd_proximity.h): buffers of its own -- nothing the collision path keeps is touched
     PairBuf<ProxState> prox;
+    // the self contour (cd_find_collisions_contour, cd_contour.h): buffers of its own, allocated on first use
+    PairBuf<ProxState> cont;
     // continuous collision queries (cd_find_ccd, cd_ccd.h): buffers of their own, allocated on first use
     PairBuf<CcdState> ccd;
     DevArray<double> ccd_x1;                // the end positions, nv vertices
@@ -373,7 +399,7 @@ void free_all(cd_ctx *c)
     }
     for (int i = 0; i < 2; ++i) { hipFree(c->pp_keys[i]); hipFree(c->pp_vals[i]); }
     hipFree(c->pp_flags); hipFree(c->pp_os);
-    c->prox.release(); c->ccd.release(); c->bw.release(); c->ccd_x1.release(); c->bw_x1a.release(); c->bw_x1b.release();
+    c->prox.release(); c->cont.release(); c->ccd.release(); c->bw.release(); c->ccd_x1.release(); c->bw_x1a.release(); c->bw_x1b.release();
     for (SweptBuf &sw : c->swept) sw.release();
     c->rays.release(); c->points.release();
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
@@ -2328,9 +2354,12 @@ static int bw_enqueue(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_
                                                                                           a->d_boxes, b->d_boxes, dist, fa, fb, q.state.d, q.d_cand, q.shard_cap);
     }
     const dim3 grid(shard_blocks(na), NSHARD);
-    if (kind == BW_CONTACT)
+    if (kind == BW_CONTACT && !wleaf)
         k_between_exact<BW_CONTACT, false><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
                                                                                dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, nullptr);
+    else if (kind == BW_CONTACT)                                          // (the contour call)
+        k_between_exact<BW_CONTACT, true><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
+                                                                              dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, wleaf);
     else if (kind == BW_PROXIMITY && wleaf)
         k_between_exact<BW_PROXIMITY, true><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
                                                                                 dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, wleaf);
@@ -2432,6 +2461,89 @@ int cd_find_ccd_between_witness(cd_ctx *a, const double *verts_end_a, cd_ctx *b,
     const int rw = witness_results(a->stream, a->bw.wit, a->bw.state.h->n_pairs, cap_pairs, a, ax1, b, bx1, a->bw.d_toi, w);
     return rw ? rw : rc;
 }
+// ---- the contour of the contact queries (cd_contour.h) ------------------------------------------------------------------------------
+// NULL, or every member NULL: no contour kernel
+static bool contour_wanted(const cd_contour_out *w) { return w && (w->faces || w->code || w->param || w->points); }
+// Behind a pass that is finished and read back (np = its pair count): the contour kernel over the rows the caller gets, on stream s, and
+// the copies into w's arrays.  a, b: the contexts A's and B's triangles come from (the self call: the same one).
+static int contour_results(hipStream_t s, const ContourBuf &cb, uint64_t np, uint64_t cap_pairs, const cd_ctx *a, const cd_ctx *b, const cd_contour_out *w)
+{
+    const uint64_t take = std::min(np, cap_pairs);
+    if (!take) return CD_OK;
+    uint32_t *faces = w->faces ? cb.d_faces : nullptr;
+    uint8_t *code = w->code ? cb.d_code : nullptr;
+    double *param = w->param ? cb.d_param : nullptr, *points = w->points ? cb.d_points : nullptr;
+    k_pair_contour<<<cdiv(take, CONTOUR_THREADS), CONTOUR_THREADS, 0, s>>>(cb.d_leaf, take, a->d_leaf, a->d_perm[0], a->d_verts, b->d_leaf, b->d_perm[0], b->d_verts,
+                                                                          faces, code, param, points);
+    HIPCHK(hipGetLastError());
+    if (faces) HIPCHK(hipMemcpyAsync(w->faces, faces, sizeof(uint32_t) * 2 * take, hipMemcpyDeviceToHost, s));
+    if (code) HIPCHK(hipMemcpyAsync(w->code, code, sizeof(uint8_t) * 3 * take, hipMemcpyDeviceToHost, s));
+    if (param) HIPCHK(hipMemcpyAsync(w->param, param, sizeof(double) * 6 * take, hipMemcpyDeviceToHost, s));
+    if (points) HIPCHK(hipMemcpyAsync(w->points, points, sizeof(double) * 6 * take, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return CD_OK;
+}
+// The self call.  Own buffers (state, candidates, pairs, leaf positions, outputs): the collision path's counters, pair list, statistics, order
+// hint and captured step, and every other query's buffers, stay as they were.
+int cd_find_collisions_contour(cd_ctx *c, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested, const cd_contour_out *w)
+{
+    if (!c || (cap_pairs && !pairs)) return CD_ERR_ARG;
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    const bool wanted = contour_wanted(w);
+    PairBuf<ProxState> &q = c->cont;
+    int rc = q.ensure(c->nt, cap_pairs);
+    if (!rc && wanted) rc = q.con.ensure(cap_pairs);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const uint32_t n = c->nt;
+    for (;;) {
+        HIPCHK(hipMemsetAsync(q.state.d, 0, sizeof(ProxState), s));
+        k_prox_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(c->d_recs32, c->d_leaf, c->d_verts, c->d_boxes, (int)n, 0.0,
+                                                                                 c->d_os_ticket + 8, q.state.d, q.d_cand, q.shard_cap);
+        k_contour_exact<<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_verts, q.state.d, q.d_pairs, cap_pairs,
+                                                                                     wanted ? q.con.d_leaf : nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(q.state.h, q.state.d, sizeof(ProxState), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (!q.overflowed(rc)) { if (rc) return rc; break; }
+    }
+    if (n_tested) *n_tested = q.state.h->n_tested;
+    rc = q.results(pairs, nullptr, nullptr, cap_pairs, n_pairs);
+    if (!wanted || (rc != CD_OK && rc != CD_OVERFLOW)) return rc;
+    const int rw = contour_results(s, q.con, q.state.h->n_pairs, cap_pairs, c, c, w);
+    return rw ? rw : rc;
+}
+int cd_find_collisions_between_contour(cd_ctx *a, cd_ctx *b, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested, const cd_contour_out *w)
+{
+    if (!contour_wanted(w)) return cd_find_collisions_between(a, b, pairs, cap_pairs, n_pairs, n_tested);
+    int rc = bw_args(a, b, pairs, cap_pairs);
+    if (rc || (rc = bw_start(a, b, cap_pairs, false)) || (rc = a->bw.con.ensure(cap_pairs))) return rc;
+    if ((rc = bw_pass(a, b, BW_CONTACT, 0.0, cap_pairs, nullptr, nullptr, a->bw.con.d_leaf))) return rc;
+    if (n_tested) *n_tested = a->bw.state.h->n_tested;
+    rc = a->bw.results(pairs, nullptr, nullptr, cap_pairs, n_pairs);
+    if (rc != CD_OK && rc != CD_OVERFLOW) return rc;
+    const int rw = contour_results(a->stream, a->bw.con, a->bw.state.h->n_pairs, cap_pairs, a, b, w);
+    return rw ? rw : rc;
+}
+int cd_tri_isect_points(const double *tri, uint64_t n, uint8_t *code, double *param, double *points)
+{
+    if (!tri || !code) return CD_ERR_ARG;
+    if (n == 0) return CD_OK;
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_t = dev.in(tri, 18 * n);
+    uint8_t *d_c = dev.out<uint8_t>(3 * n);
+    double *d_p = param ? dev.out<double>(6 * n) : nullptr, *d_x = points ? dev.out<double>(6 * n) : nullptr;
+    if (dev.e == hipSuccess) {
+        k_tri_isect_points<<<strided_grid(n, CONTOUR_THREADS), CONTOUR_THREADS>>>(d_t, n, d_c, d_p, d_x);
+        dev.e = hipGetLastError();
+    }
+    dev.back(code, d_c, 3 * n);
+    dev.back(param, d_p, 6 * n);
+    dev.back(points, d_x, 6 * n);
+    return dev.rc();
+}
+
 // ---- ray queries (cd_rays.h) ------------------------------------------------------------------------------------------------------
 // Own buffers (rays, results, counters): nothing any other call keeps is touched.
 constexpr uint64_t RAY_BYTES = 7 * 8 + 8 + 16 + 4 + 4 + 1;                  // device bytes a ray: the ray, t, uv, face, ID, side

@@ -101,6 +101,50 @@ class _WitnessArrays:
         return Witness(self.faces[:got].copy(), self.points[:got].copy(), self.bary[:got].copy(), self.feature[:got].copy())
 
 
+class CdContourOut(C.Structure):
+    _fields_ = [("faces", C.c_void_p), ("code", C.c_void_p), ("param", C.c_void_p), ("points", C.c_void_p)]
+
+
+TERM_NONE = 7                       # tri_isect: a missing endpoint (fewer than two of the six edge-against-face terms hit)
+
+
+class Contour(collections.namedtuple("Contour", "faces code param points")):
+    """The intersection segments of the reported pairs (cd_contour_out), row k for pairs[k]: faces u32[n, 2] (indices in the face list of
+    the triangles that played A and B), code u8[n, 3] (endpoint 0 and 1 as term | side << 3, 7 = missing; the mask of the terms that
+    hit: 0-2 A's edges 01 / 12 / 20 against B's face, 3-5 B's edges against A's face), param f64[n, 2, 3] ((t, u, v) of the two
+    endpoints: t along the piercing edge, (u, v) on the pierced face), points f64[n, 2, 3]."""
+    __slots__ = ()
+
+    @property
+    def term(self):
+        """u8[n, 2]: the term of each endpoint (7: missing)."""
+        return self.code[:, :2] & 7
+
+    @property
+    def side(self):
+        """u8[n, 2]: 1 where the piercing edge meets the face that runs counter-clockwise as seen from the edge's start."""
+        return self.code[:, :2] >> 3
+
+    @property
+    def mask(self):
+        return self.code[:, 2]
+
+
+class _ContourArrays:
+    """The four arrays of a contour call with room for cap rows, and the cd_contour_out that points at them."""
+
+    def __init__(self, cap):
+        n = max(cap, 1)
+        self.faces = np.empty((n, 2), dtype=np.uint32)
+        self.code = np.empty((n, 3), dtype=np.uint8)
+        self.param = np.empty((n, 2, 3), dtype=np.float64)
+        self.points = np.empty((n, 2, 3), dtype=np.float64)
+        self.out = CdContourOut(self.faces.ctypes.data, self.code.ctypes.data, self.param.ctypes.data, self.points.ctypes.data)
+
+    def take(self, got):
+        return Contour(self.faces[:got].copy(), self.code[:got].copy(), self.param[:got].copy(), self.points[:got].copy())
+
+
 class CdMultiInfo(C.Structure):
     _fields_ = [("world", C.c_uint32), ("rank", C.c_uint32), ("n_peers", C.c_uint32), ("host_syncs", C.c_uint32), ("attempts", C.c_uint32),
                 ("failed_rank_plus1", C.c_uint32), ("sent_queries", C.c_uint64), ("recv_queries", C.c_uint64), ("local_pairs", C.c_uint64),
@@ -123,6 +167,7 @@ EXPORTS = [
     "cd_cast_rays", "cd_ray_tri_points",
     "cd_closest_points", "cd_pt_tri_points",
     "cd_find_proximity_witness", "cd_find_proximity_between_witness", "cd_find_ccd_witness", "cd_find_ccd_between_witness", "cd_tri_witness_points",
+    "cd_find_collisions_contour", "cd_find_collisions_between_contour", "cd_tri_isect_points",
 ]
 
 _lib = None
@@ -211,6 +256,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_find_ccd_witness.argtypes = lib.cd_find_ccd.argtypes + [wp]
     lib.cd_find_ccd_between_witness.argtypes = lib.cd_find_ccd_between.argtypes + [wp]
     lib.cd_tri_witness_points.argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
+    cp = C.POINTER(CdContourOut)
+    lib.cd_find_collisions_contour.argtypes = [vp, vp, C.c_uint64, u64p, u64p, cp]
+    lib.cd_find_collisions_between_contour.argtypes = lib.cd_find_collisions_between.argtypes + [cp]
+    lib.cd_tri_isect_points.argtypes = [vp, C.c_uint64, vp, vp, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -469,6 +518,32 @@ class CollisionDetector:
         return self._ccd_call(self.lib.cd_self_ccd, "cd_self_ccd", verts_end, dist, cap)
 
     # ---- queries between this mesh (a) and another context's (b): pairs (ID in self, ID in other), self's triangle first
+    def find_collisions_contour(self, cap: int = 1 << 20):
+        """cd_find_collisions_contour: (pairs[n, 2] (smaller ID, larger ID), n, rc, Contour) -- find_collisions' pair set from a pass of
+        its own, and per pair the segment the two triangles cut each other in.  self.contour_tested: pairs that reached tri_contact.  The
+        tree must be built from the current vertices."""
+        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        ca = _ContourArrays(cap)
+        n, tested = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.cd_find_collisions_contour(self._ctx, _ptr(pairs) if cap else None, cap, C.byref(n), C.byref(tested), C.byref(ca.out))
+        self._chk("cd_find_collisions_contour", rc, allow=(CD_OK, CD_OVERFLOW))
+        self.contour_tested = tested.value
+        got = min(n.value, cap)
+        return pairs[:got].copy(), n.value, rc, ca.take(got)
+
+    def find_collisions_between_contour(self, other, cap: int = 1 << 20):
+        """cd_find_collisions_between_contour: find_collisions_between's (pairs, n, rc) and a Contour (A: self's triangle; faces index each
+        context's own face list)."""
+        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        ca = _ContourArrays(cap)
+        n, tested = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.cd_find_collisions_between_contour(self._ctx, other._ctx, _ptr(pairs) if cap else None, cap, C.byref(n), C.byref(tested),
+                                                         C.byref(ca.out))
+        self._chk("cd_find_collisions_between_contour", rc, allow=(CD_OK, CD_OVERFLOW))
+        self.between_tested = tested.value
+        got = min(n.value, cap)
+        return pairs[:got].copy(), n.value, rc, ca.take(got)
+
     def find_collisions_between(self, other, cap: int = 1 << 20):
         """cd_find_collisions_between(self, other): (pairs[n, 2] (ID in self, ID in other), n, rc); n may exceed cap (rc = CD_OVERFLOW,
         the first cap pairs are returned).  self.between_tested: pairs whose FP64 boxes overlap strictly.  Both trees must be built."""
@@ -817,6 +892,21 @@ def tri_witness_points(tri):
     if rc != CD_OK:
         raise CdError("cd_tri_witness_points", rc)
     return dist, points, bary, feature
+
+
+def tri_isect_points(tri, want_param=True, want_points=True):
+    """tri_isect (the segment two triangles cut each other in) on explicit vertex positions [n, 6, 3], on the device
+    (cd_tri_isect_points): (code[n, 3] (endpoint 0, endpoint 1 as term | side << 3, the mask), param[n, 2, 3] ((t, u, v) of the two
+    endpoints), points[n, 2, 3]); param / points are None when not wanted (the call then gets NULL)."""
+    t = np.ascontiguousarray(tri, dtype=np.float64).reshape(-1, 18)
+    n = t.shape[0]
+    code = np.zeros((n, 3), dtype=np.uint8)
+    param = np.zeros((n, 2, 3), dtype=np.float64) if want_param else None
+    points = np.zeros((n, 2, 3), dtype=np.float64) if want_points else None
+    rc = load_library().cd_tri_isect_points(_ptr(t), n, _ptr(code), _ptr(param), _ptr(points))
+    if rc != CD_OK:
+        raise CdError("cd_tri_isect_points", rc)
+    return code, param, points
 
 
 def pack_rays(origins, dirs, tmax=np.inf) -> np.ndarray:

@@ -551,6 +551,67 @@ int cd_find_ccd_between_witness(cd_ctx *a, const double *verts_end_a, cd_ctx *b,
  * pin of the device function. */
 int cd_tri_witness_points(const double *tri, uint64_t n, double *dist, double *points, double *bary, uint8_t *feature);
 
+/* ---- the intersection segment of pairs in contact: the contour (not reference behaviour) ----
+ * The witness has nothing to say about a pair in contact (features 7 / 7).  For such a pair the answer is the segment in which the two
+ * triangles cut each other: which edge of which triangle pierces the other's face, where on that edge and on that face, from which
+ * side.  Chained over the pairs the segments are the intersection contour of the mesh(es).
+ * tri_isect(A, B) -> (n, mask, two endpoints): six evaluations of ray_tri (the ray section below) in this order and a selection rule;
+ * FP64, ray_tri's operation order, IEEE divide, no contraction, a NaN fails every comparison (csrc/cd_math.h):
+ *   term k = 0, 1, 2: A's edge from A_k to A_(k+1 mod 3) against B's face (B0, B1, B2);
+ *   term k = 3, 4, 5: B's edge from B_(k-3) to B_(k-2 mod 3) against A's face (A0, A1, A2);
+ *   r_k = ray_tri(o, d, tmax = 1; p0, p1, p2) with o the edge's start and d = end - start per coordinate (one rounding).  On a hit
+ *   x_k = o + t d per coordinate, the product rounded and then the sum: the point ray_tri's gate forms.
+ *   mask: bit k is set when term k hit.
+ *   No hit: n = 0, both endpoints have term 7 and everything else is 0 -- coplanar pairs (every edge is parallel to the other face),
+ *   touching pairs that the gate or the range checks reject, degenerate triangles.
+ *   One hit: n = 1; endpoint 0 is that term, endpoint 1 has term 7 and zeros.
+ *   Two or more hits: n = 2.  The pairs (i, j), i < j, of hit terms are taken in lexicographic order, each with
+ *   D = (dx dx + dy dy) + dz dz of x_i - x_j; a later pair replaces the kept one only when its D is STRICTLY larger (an earlier pair
+ *   keeps a tie).  Endpoint 0 is i, endpoint 1 is j: the two hit points that lie farthest apart.  With exactly two hits -- every pair
+ *   in general position -- these are the two hits in term order.
+ *   Per endpoint: the term 0..5; ray_tri's t, the parameter along the piercing edge from its start; (u, v), the barycentrics on the
+ *   pierced face (x = (1 - u - v) p0 + u p1 + v p2); side, 1 when the edge, in its direction, meets the face whose vertices run
+ *   counter-clockwise as seen from the edge's start; the point x.
+ * Finite input gives no NaN in any output.  Scaling all six vertices by 2^k scales x exactly and changes nothing else while the
+ * coordinates stay inside ray_tri's band.  tri_isect(B, A) hits exactly the terms (k + 3) mod 6, with bit-identical t, u, v, side, x --
+ * each term is the same ray_tri call; only the order of the two endpoints may differ.  Both endpoints lie on both triangles within
+ * 2^-42 M, M the largest |coordinate| of the six vertices: a condition on the inputs, as the witness's bound (the numpy restatement
+ * measured at most 2^-44.58 M over every input the tests use -- unit-cube pairs, pairs of diameter 0.2, the same offset by 2^20 + 0.37,
+ * integer-grid pairs, slivers, degenerate triangles, the test meshes; tests/test_isect_ref.py re-checks it).  The definition applies no
+ * contact test: a pair tri_contact rejects may have hits and a pair it accepts may have none (coplanar pairs); on inputs in general
+ * position a pair in contact has exactly two.
+ *
+ * The two calls below are the contact queries with one trailing argument.  Each member of w holds cap_pairs rows -- faces 2, code 3,
+ * param 6, points 6 elements a row -- and may be NULL.  Row k describes pairs[k]:
+ *   faces[2 k], faces[2 k + 1]: the indices in cd_create's face list of the triangles that played A and B (with custom or repeated IDs
+ *   this is what tells which face a reported ID is).
+ *   code[3 k], code[3 k + 1]: endpoint 0 and endpoint 1 as term | side << 3, 7 for a missing endpoint;  code[3 k + 2]: the mask.
+ *   param[6 k ..]: t, u, v of endpoint 0, then of endpoint 1.    points[6 k ..]: x of endpoint 0, then of endpoint 1.
+ * cd_find_collisions_between_contour: the pair set, *n_tested, the errors and the overflow behaviour are cd_find_collisions_between's;
+ * A is a's triangle and each face index is into its own context's list.  A NULL w (or one whose members are all NULL) makes it the
+ * plain call.
+ * cd_find_collisions_contour: as a set of (smaller ID, larger ID) rows the pair set is cd_find_collisions' on the same tree -- the FP64
+ * boxes overlap strictly, no vertex index is shared, the IDs differ (pairs of equal IDs are never reported), and tri_contact holds with
+ * the smaller ID's triangle as P.  A is the smaller ID's triangle.  *n_tested: the pairs that reach tri_contact (after the neighbour
+ * filter, the ID rule and the strict box test), a number of the mesh alone -- not cd_stats' pairs_tested, which depends on the walk.
+ * It needs a tree built from the current vertices (cd_build_tree, or a step): CD_ERR_ORDER otherwise.  CD_OVERFLOW with the true
+ * *n_pairs when the pairs do not fit; nothing is written past cap_pairs in any array.  It is a pass of its own behind the tree, not
+ * the collision path's: cd_stats, the last pair list (cd_sorted_pairs), the order hint, a captured step and every other query's
+ * buffers stay as they were, and bench.py's step runs the kernels it ran before.  With a NULL w the call still runs and returns the
+ * pairs: a second implementation of the pair set.
+ * The result depends on the mesh(es) only, row by row (the order of the rows is free): not on the Morton frame, CD_OPT_TRAVERSAL, the
+ * cell table or the build variant.  The calls keep device buffers of their own (grown on demand; cd_destroy frees them) and cost one
+ * more kernel over the reported pairs and one more host synchronisation. */
+typedef struct cd_contour_out { uint32_t *faces; uint8_t *code; double *param; double *points; } cd_contour_out;
+int cd_find_collisions_contour(cd_ctx *ctx, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs,
+                               uint64_t *n_tested, const cd_contour_out *w);
+int cd_find_collisions_between_contour(cd_ctx *a, cd_ctx *b, uint32_t *pairs, uint64_t cap_pairs,
+                                       uint64_t *n_pairs, uint64_t *n_tested, const cd_contour_out *w);
+/* tri_isect on explicit positions (host pointers; no context): tri is n x 18 doubles as for cd_tri_contact_points.  code[3 k ..],
+ * param[6 k ..], points[6 k ..] as above.  code is required; param and points may be NULL.  No finiteness check, no contact test, no
+ * box test: the arithmetic decides.  The pin of the device function. */
+int cd_tri_isect_points(const double *tri, uint64_t n, uint8_t *code, double *param, double *points);
+
 /* ---- ray queries: closest hit and occlusion (not reference behaviour) ----
  * A ray is seven doubles: an origin o, a direction d and an upper end tmax.  o and d are finite and d is not all zero; d is NOT
  * normalised, so t is in units of d; 0 <= tmax <= +inf and the ray's parameter range is [0, tmax] (a segment from a to b: o = a,
