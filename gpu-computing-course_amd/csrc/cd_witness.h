@@ -7,7 +7,7 @@
 //       (leaf_a, ax0 / ax1), B's from (leaf_b, bx0 / bx1) -- the self calls pass their own mesh twice.  toi == NULL: the positions are
 //       x0 (proximity).  Else row k is evaluated where the advancement reported it: x1 itself when toi[k] == 1, otherwise
 //       a + toi (b - a) per coordinate as ccd_at writes it (x0's values at toi == 0).  faces: perm[] of the two leaves, the indices in
-//       cd_create's face list.  Every output may be NULL.
+//       cd_create's face list.  Every output may be NULL.  A row whose leaf of A is WITNESS_NO_PAIR gets zeros.
 //   k_tri_witness_points : tri_witness on explicit positions (cd_tri_witness_points): the pin of the device code.
 #pragma once
 #include "cd_between.h"
@@ -15,6 +15,7 @@
 namespace cd {
 
 constexpr int WITNESS_THREADS = 256;
+constexpr uint32_t WITNESS_NO_PAIR = 0xffffffffu;     // in wleaf[k].x: row k has no pair (only cd_nearest_between leaves such rows)
 
 // every output may be NULL
 __device__ __forceinline__ void witness_store(const TriWitness &w, unsigned long long k, double *__restrict__ points, double *__restrict__ bary,
@@ -51,6 +52,11 @@ __global__ __launch_bounds__(WITNESS_THREADS) void k_pair_witness(const uint2 *_
     const unsigned long long k = (unsigned long long)blockIdx.x * WITNESS_THREADS + threadIdx.x;
     if (k >= n) return;
     const uint2 l = wleaf[k];
+    if (l.x == WITNESS_NO_PAIR) {                                        // cd_nearest_between's "nothing" row: no leaves, feature 0 / 0 and zeros
+        if (faces) { faces[2 * k] = WITNESS_NO_PAIR; faces[2 * k + 1] = WITNESS_NO_PAIR; }
+        witness_store(TriWitness{}, k, points, bary, feature);
+        return;
+    }
     if (faces) { faces[2 * k] = perm_a[l.x]; faces[2 * k + 1] = perm_b[l.y]; }
     if (!points && !bary && !feature) return;
     const LeafTri A = leaf_a[l.x], B = leaf_b[l.y];

@@ -14,6 +14,7 @@
 #include "cd_contour.h"
 #include "cd_rays.h"
 #include "cd_points.h"
+#include "cd_nearest.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -373,6 +374,10 @@ struct cd_ctx {
     // closest-point queries (cd_closest_points, cd_points.h): buffers of their own, as the rays'.
     // points.block: points [4 n] | dist [n] | closest [3 n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | feature [n] | side [n] (u8)
     ItemBuf<PointState> points;
+    // nearest triangle / separation distance against another mesh (cd_nearest_between, cd_nearest.h) with this context as a: buffers of
+    // their own, na + 1 rows (the last one: CD_NEAREST_MIN's).
+    // nearest.block: dist [n] | points [6 n] | bary [4 n] (doubles) | leaf pair [n] (uint2) | faces [2 n] | ids [2 n] (u32) | feature [2 n] (u8)
+    ItemBuf<NearestState> nearest;
 };
 
 namespace {
@@ -401,7 +406,7 @@ void free_all(cd_ctx *c)
     hipFree(c->pp_flags); hipFree(c->pp_os);
     c->prox.release(); c->cont.release(); c->ccd.release(); c->bw.release(); c->ccd_x1.release(); c->bw_x1a.release(); c->bw_x1b.release();
     for (SweptBuf &sw : c->swept) sw.release();
-    c->rays.release(); c->points.release();
+    c->rays.release(); c->points.release(); c->nearest.release();
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -2665,6 +2670,59 @@ int cd_pt_tri_points(const double *points, const double *tri, uint64_t n, double
     dev.back(feature, d_f, n);
     dev.back(side, d_s, n);
     return dev.rc();
+}
+// ---- nearest triangle and separation distance between two meshes (cd_nearest.h) ---------------------------------------------------
+// Everything runs on a's stream, in buffers a owns (rows, leaf pairs, witness, counters): nothing any other call keeps is touched.  Both
+// trees are finished (every call of the library blocks); b's stream is drained all the same before its records are read on a's.
+constexpr uint64_t NEAREST_BYTES = 8 + 48 + 32 + 8 + 8 + 8 + 2;             // device bytes a row: dist, points, bary, leaf pair, faces, IDs, feature
+int cd_nearest_between(cd_ctx *a, cd_ctx *b, double rmax, int flags, uint32_t *faces, uint32_t *ids, double *dist, const cd_witness_out *w, cd_nearest_info *info)
+{
+    const bool mn = flags == CD_NEAREST_MIN;
+    int rc = bw_args(a, b, faces, 1);                                       // (NULL faces: an argument error)
+    if (rc) return rc;
+    if (!(rmax >= 0.0) || (flags != 0 && !mn)) return CD_ERR_ARG;          // (a NaN rmax fails the comparison)
+    if (a->stage < ST_REFIT || b->stage < ST_REFIT) return CD_ERR_ORDER;
+    const uint64_t na = a->nt;
+    if ((rc = a->nearest.ensure(na + 1, NEAREST_BYTES))) return rc;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    hipStream_t s = a->stream;
+    const uint64_t cap = a->nearest.block.cap;
+    double *d_dist = reinterpret_cast<double *>(a->nearest.block.d), *d_points = d_dist + cap, *d_bary = d_points + 6 * cap;
+    uint2 *d_leaf = reinterpret_cast<uint2 *>(d_bary + 4 * cap);
+    uint32_t *d_faces = reinterpret_cast<uint32_t *>(d_leaf + cap), *d_ids = d_faces + 2 * cap;
+    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + 2 * cap);
+    NearestState *st = a->nearest.state.d, *h = a->nearest.state.h;
+    *h = NearestState{};
+    std::memcpy(&h->min_bits, &rmax, sizeof rmax);                          // the shared bound starts at rmax
+    HIPCHK(hipMemcpyAsync(st, h, sizeof(NearestState), hipMemcpyHostToDevice, s));
+    const uint32_t grid = cdiv(na, NEAREST_THREADS);
+    if (mn) {
+        k_nearest_between<true><<<grid, NEAREST_THREADS, 0, s>>>(b->d_recs32, b->d_root, b->d_leaf, b->d_perm[0], b->d_verts, b->d_boxes, (int)b->nt,
+                                                                 a->d_leaf, a->d_perm[0], a->d_verts, a->d_boxes, (int)na, rmax, st, d_faces, d_ids, d_dist, d_leaf);
+        k_nearest_min<<<1, NEAREST_MIN_THREADS, 0, s>>>(na, na, st, d_faces, d_ids, d_dist, d_leaf);
+    } else {
+        k_nearest_between<false><<<grid, NEAREST_THREADS, 0, s>>>(b->d_recs32, b->d_root, b->d_leaf, b->d_perm[0], b->d_verts, b->d_boxes, (int)b->nt,
+                                                                  a->d_leaf, a->d_perm[0], a->d_verts, a->d_boxes, (int)na, rmax, st, d_faces, d_ids, d_dist, d_leaf);
+    }
+    const uint64_t first = mn ? na : 0, rows = mn ? 1 : na;                 // the rows the caller gets
+    const bool wit = w && (w->points || w->bary || w->feature);
+    if (wit)
+        k_pair_witness<false><<<cdiv(rows, WITNESS_THREADS), WITNESS_THREADS, 0, s>>>(d_leaf + first, rows, a->d_leaf, a->d_perm[0], a->d_verts, nullptr,
+                                                                                      b->d_leaf, b->d_perm[0], b->d_verts, nullptr, nullptr, nullptr,
+                                                                                      w->points ? d_points + 6 * first : nullptr, w->bary ? d_bary + 4 * first : nullptr,
+                                                                                      w->feature ? d_feat + 2 * first : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h, st, sizeof(NearestState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(faces, d_faces + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
+    if (w && w->faces) HIPCHK(hipMemcpyAsync(w->faces, d_faces + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
+    if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
+    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist + first, sizeof(double) * rows, hipMemcpyDeviceToHost, s));
+    if (w && w->points) HIPCHK(hipMemcpyAsync(w->points, d_points + 6 * first, sizeof(double) * 6 * rows, hipMemcpyDeviceToHost, s));
+    if (w && w->bary) HIPCHK(hipMemcpyAsync(w->bary, d_bary + 4 * first, sizeof(double) * 4 * rows, hipMemcpyDeviceToHost, s));
+    if (w && w->feature) HIPCHK(hipMemcpyAsync(w->feature, d_feat + 2 * first, sizeof(uint8_t) * 2 * rows, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (info) { info->n_found = h->n_found; info->node_visits = h->node_visits; info->tri_tests = h->tri_tests; }
+    return CD_OK;
 }
 }  // extern "C"
 

@@ -72,6 +72,20 @@ CD_POINT_ANY = 1
 POINT_NONE = 0xFFFFFFFF
 
 
+class CdNearestInfo(C.Structure):
+    _fields_ = [("n_found", C.c_uint64), ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64)]
+
+
+CD_NEAREST_MIN = 1
+NEAREST_NONE = 0xFFFFFFFF
+
+
+class Nearest(collections.namedtuple("Nearest", "faces ids dist witness info")):
+    """cd_nearest_between's rows: faces u32[n, 2] (face of self, face of other; NEAREST_NONE twice when nothing is within rmax),
+    ids u32[n, 2], dist f64[n] (+inf then), witness (a Witness over the same rows, or None), info (CdNearestInfo)."""
+    __slots__ = ()
+
+
 class CdWitnessOut(C.Structure):
     _fields_ = [("faces", C.c_void_p), ("points", C.c_void_p), ("bary", C.c_void_p), ("feature", C.c_void_p)]
 
@@ -168,6 +182,7 @@ EXPORTS = [
     "cd_closest_points", "cd_pt_tri_points",
     "cd_find_proximity_witness", "cd_find_proximity_between_witness", "cd_find_ccd_witness", "cd_find_ccd_between_witness", "cd_tri_witness_points",
     "cd_find_collisions_contour", "cd_find_collisions_between_contour", "cd_tri_isect_points",
+    "cd_nearest_between",
 ]
 
 _lib = None
@@ -260,6 +275,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_find_collisions_contour.argtypes = [vp, vp, C.c_uint64, u64p, u64p, cp]
     lib.cd_find_collisions_between_contour.argtypes = lib.cd_find_collisions_between.argtypes + [cp]
     lib.cd_tri_isect_points.argtypes = [vp, C.c_uint64, vp, vp, vp]
+    lib.cd_nearest_between.argtypes = [vp, vp, C.c_double, C.c_int, vp, vp, vp, wp, C.POINTER(CdNearestInfo)]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -642,6 +658,23 @@ class CollisionDetector:
                                         C.byref(info))
         self._chk("cd_closest_points", rc)
         return face, ids, dist, closest, uv, feature, side, info
+
+    # ---- nearest triangle of another mesh, and the separation distance (cd_nearest_between)
+    def nearest_between(self, other, rmax=np.inf, minimum: bool = False, witness: bool = False):
+        """cd_nearest_between on the two trees that are there, self as a.  -> Nearest(faces, ids, dist, witness, info): one row per
+        triangle of self in face-list order -- of other's triangles with tri_distance <= rmax the smallest (dist, ID, face index) --
+        or, with minimum, the ONE row of the separation distance: the smallest (dist, ID a, face a, ID b, face b) over all pairs.
+        Nothing within rmax: faces NEAREST_NONE, dist +inf, everything else 0.  witness: a Witness of the rows' pairs (else None)."""
+        n = 1 if minimum else self.nt
+        faces = np.empty((n, 2), dtype=np.uint32)
+        ids = np.empty((n, 2), dtype=np.uint32)
+        dist = np.empty(n, dtype=np.float64)
+        wa = _WitnessArrays(n) if witness else None
+        info = CdNearestInfo()
+        rc = self.lib.cd_nearest_between(self._ctx, other._ctx, float(rmax), CD_NEAREST_MIN if minimum else 0, _ptr(faces), _ptr(ids), _ptr(dist),
+                                         C.byref(wa.out) if witness else None, C.byref(info))
+        self._chk("cd_nearest_between", rc)
+        return Nearest(faces, ids, dist, wa.take(n) if witness else None, info)
 
     def find_collisions(self, cap: int = 1 << 20):
         return self._pairs_call(self.lib.cd_find_collisions, "cd_find_collisions", cap)

@@ -709,6 +709,36 @@ int cd_closest_points(cd_ctx *ctx, const double *points, uint64_t n, int flags, 
 int cd_pt_tri_points(const double *points, const double *tri, uint64_t n, double *dist, double *closest, double *uv,
                      uint8_t *feature, uint8_t *side);
 
+/* ---- nearest triangle and separation distance between two meshes (not reference behaviour) ----
+ * The threshold-free between-mesh question: how far is mesh a from mesh b, and where are they closest?  The per-pair functions are
+ * tri_distance (the proximity section) and tri_witness (the witness section), a's triangle as the first argument, as in every
+ * between call.  rmax is a search radius, 0 <= rmax <= +inf.
+ *
+ * flags = 0, per triangle: na rows, na the number of a's triangles.  Row i belongs to face i of a's face list from cd_create.  Of the
+ * triangles B of b with tri_distance(A_i, B) <= rmax (closed) the winner is the one with the smallest (dist, ID of B, face index of B)
+ * in lexicographic order.  faces[2 i] = i, faces[2 i + 1] = the winner's index in b's face list; ids[2 i], ids[2 i + 1]: the two IDs;
+ * dist[i]: tri_distance(A_i, B), bit for bit.  When nothing is within rmax both faces are 0xFFFFFFFF, dist[i] = +inf and every other
+ * output of the row is 0.  With rmax = +inf every row finds a triangle.
+ * flags = CD_NEAREST_MIN, the separation distance: exactly ONE row.  Over all pairs with dist <= rmax the pair with the smallest
+ * (dist, ID in a, face in a, ID in b, face in b); the "nothing" row above when no pair is within rmax.  By definition it is the
+ * lexicographic minimum over the rows of the flags = 0 call.
+ * ids and dist may be NULL.  w (may be NULL, and so may each of its members): points, bary and feature of a row are
+ * tri_witness(A, B) of that row's pair -- its dist is dist[row] bit for bit, by tri_witness's own contract; a pair in contact is at 0
+ * with features 7 / 7 and zeros; w->faces receives the same values as faces; a "nothing" row gets features 0 / 0 and zeros.
+ * info (may be NULL): rows that found a triangle, boxes tested, tri_distance evaluations -- numbers of this run and this tree, not of
+ * the meshes; with CD_NEAREST_MIN the last two may differ from run to run (the lanes share a shrinking bound), the result may not.
+ * Guarantee: the result depends on the two meshes and rmax only -- not on either Morton frame, CD_OPT_TRAVERSAL, CD_OPT_CELL_TABLE,
+ * the build variant or the run -- over the band of coordinate magnitudes of cd_find_proximity.  Both contexts are left as they were:
+ * cd_stats, the last pair list, the order hint, a captured CD_OPT_GRAPH step and every other query's buffers.  The call keeps device
+ * buffers of its own in a (grown on demand; cd_destroy frees them) and runs on a's stream with one host synchronisation.
+ * CD_ERR_ARG: a NULL context; a == b; contexts on different HIP devices; rmax NaN or negative; flags other than 0 / CD_NEAREST_MIN;
+ * NULL faces -- checked on the host before anything is launched, and nothing is written then.  CD_ERR_ORDER unless both contexts have
+ * a tree of their current vertices.  There is no CD_OVERFLOW: the row count is fixed. */
+typedef struct cd_nearest_info { uint64_t n_found, node_visits, tri_tests; } cd_nearest_info;
+enum { CD_NEAREST_MIN = 1 };
+int cd_nearest_between(cd_ctx *a, cd_ctx *b, double rmax, int flags, uint32_t *faces, uint32_t *ids, double *dist,
+                       const cd_witness_out *w, cd_nearest_info *info);
+
 /* Library / build identification: "mi355cd <version> gfx950". */
 const char *cd_version(void);
 
