@@ -15,17 +15,22 @@ import numpy as np
 
 import between_ref as br
 import ccd_ref as cr
+import isect_ref as ir
 import mi355_synth as synth
+import mi355cd
+import nearest_ref as nr
 import oracle
 import point_ref as ptr
 import proximity_ref as pr
 import ray_ref as rr
 import swept_ref as sr
+import witness_ref as wr
 from test_between_gpu import _same_ccd as same_between_ccd, _same_contact as same_between_contact, _same_prox as same_between_prox  # noqa: F401
 from test_ccd_gpu import _same as _same_ccd
 from test_points_gpu import _same as same_points
 from test_proximity_gpu import _same as _same_prox
 from test_rays_gpu import _same as same_rays  # noqa: F401
+from test_witness_gpu import _same_as_plain as same_as_plain  # noqa: F401
 
 NQ = 1000                       # rays, and points, a frame: 15 full waves and a ragged one of 40
 MISS = 0xFFFFFFFF
@@ -302,6 +307,27 @@ def want_ccd(name, f):
     return cr.ccd_pairs(s.frames[f], x1(name, f), s.vidx, None, ccd_dist(name, f), counts=True, brute=_brute(s))
 
 
+@functools.lru_cache(maxsize=None)
+def want_prox_witness(name, f):
+    """witness_ref's Rows of cd_find_proximity_witness on frame f, sorted by (face a, face b)."""
+    s = seq(name)
+    return wr.witness_pairs(s.frames[f], s.vidx, dist=prox_dist(name, f), brute=_brute(s))
+
+
+@functools.lru_cache(maxsize=None)
+def want_ccd_witness(name, f):
+    """witness_ref's Rows of cd_find_ccd_witness on frame f moving to x1(name, f)."""
+    s = seq(name)
+    return wr.witness_pairs(s.frames[f], s.vidx, dist=ccd_dist(name, f), verts_end=x1(name, f), brute=_brute(s))
+
+
+@functools.lru_cache(maxsize=None)
+def want_contour(name, f):
+    """isect_ref's Rows of cd_find_collisions_contour on frame f (with `tested`, the pairs that reach tri_contact)."""
+    s = seq(name)
+    return ir.contour_pairs(s.frames[f], s.vidx, brute=_brute(s))
+
+
 def _pipeline(mode, v, vidx):
     if mode == "auto":
         off, span, lay = oracle.auto_frame(v, vidx)
@@ -471,11 +497,102 @@ def same_step(pairs, n, rc, pairs_tested, step, what=""):
     assert pairs_tested == step["stats"].pairs_tested, (what, pairs_tested, step["stats"].pairs_tested)
 
 
+def _same_bytes(got, want, what):
+    """Two arrays of one type and shape with the same bytes: no tolerance, -0.0 is not 0.0 and a NaN equals only itself."""
+    g, w = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert g.dtype == w.dtype and g.shape == w.shape, (what, g.dtype, w.dtype, g.shape, w.shape)
+    if g.tobytes() != w.tobytes():
+        bad = np.nonzero((g.reshape(g.shape[0], -1) != w.reshape(w.shape[0], -1)).any(axis=1))[0]
+        raise AssertionError((what, "rows that differ", bad.size, bad[:4].tolist()))
+
+
+def witness_rows(got) -> wr.Rows:
+    """A witness call's (pairs, [toi,] dists, n, rc, Witness) as witness_ref's Rows, sorted by (face a, face b)."""
+    *cols, _, _, wit = got
+    toi = cols[1] if len(cols) == 3 else None
+    return wr.Rows(*wr.sort_rows(wit.faces, cols[0], toi, cols[-1], wit.points, wit.bary, wit.feature))
+
+
+def witness_call(rows: wr.Rows, rc=0):
+    """What a witness call that found `rows` returns."""
+    cols = (rows.pairs, rows.dists) if rows.toi is None else (rows.pairs, rows.toi, rows.dists)
+    return cols + (rows.faces.shape[0], rc, mi355cd.Witness(rows.faces, rows.points, rows.bary, rows.feature))
+
+
+def same_witness(got, want: wr.Rows, what=""):
+    """got: the tuple of cd_find_proximity_witness / cd_find_ccd_witness or of their between-mesh forms; want: witness_ref's Rows.
+    The return code, the count, then every column of the rows in (face a, face b) order by its bytes."""
+    n, rc = got[-3], got[-2]
+    assert rc == 0 and n == want.faces.shape[0], (what, rc, n, want.faces.shape[0])
+    g = witness_rows(got)
+    assert (g.toi is None) == (want.toi is None), what
+    for k in wr.Rows._fields:
+        if getattr(want, k) is not None:
+            _same_bytes(getattr(g, k), getattr(want, k), (what, k))
+
+
+def contour_rows(got, tested=None) -> ir.Rows:
+    """A contour call's (pairs, n, rc, Contour) as isect_ref's Rows, sorted by (face a, face b)."""
+    pairs, _, _, con = got
+    n = con.faces.shape[0]
+    return ir.Rows(*ir.sort_got(con.faces, pairs, con.code, con.param.reshape(n, 6), con.points.reshape(n, 6)), tested)
+
+
+def contour_call(rows: ir.Rows, rc=0):
+    """What a contour call that found `rows` returns."""
+    return rows.pairs, rows.faces.shape[0], rc, mi355cd.Contour(rows.faces, rows.code, rows.param.reshape(-1, 2, 3), rows.points.reshape(-1, 2, 3))
+
+
+def same_contour(got, want: ir.Rows, what="", tested=None):
+    """got: cd_find_collisions_contour's / cd_find_collisions_between_contour's tuple; want: isect_ref's Rows; tested: the call's
+    n_tested, compared with the restatement's where the restatement has one."""
+    assert got[2] == 0 and got[1] == want.faces.shape[0], (what, got[2], got[1], want.faces.shape[0])
+    g = contour_rows(got)
+    for k in ("faces", "pairs", "code", "param", "points"):
+        _same_bytes(getattr(g, k), getattr(want, k), (what, k))
+    if tested is not None and want.tested is not None:
+        assert tested == want.tested, (what, tested, want.tested)
+
+
+def unordered_pairs(pairs):
+    """oracle.pair_set of the pairs as (smaller ID, larger ID)."""
+    p = np.asarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    return oracle.pair_set(np.stack([p.min(axis=1), p.max(axis=1)], axis=1))
+
+
+def same_pair_set(pairs, want_pairs, what=""):
+    """The contour call's pairs against the collision step's: one set."""
+    assert np.array_equal(unordered_pairs(pairs), unordered_pairs(want_pairs)), what
+
+
+def nearest_call(rows: nr.NearestRows):
+    """What cd_nearest_between with a witness returns for `rows`."""
+    found = int((rows.faces[:, 0] != nr.NONE).sum())
+    return mi355cd.Nearest(rows.faces, rows.ids, rows.dist, mi355cd.Witness(rows.faces, rows.points, rows.bary, rows.feature), mi355cd.CdNearestInfo(found, 0, 0))
+
+
+def same_nearest(got, want: nr.NearestRows, what=""):
+    """got: a Nearest with its witness (rows in a's face order, or the one row of CD_NEAREST_MIN); want: nearest_ref's NearestRows."""
+    w = got.witness
+    for k, x, y in (("faces", got.faces, want.faces), ("ids", got.ids, want.ids), ("dist", got.dist, want.dist), ("witness faces", w.faces, want.faces),
+                    ("points", w.points, want.points), ("bary", w.bary, want.bary), ("feature", w.feature, want.feature)):
+        _same_bytes(x, y, (what, k))
+    found = int((want.faces[:, 0] != nr.NONE).sum())
+    assert got.info.n_found == found, (what, got.info.n_found, found)
+
+
 # ---------------------------------------------------------------- between two meshes
 BETWEEN_FRAMES = 6
-BETWEEN_SCHEDULES = ("a_moves", "b_moves", "both_move")
+APART = "both_move_apart"
+BETWEEN_SCHEDULES = ("a_moves", "b_moves", "both_move", APART)
 BETWEEN_DIST = SLIDE_QUAD[0] / 4
 BETWEEN_CCD_DIST = SLIDE_QUAD[0] / 10
+NEAREST_R = 2 * SLIDE_QUAD[0]   # cd_nearest_between's radii: NEAREST_R and a quarter of it; +inf for CD_NEAREST_MIN
+# APART: sheet b lifted along y, the direction the sheets' heights are measured in, by another amount every frame: enough to clear
+# sheet a where the two are placed in that frame, and little enough to leave them within BETWEEN_CCD_DIST of each other, so that the
+# proximity and CCD queries still find pairs (tests/test_moving_inputs.py pins the separation distances: 0.004 to 0.009)
+APART_LIFT = (0.025, 0.032, 0.036, 0.030, 0.022, 0.034)
+APART_INF_FRAMES = (1, 2)       # the frames whose per-triangle rows at rmax = +inf are restated over all a x b pairs, roles (a, b) only
 
 
 @functools.lru_cache(maxsize=None)
@@ -487,32 +604,99 @@ def between_meshes():
     return np.ascontiguousarray(v[:half]), np.ascontiguousarray(i[:na]), np.ascontiguousarray(v[half:]), np.ascontiguousarray((i[na:] - half).astype(np.uint32))
 
 
+def _lifted(v, dy):
+    w = v.copy()
+    w[:, 1] = np.float32(w[:, 1] + np.float32(dy))
+    return w
+
+
+def between_place(schedule, f):
+    """Where the sheets are in frame f: (a's quads along x, b's quads along z, b's lift along y).  a slides along x, b along z, one quad
+    a frame (0, 1, 2, 1, 0, 1: inside the reference's frame), whichever the schedule moves.  Every reference of a frame is a function
+    of this alone (the schedules and frames that share a place share its references)."""
+    at = 2 - abs(2 - f % 4)
+    return (at if schedule != "b_moves" else 0, at if schedule != "a_moves" else 0, APART_LIFT[f] if schedule == APART else 0.0)
+
+
+@functools.lru_cache(maxsize=None)
+def _placed(place):
+    va, ia, vb, ib = between_meshes()
+    qa, qb, lift = place
+    wb = _shifted(vb, 0, qb)
+    return _shifted(va, qa, 0), _lifted(wb, lift) if lift else wb
+
+
 @functools.lru_cache(maxsize=None)
 def between_positions(schedule):
-    """Per frame (va, vb, a moved, b moved): a slides along x, b along z, one quad a frame (0, 1, 2, 1, 0, 1: inside the reference's
-    frame), whichever the schedule moves."""
-    va, ia, vb, ib = between_meshes()
-    at = lambda k: 2 - abs(2 - k % 4)
+    """Per frame (va, vb, a moved, b moved)."""
     out = []
     for f in range(BETWEEN_FRAMES):
-        ma, mb = f > 0 and schedule != "b_moves", f > 0 and schedule != "a_moves"
-        out.append((_shifted(va, at(f) if schedule != "b_moves" else 0, 0), _shifted(vb, 0, at(f) if schedule != "a_moves" else 0), ma, mb))
+        wa, wb = _placed(between_place(schedule, f))
+        out.append((wa, wb, f > 0 and schedule != "b_moves", f > 0 and schedule != "a_moves"))
     return out
 
 
 @functools.lru_cache(maxsize=None)
-def between_x1(schedule, f):
-    wa, wb, _, _ = between_positions(schedule)[f]
+def _x1_placed(place):
+    wa, wb = _placed(place)
     return br.motion(wa, 0.15 * SLIDE_QUAD[0], 11), br.motion(wb, 0.15 * SLIDE_QUAD[0], 12)
+
+
+def between_x1(schedule, f):
+    return _x1_placed(between_place(schedule, f))
+
+
+def between_x1_moving(schedule, f):
+    """between_x1 with None for the mesh the schedule never moves (a static obstacle: cd_find_ccd_between's NULL end positions)."""
+    ea, eb = between_x1(schedule, f)
+    return None if schedule == "b_moves" else ea, None if schedule == "a_moves" else eb
+
+
+def _roles(place, swap):
+    """(va, ia, ea, vb, ib, eb) of the place in the roles (a, b), or (b, a) with swap."""
+    wa, wb = _placed(place)
+    _, ia, _, ib = between_meshes()
+    ea, eb = _x1_placed(place)
+    return (wb, ib, eb, wa, ia, ea) if swap else (wa, ia, ea, wb, ib, eb)
+
+
+@functools.lru_cache(maxsize=None)
+def _want_plain_between(place, swap):
+    wa, ia, ea, wb, ib, eb = _roles(place, swap)
+    return dict(contact=br.contact_pairs(wa, ia, wb, ib, brute=False), prox=br.proximity_pairs(wa, ia, wb, ib, BETWEEN_DIST, brute=False),
+                ccd=br.ccd_pairs(wa, ia, wb, ib, BETWEEN_CCD_DIST, ea, eb, brute=False))       # (the grid's candidates: 1.3 M pairs otherwise)
+
+
+@functools.lru_cache(maxsize=None)
+def _want_rows_between(place, swap):
+    wa, ia, ea, wb, ib, eb = _roles(place, swap)
+    near = nr.rows_of_all_pairs(wa, ia, wb, ib, rmax=NEAREST_R)
+    near_q = nr.within(near, NEAREST_R / 4)
+    return dict(prox_witness=wr.witness_pairs_between(wa, ia, wb, ib, BETWEEN_DIST), contour=ir.contour_pairs_between(wa, ia, wb, ib),
+                near=near, near_q=near_q, near_min=nr.nearest_min(near), near_q_min=nr.nearest_min(near_q))
+
+
+@functools.lru_cache(maxsize=None)
+def _want_ccd_witness_between(place, swap, a_ends, b_ends):
+    wa, ia, ea, wb, ib, eb = _roles(place, swap)
+    return wr.witness_pairs_between(wa, ia, wb, ib, BETWEEN_CCD_DIST, ccd=True, va1=ea if a_ends else None, vb1=eb if b_ends else None)
 
 
 @functools.lru_cache(maxsize=None)
 def want_between(schedule, f, swap=False):
-    """between_ref's contact, proximity and CCD pairs of frame f in the roles (a, b), or (b, a) with swap."""
-    wa, wb, _, _ = between_positions(schedule)[f]
-    _, ia, _, ib = between_meshes()
-    ea, eb = between_x1(schedule, f)
-    if swap:
-        wa, ia, ea, wb, ib, eb = wb, ib, eb, wa, ia, ea
-    return dict(contact=br.contact_pairs(wa, ia, wb, ib, brute=False), prox=br.proximity_pairs(wa, ia, wb, ib, BETWEEN_DIST, brute=False),
-                ccd=br.ccd_pairs(wa, ia, wb, ib, BETWEEN_CCD_DIST, ea, eb, brute=False))       # (the grid's candidates: 1.3 M pairs otherwise)
+    """The references of frame f in the roles (a, b), or (b, a) with swap.  contact, prox, ccd: between_ref's pairs (CCD with both
+    meshes moving to between_x1).  prox_witness, ccd_witness: witness_ref's Rows (CCD to between_x1_moving: None for a mesh the
+    schedule does not move).  contour: isect_ref's Rows.  near, near_q: nearest_ref's rows at NEAREST_R and a quarter of it, near_min,
+    near_q_min: their CD_NEAREST_MIN row; near_min is the row at rmax = +inf too wherever `near` finds anything."""
+    place = between_place(schedule, f)
+    ea, eb = between_x1_moving(schedule, f)
+    ends = (eb is not None, ea is not None) if swap else (ea is not None, eb is not None)
+    return dict(_want_plain_between(place, swap), **_want_rows_between(place, swap), ccd_witness=_want_ccd_witness_between(place, swap, *ends))
+
+
+@functools.lru_cache(maxsize=None)
+def want_between_inf(f):
+    """APART's per-triangle rows of frame f at rmax = +inf, roles (a, b): nearest_ref.nearest_rows, every a x b pair."""
+    assert f in APART_INF_FRAMES
+    wa, ia, _, wb, ib, _ = _roles(between_place(APART, f), False)
+    return nr.nearest_rows(wa, ia, wb, ib, np.inf)

@@ -1,15 +1,19 @@
 """The motion sequences of tests/moving_inputs.py can catch stale state, shown on the CPU: consecutive frames have different right
 answers, each sequence does what it is named for, and every comparison helper of tests/test_moving_mesh_gpu.py raises when it is fed
-frame f - 1's expected result against frame f's (the planted error: a device that kept the previous frame's state)."""
+frame f - 1's expected result against frame f's (the planted error: a device that kept the previous frame's state), and the
+comparisons of the witness, contour and nearest-triangle rows also when one field of one row of the right frame's result is changed."""
 from __future__ import annotations
 
 import numpy as np
 import pytest
 
 import moving_inputs as mi
+import nearest_ref as nr
 import oracle
+import proximity_ref as pr
 import scale_inputs as si
 import swept_ref as sr
+import witness_ref as wr
 
 
 def _bits(d):
@@ -135,7 +139,34 @@ def test_every_comparison_raises_on_the_previous_frames_result(name):
         mi.same_root_box(mi.want_root_box(name, f), mi.want_root_box(name, f), what)
         st = mi.want_step(name, f)
         mi.same_step(st["pairs"], st["stats"].n_pairs, 0, st["stats"].pairs_tested, st, what)
+        pw, cw, ct = mi.want_prox_witness(name, f), mi.want_ccd_witness(name, f), mi.want_contour(name, f)
+        plain_p, plain_c = (wp[0], wp[1], wp[0].shape[0], 0), (wc[0], wc[1], wc[2], wc[0].shape[0], 0)
+        mi.same_witness(mi.witness_call(pw), pw, what)
+        mi.same_witness(mi.witness_call(cw), cw, what)
+        mi.same_as_plain(mi.witness_call(pw)[:4], plain_p, what)            # (the restatements agree: the witness rows are the plain calls' pairs)
+        mi.same_as_plain(mi.witness_call(cw)[:5], plain_c, what)
+        mi.same_contour(mi.contour_call(ct), ct, what, ct.tested)
+        mi.same_pair_set(ct.pairs, st["pairs"], what)
         # ... and raises on the one before it
+        pw0, cw0, ct0 = mi.want_prox_witness(name, f - 1), mi.want_ccd_witness(name, f - 1), mi.want_contour(name, f - 1)
+        if pw0.faces.shape[0] or pw.faces.shape[0]:
+            with pytest.raises(AssertionError):
+                mi.same_witness(mi.witness_call(pw0), pw, what)
+            with pytest.raises(AssertionError):
+                mi.same_as_plain(mi.witness_call(pw0)[:4], plain_p, what)
+        if cw0.faces.shape[0] or cw.faces.shape[0]:
+            with pytest.raises(AssertionError):
+                mi.same_witness(mi.witness_call(cw0), cw, what)
+            with pytest.raises(AssertionError):
+                mi.same_as_plain(mi.witness_call(cw0)[:5], plain_c, what)
+        if ct0.faces.shape[0] or ct.faces.shape[0]:
+            with pytest.raises(AssertionError):
+                mi.same_contour(mi.contour_call(ct0), ct, what)
+            with pytest.raises(AssertionError):
+                mi.same_pair_set(ct0.pairs, st["pairs"], what)
+        if ct0.tested != ct.tested:
+            with pytest.raises(AssertionError):                                 # this frame's rows with the previous frame's n_tested
+                mi.same_contour(mi.contour_call(ct), ct, what, ct0.tested)
         with pytest.raises(AssertionError):
             mi.same_rays(mi.want_rays(name, f - 1), mi.want_rays(name, f), what)
         with pytest.raises(AssertionError):
@@ -175,10 +206,184 @@ def test_between_comparisons_raise_on_the_previous_frames_result():
             mi.same_between_prox((p[0], p[1], p[0].shape[0], 0), p, what)
             mi.same_between_ccd((q[0], q[1], q[2], q[0].shape[0], 0), q, what)
             c0, p0, q0 = w0["contact"][0], w0["prox"], w0["ccd"]
-            assert c.shape[0] > 0 and p[0].shape[0] > 0 and q[0].shape[0] > 0
-            with pytest.raises(AssertionError):
-                mi.same_between_contact((c0, c0.shape[0], 0), c, what)
+            assert (c.shape[0] > 0 or schedule == mi.APART) and p[0].shape[0] > 0 and q[0].shape[0] > 0
+            if schedule != mi.APART:                                            # (sheets that do not touch: no pairs in contact in either frame)
+                with pytest.raises(AssertionError):
+                    mi.same_between_contact((c0, c0.shape[0], 0), c, what)
             with pytest.raises(AssertionError):
                 mi.same_between_prox((p0[0], p0[1], p0[0].shape[0], 0), p, what)
             with pytest.raises(AssertionError):
                 mi.same_between_ccd((q0[0], q0[1], q0[2], q0[0].shape[0], 0), q, what)
+            for k in ("prox_witness", "ccd_witness"):
+                assert w1[k].faces.shape[0] > 0, (what, k)
+                mi.same_witness(mi.witness_call(w1[k]), w1[k], what)
+                with pytest.raises(AssertionError):
+                    mi.same_witness(mi.witness_call(w0[k]), w1[k], what)
+            mi.same_as_plain(mi.witness_call(w1["prox_witness"])[:4], (p[0], p[1], p[0].shape[0], 0), what)
+            mi.same_contour(mi.contour_call(w1["contour"]), w1["contour"], what, w1["contour"].tested)
+            mi.same_between_contact(mi.contour_call(w1["contour"])[:3], c, what)
+            if schedule != mi.APART:
+                with pytest.raises(AssertionError):
+                    mi.same_contour(mi.contour_call(w0["contour"]), w1["contour"], what)
+                assert w0["contour"].tested != w1["contour"].tested
+                with pytest.raises(AssertionError):                             # this frame's rows with the previous frame's n_tested
+                    mi.same_contour(mi.contour_call(w1["contour"]), w1["contour"], what, w0["contour"].tested)
+            for k in ("near", "near_q", "near_min", "near_q_min"):
+                mi.same_nearest(mi.nearest_call(w1[k]), w1[k], what)
+                with pytest.raises(AssertionError):
+                    mi.same_nearest(mi.nearest_call(w0[k]), w1[k], what)
+
+
+# ---------------------------------------------------------------- one field of the right frame's rows
+def _copy(rows):
+    return type(rows)(*(x.copy() if isinstance(x, np.ndarray) else x for x in rows))
+
+
+def _flip_lowest_bit(a, at):
+    a.view(np.uint64)[at] ^= np.uint64(1)
+
+
+def _corrupted_witness(rows, k):
+    """name -> a copy of witness_ref's Rows with ONE field of row k changed."""
+    out = {}
+    for name, at in (("bary", (k, 1, 0)), ("points", (k, 0, 2)), ("dists", (k,))) + ((("toi", (k,)),) if rows.toi is not None else ()):
+        out[name + " bit"] = r = _copy(rows)
+        _flip_lowest_bit(getattr(r, name), at)
+    out["feature code"] = r = _copy(rows)
+    r.feature[k, 0] = (int(r.feature[k, 0]) + 1) % 7
+    out["faces swapped within the pair"] = r = _copy(rows)
+    r.faces[k] = r.faces[k, ::-1]
+    out["pair"] = r = _copy(rows)
+    r.pairs[k, 1] ^= 1
+    return out
+
+
+def _corrupted_contour(rows, k):
+    out = {}
+    for name, at in (("param", (k, 1)), ("points", (k, 5))):
+        out[name + " bit"] = r = _copy(rows)
+        _flip_lowest_bit(getattr(r, name), at)
+    out["endpoint code"] = r = _copy(rows)
+    r.code[k, 0] ^= 8                                                           # the side bit of endpoint 0
+    out["mask"] = r = _copy(rows)
+    r.code[k, 2] ^= 1
+    out["faces swapped within the pair"] = r = _copy(rows)
+    r.faces[k] = r.faces[k, ::-1]
+    out["pair"] = r = _copy(rows)
+    r.pairs[k, 1] ^= 1
+    return out
+
+
+def _second_nearest(rows, k, place):
+    """rows with row k replaced by a's face k against the SECOND nearest triangle of b, with that pair's own distance and witness."""
+    wa, ia, _, wb, ib, _ = mi._roles(place, False)
+    nb = ib.shape[0]
+    tri = np.concatenate([np.repeat(wa[ia[k].astype(np.int64)][None], nb, axis=0), wb[ib.astype(np.int64)]], axis=1)
+    d = pr.tri_distance_np(tri)
+    o = np.lexsort((np.arange(nb), d))
+    assert o[0] == rows.faces[k, 1] and d[o[0]] == rows.dist[k]
+    j = int(o[1])
+    w = wr.tri_witness_np(tri[j:j + 1])
+    r = _copy(rows)
+    r.faces[k], r.ids[k], r.dist[k], r.points[k], r.bary[k], r.feature[k] = (k, j), (k, j), d[j], w.points[0], w.bary[0], w.feature[0]
+    return r
+
+
+def _corrupted_nearest(rows, k, place=None):
+    out = {}
+    for name, at in (("bary", (k, 0, 1)), ("points", (k, 1, 0)), ("dist", (k,))):
+        out[name + " bit"] = r = _copy(rows)
+        _flip_lowest_bit(getattr(r, name), at)
+    out["feature code"] = r = _copy(rows)
+    r.feature[k, 1] = (int(r.feature[k, 1]) + 1) % 7
+    out["faces swapped within the pair"] = r = _copy(rows)
+    r.faces[k] = r.faces[k, ::-1]
+    out["id"] = r = _copy(rows)
+    r.ids[k, 1] ^= 1
+    if place is not None:
+        out["the second nearest triangle"] = _second_nearest(rows, k, place)
+    return out
+
+
+def test_every_new_comparison_raises_on_one_corrupted_field():
+    """The right frame's rows with one field of one row changed: one bit of a barycentric, a point, a distance, a toi or a parameter,
+    one feature or endpoint code, the two faces of one pair exchanged, one ID, one nearest row replaced by the second nearest triangle's."""
+    name, f, schedule = "jitter", 1, "both_move"
+    place = mi.between_place(schedule, f)
+    w = mi.want_between(schedule, f)
+    for what, rows in (("proximity", mi.want_prox_witness(name, f)), ("ccd", mi.want_ccd_witness(name, f)), ("between proximity", w["prox_witness"]),
+                       ("between ccd", w["ccd_witness"])):
+        ok = np.flatnonzero((rows.feature != wr.FEATURE_NONE).all(axis=1) & (rows.faces[:, 0] != rows.faces[:, 1]))     # (rows with a witness to corrupt)
+        k = int(ok[ok.size // 2])
+        for field, bad in _corrupted_witness(rows, k).items():
+            with pytest.raises(AssertionError):
+                mi.same_witness(mi.witness_call(bad), rows, (what, field))
+        with pytest.raises(AssertionError):                                     # the return code
+            mi.same_witness(mi.witness_call(rows, rc=1), rows, what)
+    for what, rows in (("contour", mi.want_contour(name, f)), ("between contour", w["contour"])):
+        k = rows.faces.shape[0] // 2
+        for field, bad in _corrupted_contour(rows, k).items():
+            with pytest.raises(AssertionError):
+                mi.same_contour(mi.contour_call(bad), rows, (what, field))
+        with pytest.raises(AssertionError):
+            mi.same_contour(mi.contour_call(rows, rc=1), rows, what)
+    rows = w["near"]
+    k = int(np.flatnonzero((rows.faces[:, 0] != nr.NONE) & (rows.feature[:, 1] != wr.FEATURE_NONE))[rows.faces.shape[0] // 3])
+    for field, bad in _corrupted_nearest(rows, k, place).items():
+        with pytest.raises(AssertionError):
+            mi.same_nearest(mi.nearest_call(bad), rows, ("nearest", field))
+    least = mi.want_between(mi.APART, f)["near_min"]                            # (sheets that do not touch: a row with a witness)
+    assert (least.feature != wr.FEATURE_NONE).all()
+    for field, bad in _corrupted_nearest(least, 0).items():
+        with pytest.raises(AssertionError):
+            mi.same_nearest(mi.nearest_call(bad), least, ("nearest MIN", field))
+    with pytest.raises(AssertionError):                                         # n_found alone
+        mi.same_nearest(mi.nearest_call(rows)._replace(info=mi.mi355cd.CdNearestInfo(0, 0, 0)), rows, "nearest")
+
+
+# ---------------------------------------------------------------- the new references are not empty, and the sheets that do not touch
+def test_witness_and_contour_references_have_rows_in_every_frame_of_the_large_sequences():
+    for name in mi.LARGE:
+        n = [(mi.want_prox_witness(name, f).faces.shape[0], mi.want_ccd_witness(name, f).faces.shape[0], mi.want_contour(name, f).faces.shape[0])
+             for f in range(len(mi.seq(name)))]
+        print(f"{name}: (proximity witness, ccd witness, contour) rows a frame: {n}")
+        assert min(min(x) for x in n) > 0, (name, n)
+    d = mi.JITTER_DENSE_FRAME
+    for k, want in enumerate((mi.want_prox_witness, mi.want_ccd_witness, mi.want_contour)):
+        assert want("jitter", d).faces.shape[0] > 4 * want("jitter", d - 1).faces.shape[0], k      # the buffers of twice the rows grow there
+
+
+def test_between_schedules_cross_in_every_frame_but_the_apart_one_which_never_touches():
+    seps = []
+    for schedule in mi.BETWEEN_SCHEDULES:
+        for f in range(mi.BETWEEN_FRAMES):
+            w = mi.want_between(schedule, f)
+            rows, near = w["contour"].faces.shape[0], w["near"]
+            found = near.faces[:, 0] != nr.NONE
+            assert found.any(), (schedule, f)                                   # the precondition of near_min standing for rmax = +inf
+            sep = float(w["near_min"].dist[0])
+            if schedule == mi.APART:
+                assert rows == 0 and w["contact"][0].shape[0] == 0 and sep > 0.0 and not (near.dist == 0.0).any(), (f, rows, sep)
+                assert sep < mi.BETWEEN_CCD_DIST and w["prox_witness"].faces.shape[0] > 0 and w["ccd_witness"].faces.shape[0] > 0, (f, sep)
+                seps.append(sep)
+            else:
+                assert rows > 0 and sep == 0.0, (schedule, f, rows, sep)
+    print("both_move_apart: the separation distance, frame by frame:", [x.hex() for x in seps])
+    assert all(_bits(x) != _bits(y) for x, y in zip(seps, seps[1:])) and len(set(seps)) == len(seps), seps
+    assert 0.004 < min(seps) and max(seps) < 0.009, seps
+    lift = mi.APART_LIFT
+    assert len(lift) == mi.BETWEEN_FRAMES and all(x != y for x, y in zip(lift, lift[1:]))
+    assert 1 <= len(mi.APART_INF_FRAMES) <= 3
+
+
+def test_the_two_routes_to_the_nearest_rows_agree_on_a_frame_of_the_apart_schedule():
+    """nearest_ref.nearest_rows at +inf (every a x b pair) cut to NEAREST_R is rows_of_all_pairs at NEAREST_R (the grid's candidates), and
+    its minimum is near_min: what the GPU test takes for CD_NEAREST_MIN at +inf."""
+    f = mi.APART_INF_FRAMES[0]
+    w, rows = mi.want_between(mi.APART, f), mi.want_between_inf(f)
+    assert (rows.faces[:, 0] == np.arange(rows.faces.shape[0])).all()
+    mi.same_nearest(mi.nearest_call(nr.within(rows, mi.NEAREST_R)), w["near"], "apart")
+    mi.same_nearest(mi.nearest_call(nr.nearest_min(rows)), w["near_min"], "apart")
+    f0 = mi.APART_INF_FRAMES[1]
+    with pytest.raises(AssertionError):                                         # the rows at +inf of one frame against another's
+        mi.same_nearest(mi.nearest_call(nr.within(rows, mi.NEAREST_R)), mi.want_between(mi.APART, f0)["near"], "apart")

@@ -4,10 +4,18 @@ frame to frame.  Each result is compared bit for bit with the CPU restatement of
 created on that frame's vertices and built with cd_build_tree (a differential check: it also covers what the restatements do not
 restate).  tests/test_moving_inputs.py shows, without a GPU, that the previous frame's result fails every comparison used here.
 
-Counters that are NOT compared with the fresh context's: node_visits and tri_tests of cd_cast_rays / cd_closest_points, and the
-collision step's node_visits and wave_steps -- they count the walk, which may legitimately differ with the options the entry left
-behind (traversal bookkeeping, the order hint).  pairs_tested of a collision step is compared with the oracle's, proximity's and CCD's
-evaluation counts with the restatement's and the fresh context's, n_candidates with swept_ref's count and the fresh context's."""
+The witness, contour and nearest-triangle calls go through the same frames: cd_find_proximity_witness, cd_find_ccd_witness and
+cd_find_collisions_contour in the permuted list of every sequence and entry, their between-mesh forms and cd_nearest_between (per
+triangle and CD_NEAREST_MIN, at two radii and at +inf) in both roles of every schedule of the two sheets.  Their rows are ordered by
+(face a, face b) and every column is compared by its bytes; their buffers get twice the frame's row count, so they grow on a dense
+frame and are reused, oversized, on the sparse frames after it.
+
+Counters that are NOT compared with the fresh context's: node_visits and tri_tests of cd_cast_rays / cd_closest_points /
+cd_nearest_between (the last also not with a restatement: nearest_ref has no walk), and the collision step's node_visits and
+wave_steps -- they count the walk, which may legitimately differ with the options the entry left behind (traversal bookkeeping, the
+order hint; cd_nearest_between's shared bound makes them differ from run to run: test_nearest_gpu.py).  pairs_tested of a collision step is
+compared with the oracle's, proximity's and CCD's evaluation counts with the restatement's and the fresh context's, n_candidates with
+swept_ref's count and the fresh context's, the contour calls' n_tested with isect_ref's, cd_nearest_between's n_found with nearest_ref's."""
 from __future__ import annotations
 
 import ctypes as C
@@ -146,7 +154,47 @@ def _queries(cd, fresh, name, f):
         mi.same_root_box(got, mi.want_root_box(name, f), what + " root box")
         mi.same_root_box(got, fresh.root_box(), what + " root box against the fresh context")
 
-    return [("proximity", proximity), ("ccd", ccd), ("rays", ray_queries), ("points", point_queries), ("root box", box)]
+    twice = lambda rows: max(1, 2 * rows.faces.shape[0])                       # the witness / contour buffers: grown on the dense frame, oversized after it
+
+    def proximity_witness():
+        d, want = mi.prox_dist(name, f), mi.want_prox_witness(name, f)
+        got = cd.find_proximity_witness(d, cap=twice(want))
+        tested = cd.proximity_tested
+        mi.same_witness(got, want, what + " proximity witness")
+        mi.same_prox(got[:4], mi.want_prox(name, f), what + " proximity witness: the plain call's pairs and distances")
+        gf = fresh.find_proximity_witness(d, cap=twice(want))
+        assert gf[3] == mi355cd.CD_OK, what
+        mi.same_witness(got, mi.witness_rows(gf), what + " proximity witness against the fresh context")
+        assert tested == fresh.proximity_tested, (what, tested, fresh.proximity_tested)
+        mi.same_as_plain(got[:4], cd.find_proximity(d, cap=CAP), what + " proximity witness against the plain call")
+
+    def ccd_witness():
+        d, e, want = mi.ccd_dist(name, f), mi.x1(name, f), mi.want_ccd_witness(name, f)
+        plain, counts = mi.want_ccd(name, f)
+        got = cd.find_ccd_witness(e, d, cap=twice(want))
+        info = cd.ccd_info
+        mi.same_witness(got, want, what + " ccd witness")
+        mi.same_ccd(got[:5], plain, what + " ccd witness: the plain call's pairs, toi and distances", info, counts)
+        sr.compare_count(info.n_candidates, mi.want_candidates(name, f), what + " ccd witness")
+        gf = fresh.find_ccd_witness(e, d, cap=twice(want))
+        assert gf[4] == mi355cd.CD_OK, what
+        mi.same_witness(got, mi.witness_rows(gf), what + " ccd witness against the fresh context")
+        fi = fresh.ccd_info
+        assert bytes(info) == bytes(fi), (what, [(k, getattr(info, k), getattr(fi, k)) for k, _ in mi355cd.CdCcdInfo._fields_])
+        mi.same_as_plain(got[:5], cd.find_ccd(e, d, cap=CAP), what + " ccd witness against the plain call")
+
+    def contour():
+        want = mi.want_contour(name, f)
+        got = cd.find_collisions_contour(cap=twice(want))
+        tested = cd.contour_tested
+        mi.same_contour(got, want, what + " contour", tested)
+        mi.same_pair_set(got[0], mi.want_step(name, f)["pairs"], what + " contour: the collision step's pair set")
+        gf = fresh.find_collisions_contour(cap=twice(want))
+        assert gf[2] == mi355cd.CD_OK, what
+        mi.same_contour(got, mi.contour_rows(gf, fresh.contour_tested), what + " contour against the fresh context", tested)
+
+    return [("proximity", proximity), ("ccd", ccd), ("rays", ray_queries), ("points", point_queries), ("root box", box),
+            ("proximity witness", proximity_witness), ("ccd witness", ccd_witness), ("contour", contour)]
 
 
 def _new(verts, vidx, mode):
@@ -197,28 +245,77 @@ def test_every_sequence_through_rotating_entries(name):
 
 
 # ---------------------------------------------------------------- between two meshes
+SENTINEL = 0xDEADBEEF
+
+
 def _order_errors(a, b):
     """A mesh moved and its tree was not rebuilt: every query between the two, in both roles, returns CD_ERR_ORDER and writes nothing."""
     lib = a.lib
     vp = lambda x: x.ctypes.data_as(C.c_void_p)
-    pairs, toi, d = np.full((16, 2), 0xDEADBEEF, dtype=np.uint32), np.full(16, -7.0), np.full(16, -7.0)
+    p = lambda x: x.ctypes.data
+    pairs, toi, d = np.full((16, 2), SENTINEL, dtype=np.uint32), np.full(16, -7.0), np.full(16, -7.0)
     n, t, info = C.c_uint64(0), C.c_uint64(0), mi355cd.CdCcdInfo()
+    rows = max(a.nt, b.nt)                                                      # cd_nearest_between writes a row per triangle of its first mesh
+    u32 = {k: np.full((r, 2), SENTINEL, dtype=np.uint32) for k, r in (("witness faces", 16), ("contour faces", 16), ("faces", rows), ("ids", rows), ("nearest faces", rows))}
+    f64 = {k: np.full(shape, -7.0) for k, shape in (("points", (16, 2, 3)), ("bary", (16, 2, 2)), ("param", (16, 2, 3)), ("contour points", (16, 2, 3)),
+                                                    ("dist", (rows,)), ("nearest points", (rows, 2, 3)), ("nearest bary", (rows, 2, 2)))}
+    u8 = {k: np.full(shape, 0xEE, dtype=np.uint8) for k, shape in (("feature", (16, 2)), ("code", (16, 3)), ("nearest feature", (rows, 2)))}
+    wit = mi355cd.CdWitnessOut(p(u32["witness faces"]), p(f64["points"]), p(f64["bary"]), p(u8["feature"]))
+    con = mi355cd.CdContourOut(p(u32["contour faces"]), p(u8["code"]), p(f64["param"]), p(f64["contour points"]))
+    nwit = mi355cd.CdWitnessOut(p(u32["nearest faces"]), p(f64["nearest points"]), p(f64["nearest bary"]), p(u8["nearest feature"]))
+    ninfo = mi355cd.CdNearestInfo(5, 5, 5)
+    E = mi355cd.CD_ERR_ORDER
     for x, y in ((a, b), (b, a)):
-        assert lib.cd_find_collisions_between(x._ctx, y._ctx, vp(pairs), 16, C.byref(n), C.byref(t)) == mi355cd.CD_ERR_ORDER
-        assert lib.cd_find_proximity_between(x._ctx, y._ctx, mi.BETWEEN_DIST, vp(pairs), vp(d), 16, C.byref(n), C.byref(t)) == mi355cd.CD_ERR_ORDER
-        assert lib.cd_find_ccd_between(x._ctx, None, y._ctx, None, mi.BETWEEN_CCD_DIST, vp(pairs), vp(toi), vp(d), 16, C.byref(n), C.byref(info)) == mi355cd.CD_ERR_ORDER
-    assert (pairs == 0xDEADBEEF).all() and (toi == -7.0).all() and (d == -7.0).all()
+        assert lib.cd_find_collisions_between(x._ctx, y._ctx, vp(pairs), 16, C.byref(n), C.byref(t)) == E
+        assert lib.cd_find_proximity_between(x._ctx, y._ctx, mi.BETWEEN_DIST, vp(pairs), vp(d), 16, C.byref(n), C.byref(t)) == E
+        assert lib.cd_find_ccd_between(x._ctx, None, y._ctx, None, mi.BETWEEN_CCD_DIST, vp(pairs), vp(toi), vp(d), 16, C.byref(n), C.byref(info)) == E
+        assert lib.cd_find_proximity_between_witness(x._ctx, y._ctx, mi.BETWEEN_DIST, vp(pairs), vp(d), 16, C.byref(n), C.byref(t), C.byref(wit)) == E
+        assert lib.cd_find_ccd_between_witness(x._ctx, None, y._ctx, None, mi.BETWEEN_CCD_DIST, vp(pairs), vp(toi), vp(d), 16, C.byref(n), C.byref(info),
+                                               C.byref(wit)) == E
+        assert lib.cd_find_collisions_between_contour(x._ctx, y._ctx, vp(pairs), 16, C.byref(n), C.byref(t), C.byref(con)) == E
+        for flags, r in ((0, mi.NEAREST_R), (0, float("inf")), (mi355cd.CD_NEAREST_MIN, mi.NEAREST_R), (mi355cd.CD_NEAREST_MIN, float("inf"))):
+            assert lib.cd_nearest_between(x._ctx, y._ctx, r, flags, vp(u32["faces"]), vp(u32["ids"]), vp(f64["dist"]), C.byref(nwit), C.byref(ninfo)) == E
+    assert (pairs == SENTINEL).all() and (toi == -7.0).all() and (d == -7.0).all()
+    assert all((x == SENTINEL).all() for x in u32.values()) and all((x == -7.0).all() for x in f64.values()) and all((x == 0xEE).all() for x in u8.values())
+    assert (ninfo.n_found, ninfo.node_visits, ninfo.tri_tests) == (5, 5, 5)
+
+
+def _new_between_queries(x, y, schedule, f, swap, w, ends, what):
+    """The witness, contour and nearest-triangle calls of x against y on frame f, each against the frame's reference w (mi.want_between)."""
+    twice = lambda rows: max(1, 2 * rows.faces.shape[0])
+    ex, ey = ends
+    g = x.find_proximity_between_witness(y, mi.BETWEEN_DIST, cap=twice(w["prox_witness"]))
+    mi.same_witness(g, w["prox_witness"], what + " proximity witness")
+    mi.same_between_prox(g[:4], w["prox"], what + " proximity witness: the plain call's pairs and distances")
+    # the end positions of this schedule: None for the mesh that never moves -- the call before or after it (the plain CCD query of this
+    # frame, the witness call of the frame before) left a swept tree of y under other end positions in x
+    g = x.find_ccd_between_witness(y, mi.BETWEEN_CCD_DIST, ex, ey, cap=twice(w["ccd_witness"]))
+    mi.same_witness(g, w["ccd_witness"], what + " ccd witness")
+    mi.same_as_plain(g[:5], x.find_ccd_between(y, mi.BETWEEN_CCD_DIST, ex, ey, cap=CAP), what + " ccd witness against the plain call")
+    g = x.find_collisions_between_contour(y, cap=twice(w["contour"]))
+    mi.same_contour(g, w["contour"], what + " contour", x.between_tested)
+    mi.same_between_contact(g[:3], w["contact"][0], what + " contour: the plain call's pair set")
+    assert (schedule == mi.APART) == (w["contour"].faces.shape[0] == 0), what
+    for rmax, rows, least in ((mi.NEAREST_R, w["near"], w["near_min"]), (mi.NEAREST_R / 4, w["near_q"], w["near_q_min"])):
+        mi.same_nearest(x.nearest_between(y, rmax, witness=True), rows, f"{what} nearest within {rmax:g}")
+        mi.same_nearest(x.nearest_between(y, rmax, minimum=True, witness=True), least, f"{what} nearest within {rmax:g}, MIN")
+    assert (w["near"].faces[:, 0] != mi355cd.NEAREST_NONE).any(), what        # ... so the closest pair of all is within NEAREST_R
+    mi.same_nearest(x.nearest_between(y, float("inf"), minimum=True, witness=True), w["near_min"], what + " nearest, MIN at +inf")
+    if schedule == mi.APART and not swap and f in mi.APART_INF_FRAMES:
+        mi.same_nearest(x.nearest_between(y, float("inf"), witness=True), mi.want_between_inf(f), what + " nearest at +inf")
 
 
 @pytest.mark.parametrize("schedule", mi.BETWEEN_SCHEDULES)
 def test_between_two_meshes_that_move(schedule):
-    """Context a is one sheet of `slide`, b the other; only a moves, only b moves, or both.  A context that did not move is neither
-    updated nor rebuilt: what a keeps of b from the last CCD call (and b of a) is the previous frame's and must not be used."""
+    """Context a is one sheet of `slide`, b the other; only a moves, only b moves, or both (and with both_move_apart b is also lifted
+    off a by another amount every frame: the sheets do not touch and their separation distance changes).  A context that did not move
+    is neither updated nor rebuilt: what a keeps of b from the last CCD call (and b of a) is the previous frame's and must not be used."""
     va, ia, vb, ib = mi.between_meshes()
     pos = mi.between_positions(schedule)
     with mi355cd.CollisionDetector(pos[0][0], ia) as a, mi355cd.CollisionDetector(pos[0][1], ib) as b:
         for f, (wa, wb, ma, mb) in enumerate(pos):
             ea, eb = mi.between_x1(schedule, f)
+            ema, emb = mi.between_x1_moving(schedule, f)
             if ma:
                 a.update_vertices(wa)
             if mb:
@@ -232,6 +329,9 @@ def test_between_two_meshes_that_move(schedule):
                 what = f"{schedule} frame {f}, roles {'(b, a)' if swap else '(a, b)'}"
                 w = mi.want_between(schedule, f, swap)
                 (vx, ex, ix), (vy, ey, iy) = ((wb, eb, ib), (wa, ea, ia)) if swap else ((wa, ea, ia), (wb, eb, ib))
+                ends = (emb, ema) if swap else (ema, emb)
+                if f % 2:                                                       # before the plain calls in the odd frames, after them in the even ones
+                    _new_between_queries(x, y, schedule, f, swap, w, ends, what)
                 mi.same_between_contact(x.find_collisions_between(y, cap=CAP), w["contact"][0], what + " contact")
                 assert x.between_tested == w["contact"][1], (what, x.between_tested, w["contact"][1])
                 mi.same_between_prox(x.find_proximity_between(y, mi.BETWEEN_DIST, cap=CAP), w["prox"], what + " proximity")
@@ -239,3 +339,5 @@ def test_between_two_meshes_that_move(schedule):
                 t = mi.read_swept(x, y)                                        # what x holds of y after the CCD call
                 mi.same_swept(t, vy, ey, iy, sr.m_bits_between(vx, ex, ix, vy, ey, iy), mi.BETWEEN_CCD_DIST, what + " swept tree",
                               a=(vx, ex, ix, x.export_keys()[1]), n_candidates=x.ccd_info.n_candidates)
+                if not f % 2:
+                    _new_between_queries(x, y, schedule, f, swap, w, ends, what)
