@@ -2066,6 +2066,16 @@ int cd_find_collisions_queries(cd_ctx *c, const void *d_queries, uint64_t nq, ui
 // ---- the witness of the pair queries (cd_witness.h) ---------------------------------------------------------------------------------
 // NULL, or every member NULL: the plain call
 static bool witness_wanted(const cd_witness_out *w) { return w && (w->faces || w->points || w->bary || w->feature); }
+// The tail of a call that wants a witness or a contour.  rc: what the pass's results() returned; CD_OK or CD_OVERFLOW: the rows are
+// there, so the per-row kernel runs (rows: witness_results / contour_results), and its error wins over rc.
+extern "C++" {                                  // (a template: the per-row call is a parameter)
+template <class Rows> static int rows_tail(bool wanted, int rc, Rows rows)
+{
+    if (!wanted || (rc != CD_OK && rc != CD_OVERFLOW)) return rc;
+    const int rw = rows();
+    return rw ? rw : rc;
+}
+}  // extern "C++"
 // Behind a pass that is finished and read back (np = its pair count): the witness kernel over the rows the caller gets, on stream s, and
 // the copies into w's arrays.  a, b: the contexts A's and B's triangles come from (the self calls: the same one); ax1 / bx1 / d_toi: the
 // end positions and the rows' times on the device (CCD), NULL for proximity.
@@ -2077,11 +2087,11 @@ static int witness_results(hipStream_t s, const WitnessBuf &wb, uint64_t np, uin
     uint32_t *faces = w->faces ? wb.d_faces : nullptr;
     double *points = w->points ? wb.d_points : nullptr, *bary = w->bary ? wb.d_bary : nullptr;
     uint8_t *feat = w->feature ? wb.d_feat : nullptr;
-    const uint32_t grid = cdiv(take, WITNESS_THREADS);
-    if (d_toi) k_pair_witness<true><<<grid, WITNESS_THREADS, 0, s>>>(wb.d_leaf, take, a->d_leaf, a->d_perm[0], a->d_verts, ax1, b->d_leaf, b->d_perm[0], b->d_verts, bx1,
-                                                                    d_toi, faces, points, bary, feat);
-    else k_pair_witness<false><<<grid, WITNESS_THREADS, 0, s>>>(wb.d_leaf, take, a->d_leaf, a->d_perm[0], a->d_verts, nullptr, b->d_leaf, b->d_perm[0], b->d_verts, nullptr,
-                                                               nullptr, faces, points, bary, feat);
+    auto rows = [&](auto toi) {
+        k_pair_witness<decltype(toi)::value><<<cdiv(take, WITNESS_THREADS), WITNESS_THREADS, 0, s>>>(wb.d_leaf, take, a->d_leaf, a->d_perm[0], a->d_verts, ax1, b->d_leaf,
+                                                                                                     b->d_perm[0], b->d_verts, bx1, d_toi, faces, points, bary, feat);
+    };
+    if (d_toi) rows(std::true_type{}); else rows(std::false_type{});
     HIPCHK(hipGetLastError());
     if (faces) HIPCHK(hipMemcpyAsync(w->faces, faces, sizeof(uint32_t) * 2 * take, hipMemcpyDeviceToHost, s));
     if (points) HIPCHK(hipMemcpyAsync(w->points, points, sizeof(double) * 6 * take, hipMemcpyDeviceToHost, s));
@@ -2103,10 +2113,11 @@ static int prox_enqueue(cd_ctx *c, double dist, uint64_t cap_pairs, uint2 *wleaf
     HIPCHK(hipMemsetAsync(q.state.d, 0, sizeof(ProxState), s));
     k_prox_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(c->d_recs32, c->d_leaf, c->d_verts, c->d_boxes, (int)n, dist,
                                                                              c->d_os_ticket + 8, q.state.d, q.d_cand, q.shard_cap);
-    if (wleaf) k_prox_exact<true><<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, dist,
-                                                                                               q.state.d, q.d_pairs, q.d_dists, cap_pairs, wleaf);
-    else k_prox_exact<false><<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, dist,
-                                                                                          q.state.d, q.d_pairs, q.d_dists, cap_pairs, nullptr);
+    auto exact = [&](auto wit) {
+        k_prox_exact<decltype(wit)::value><<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, dist,
+                                                                                                        q.state.d, q.d_pairs, q.d_dists, cap_pairs, wleaf);
+    };
+    if (wleaf) exact(std::true_type{}); else exact(std::false_type{});
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(q.state.h, q.state.d, sizeof(ProxState), hipMemcpyDeviceToHost, s));
     return CD_OK;
@@ -2131,27 +2142,22 @@ static int prox_args(cd_ctx *c, double dist, uint32_t *pairs, uint64_t cap_pairs
     if (!c || !prox_dist_ok(dist) || (cap_pairs && !pairs)) return CD_ERR_ARG;
     return CD_OK;
 }
-int cd_find_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
+static int find_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested, const cd_witness_out *w)
 {
     int rc = prox_args(c, dist, pairs, cap_pairs);
     if (rc) return rc;
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
-    if ((rc = c->prox.ensure(c->nt, cap_pairs))) return rc;
-    return prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
+    const bool wanted = witness_wanted(w);
+    PairBuf<ProxState> &q = c->prox;
+    if ((rc = q.ensure(c->nt, cap_pairs)) || (wanted && (rc = q.wit.ensure(cap_pairs)))) return rc;
+    rc = prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested, wanted ? q.wit.d_leaf : nullptr);
+    return rows_tail(wanted, rc, [&] { return witness_results(c->stream, q.wit, q.state.h->n_pairs, cap_pairs, c, nullptr, c, nullptr, nullptr, w); });
 }
+int cd_find_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
+{ return find_proximity(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested, nullptr); }
 int cd_find_proximity_witness(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested,
                               const cd_witness_out *w)
-{
-    if (!witness_wanted(w)) return cd_find_proximity(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
-    int rc = prox_args(c, dist, pairs, cap_pairs);
-    if (rc) return rc;
-    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
-    if ((rc = c->prox.ensure(c->nt, cap_pairs)) || (rc = c->prox.wit.ensure(cap_pairs))) return rc;
-    rc = prox_pass(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested, c->prox.wit.d_leaf);
-    if (rc != CD_OK && rc != CD_OVERFLOW) return rc;
-    const int rw = witness_results(c->stream, c->prox.wit, c->prox.state.h->n_pairs, cap_pairs, c, nullptr, c, nullptr, nullptr, w);
-    return rw ? rw : rc;
-}
+{ return find_proximity(c, dist, pairs, dists, cap_pairs, n_pairs, n_tested, w); }
 int cd_self_proximity(cd_ctx *c, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
 {
     int rc = prox_args(c, dist, pairs, cap_pairs);
@@ -2238,10 +2244,11 @@ static int ccd_enqueue(cd_ctx *c, const double *verts_end /* NULL: a redo, x1 is
         if (rc) return rc;
         k_ccd_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(c->swept[0].d_recs, c->d_leaf, c->d_verts, x1, (int)n, dist,
                                                                                c->d_os_ticket + 8, q.state.d, q.d_cand, q.shard_cap);
-        if (wleaf) k_ccd_exact<true><<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, x1, dist,
-                                                                                                  q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, wleaf);
-        else k_ccd_exact<false><<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, x1, dist,
-                                                                                             q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, nullptr);
+        auto exact = [&](auto wit) {
+            k_ccd_exact<decltype(wit)::value><<<dim3(shard_blocks(n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, x1, dist,
+                                                                                                           q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, wleaf);
+        };
+        if (wleaf) exact(std::true_type{}); else exact(std::false_type{});
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(q.state.h, q.state.d, sizeof(CcdState), hipMemcpyDeviceToHost, s));
@@ -2266,32 +2273,27 @@ static int ccd_args(cd_ctx *c, const double *verts_end, double dist, uint32_t *p
     if (!c || !verts_end || !ccd_dist_ok(dist) || (cap_pairs && !pairs)) return CD_ERR_ARG;
     return CD_OK;
 }
+static int find_ccd(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
+                    cd_ccd_info *info, const cd_witness_out *w)
+{
+    int rc = ccd_args(c, verts_end, dist, pairs, cap_pairs);
+    if (rc) return rc;
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    const bool wanted = witness_wanted(w);
+    PairBuf<CcdState> &q = c->ccd;
+    if ((rc = ccd_buffers(c, cap_pairs)) || (wanted && (rc = q.wit.ensure(cap_pairs)))) return rc;
+    uint2 *wleaf = wanted ? q.wit.d_leaf : nullptr;
+    if ((rc = ccd_enqueue(c, verts_end, dist, cap_pairs, wleaf))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    rc = ccd_finish(c, dist, pairs, toi, dists, cap_pairs, n_pairs, info, wleaf);
+    return rows_tail(wanted, rc, [&] { return witness_results(c->stream, q.wit, q.state.h->n_pairs, cap_pairs, c, c->ccd_x1.d, c, c->ccd_x1.d, q.d_toi, w); });
+}
 int cd_find_ccd(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
                 cd_ccd_info *info)
-{
-    int rc = ccd_args(c, verts_end, dist, pairs, cap_pairs);
-    if (rc) return rc;
-    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
-    if ((rc = ccd_buffers(c, cap_pairs))) return rc;
-    if ((rc = ccd_enqueue(c, verts_end, dist, cap_pairs))) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return ccd_finish(c, dist, pairs, toi, dists, cap_pairs, n_pairs, info);
-}
+{ return find_ccd(c, verts_end, dist, pairs, toi, dists, cap_pairs, n_pairs, info, nullptr); }
 int cd_find_ccd_witness(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
                         cd_ccd_info *info, const cd_witness_out *w)
-{
-    if (!witness_wanted(w)) return cd_find_ccd(c, verts_end, dist, pairs, toi, dists, cap_pairs, n_pairs, info);
-    int rc = ccd_args(c, verts_end, dist, pairs, cap_pairs);
-    if (rc) return rc;
-    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
-    if ((rc = ccd_buffers(c, cap_pairs)) || (rc = c->ccd.wit.ensure(cap_pairs))) return rc;
-    if ((rc = ccd_enqueue(c, verts_end, dist, cap_pairs, c->ccd.wit.d_leaf))) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    rc = ccd_finish(c, dist, pairs, toi, dists, cap_pairs, n_pairs, info, c->ccd.wit.d_leaf);
-    if (rc != CD_OK && rc != CD_OVERFLOW) return rc;
-    const int rw = witness_results(c->stream, c->ccd.wit, c->ccd.state.h->n_pairs, cap_pairs, c, c->ccd_x1.d, c, c->ccd_x1.d, c->ccd.d_toi, w);
-    return rw ? rw : rc;
-}
+{ return find_ccd(c, verts_end, dist, pairs, toi, dists, cap_pairs, n_pairs, info, w); }
 int cd_self_ccd(cd_ctx *c, const double *verts_end, double dist, uint32_t *pairs, double *toi, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
                 cd_ccd_info *info)
 {
@@ -2342,7 +2344,7 @@ static int bw_buffers(cd_ctx *a, const cd_ctx *b, uint64_t cap_pairs, bool ccd)
 }
 // one pass (CCD: a's M, b's swept refit; descent; exact stage) and the read-back of the counters (no synchronisation).  ax1 / bx1: device
 // pointers to the end positions (CCD only).
-static int bw_enqueue(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_pairs, const double *ax1, const double *bx1, uint2 *wleaf = nullptr)
+static int bw_enqueue(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_pairs, const double *ax1, const double *bx1, uint2 *wleaf)
 {
     hipStream_t s = a->stream;
     const uint32_t na = a->nt, nb = b->nt;
@@ -2358,31 +2360,22 @@ static int bw_enqueue(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_
         k_between_descend<false><<<cdiv(na, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(b->d_recs32, b->d_root, (int)nb, a->d_leaf, a->d_verts, nullptr, (int)na,
                                                                                           a->d_boxes, b->d_boxes, dist, fa, fb, q.state.d, q.d_cand, q.shard_cap);
     }
-    const dim3 grid(shard_blocks(na), NSHARD);
-    if (kind == BW_CONTACT && !wleaf)
-        k_between_exact<BW_CONTACT, false><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
-                                                                               dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, nullptr);
-    else if (kind == BW_CONTACT)                                          // (the contour call)
-        k_between_exact<BW_CONTACT, true><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
-                                                                              dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, wleaf);
-    else if (kind == BW_PROXIMITY && wleaf)
-        k_between_exact<BW_PROXIMITY, true><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
-                                                                                dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, wleaf);
-    else if (kind == BW_PROXIMITY)
-        k_between_exact<BW_PROXIMITY, false><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, nullptr, b->d_leaf, b->d_verts, nullptr,
-                                                                                 dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, nullptr);
-    else if (wleaf)
-        k_between_exact<BW_CCD, true><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, ax1, b->d_leaf, b->d_verts, bx1,
-                                                                          dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, wleaf);
-    else
-        k_between_exact<BW_CCD, false><<<grid, PROX_EXACT_THREADS, 0, s>>>(q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, ax1, b->d_leaf, b->d_verts, bx1,
-                                                                           dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, nullptr);
+    auto exact = [&](auto k, auto wit) {
+        k_between_exact<decltype(k)::value, decltype(wit)::value><<<dim3(shard_blocks(na), NSHARD), PROX_EXACT_THREADS, 0, s>>>(
+            q.d_cand, q.shard_cap, a->d_leaf, a->d_verts, ax1, b->d_leaf, b->d_verts, bx1, dist, q.state.d, q.d_pairs, q.d_toi, q.d_dists, cap_pairs, wleaf);
+    };
+    auto of_kind = [&](auto k) { if (wleaf) exact(k, std::true_type{}); else exact(k, std::false_type{}); };
+    switch (kind) {
+    case BW_CONTACT:   of_kind(std::integral_constant<int, BW_CONTACT>{}); break;      // (with leaf positions: the contour call)
+    case BW_PROXIMITY: of_kind(std::integral_constant<int, BW_PROXIMITY>{}); break;
+    default:           of_kind(std::integral_constant<int, BW_CCD>{}); break;
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(q.state.h, q.state.d, sizeof(CcdState), hipMemcpyDeviceToHost, s));
     return CD_OK;
 }
 // enqueue, synchronise, and again with a grown candidate buffer while a shard overflowed
-static int bw_pass(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_pairs, const double *ax1, const double *bx1, uint2 *wleaf = nullptr)
+static int bw_pass(cd_ctx *a, cd_ctx *b, int kind, double dist, uint64_t cap_pairs, const double *ax1, const double *bx1, uint2 *wleaf)
 {
     for (;;) {
         int rc = bw_enqueue(a, b, kind, dist, cap_pairs, ax1, bx1, wleaf);
@@ -2399,73 +2392,50 @@ static int bw_start(cd_ctx *a, cd_ctx *b, uint64_t cap_pairs, bool ccd)
     HIPCHK(hipStreamSynchronize(b->stream));
     return CD_OK;
 }
-int cd_find_collisions_between(cd_ctx *a, cd_ctx *b, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
-{
-    int rc = bw_args(a, b, pairs, cap_pairs);
-    if (rc || (rc = bw_start(a, b, cap_pairs, false))) return rc;
-    if ((rc = bw_pass(a, b, BW_CONTACT, 0.0, cap_pairs, nullptr, nullptr))) return rc;
-    if (n_tested) *n_tested = a->bw.state.h->n_tested;
-    return a->bw.results(pairs, nullptr, nullptr, cap_pairs, n_pairs);
-}
-int cd_find_proximity_between(cd_ctx *a, cd_ctx *b, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
+// (the contact query returns a contour: find_collisions_between, behind contour_results)
+static int find_proximity_between(cd_ctx *a, cd_ctx *b, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested,
+                                  const cd_witness_out *w)
 {
     int rc = bw_args(a, b, pairs, cap_pairs);
     if (rc) return rc;
     if (!prox_dist_ok(dist)) return CD_ERR_ARG;
-    if ((rc = bw_start(a, b, cap_pairs, false))) return rc;
-    if ((rc = bw_pass(a, b, BW_PROXIMITY, dist, cap_pairs, nullptr, nullptr))) return rc;
-    if (n_tested) *n_tested = a->bw.state.h->n_tested;
-    return a->bw.results(pairs, nullptr, dists, cap_pairs, n_pairs);
+    const bool wanted = witness_wanted(w);
+    PairBuf<CcdState> &q = a->bw;
+    if ((rc = bw_start(a, b, cap_pairs, false)) || (wanted && (rc = q.wit.ensure(cap_pairs)))) return rc;
+    if ((rc = bw_pass(a, b, BW_PROXIMITY, dist, cap_pairs, nullptr, nullptr, wanted ? q.wit.d_leaf : nullptr))) return rc;
+    if (n_tested) *n_tested = q.state.h->n_tested;
+    rc = q.results(pairs, nullptr, dists, cap_pairs, n_pairs);
+    return rows_tail(wanted, rc, [&] { return witness_results(a->stream, q.wit, q.state.h->n_pairs, cap_pairs, a, nullptr, b, nullptr, nullptr, w); });
+}
+int cd_find_proximity_between(cd_ctx *a, cd_ctx *b, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
+{ return find_proximity_between(a, b, dist, pairs, dists, cap_pairs, n_pairs, n_tested, nullptr); }
+int cd_find_proximity_between_witness(cd_ctx *a, cd_ctx *b, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
+                                      uint64_t *n_tested, const cd_witness_out *w)
+{ return find_proximity_between(a, b, dist, pairs, dists, cap_pairs, n_pairs, n_tested, w); }
+static int find_ccd_between(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const double *verts_end_b, double dist, uint32_t *pairs, double *toi, double *dists,
+                            uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info, const cd_witness_out *w)
+{
+    int rc = bw_args(a, b, pairs, cap_pairs);
+    if (rc) return rc;
+    if (!ccd_dist_ok(dist)) return CD_ERR_ARG;
+    const bool wanted = witness_wanted(w);
+    PairBuf<CcdState> &q = a->bw;
+    if ((rc = bw_start(a, b, cap_pairs, true)) || (wanted && (rc = q.wit.ensure(cap_pairs)))) return rc;
+    const double *ax1 = a->d_verts, *bx1 = b->d_verts;                     // NULL: that mesh does not move (x1 = x0)
+    if (verts_end_a) { HIPCHK(hipMemcpyAsync(a->bw_x1a.d, verts_end_a, sizeof(double) * 3 * (size_t)a->nv, hipMemcpyHostToDevice, a->stream)); ax1 = a->bw_x1a.d; }
+    if (verts_end_b) { HIPCHK(hipMemcpyAsync(a->bw_x1b.d, verts_end_b, sizeof(double) * 3 * (size_t)b->nv, hipMemcpyHostToDevice, a->stream)); bx1 = a->bw_x1b.d; }
+    if ((rc = bw_pass(a, b, BW_CCD, dist, cap_pairs, ax1, bx1, wanted ? q.wit.d_leaf : nullptr))) return rc;
+    a->swept[1].seen = {true, b->nt, q.state.h->m_bits, dist};
+    q.fill_info(info);
+    rc = q.results(pairs, toi, dists, cap_pairs, n_pairs);
+    return rows_tail(wanted, rc, [&] { return witness_results(a->stream, q.wit, q.state.h->n_pairs, cap_pairs, a, ax1, b, bx1, q.d_toi, w); });
 }
 int cd_find_ccd_between(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const double *verts_end_b, double dist, uint32_t *pairs, double *toi, double *dists,
                         uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info)
-{
-    int rc = bw_args(a, b, pairs, cap_pairs);
-    if (rc) return rc;
-    if (!ccd_dist_ok(dist)) return CD_ERR_ARG;
-    if ((rc = bw_start(a, b, cap_pairs, true))) return rc;
-    const double *ax1 = a->d_verts, *bx1 = b->d_verts;                     // NULL: that mesh does not move (x1 = x0)
-    if (verts_end_a) { HIPCHK(hipMemcpyAsync(a->bw_x1a.d, verts_end_a, sizeof(double) * 3 * (size_t)a->nv, hipMemcpyHostToDevice, a->stream)); ax1 = a->bw_x1a.d; }
-    if (verts_end_b) { HIPCHK(hipMemcpyAsync(a->bw_x1b.d, verts_end_b, sizeof(double) * 3 * (size_t)b->nv, hipMemcpyHostToDevice, a->stream)); bx1 = a->bw_x1b.d; }
-    if ((rc = bw_pass(a, b, BW_CCD, dist, cap_pairs, ax1, bx1))) return rc;
-    a->swept[1].seen = {true, b->nt, a->bw.state.h->m_bits, dist};
-    a->bw.fill_info(info);
-    return a->bw.results(pairs, toi, dists, cap_pairs, n_pairs);
-}
-int cd_find_proximity_between_witness(cd_ctx *a, cd_ctx *b, double dist, uint32_t *pairs, double *dists, uint64_t cap_pairs, uint64_t *n_pairs,
-                                      uint64_t *n_tested, const cd_witness_out *w)
-{
-    if (!witness_wanted(w)) return cd_find_proximity_between(a, b, dist, pairs, dists, cap_pairs, n_pairs, n_tested);
-    int rc = bw_args(a, b, pairs, cap_pairs);
-    if (rc) return rc;
-    if (!prox_dist_ok(dist)) return CD_ERR_ARG;
-    if ((rc = bw_start(a, b, cap_pairs, false)) || (rc = a->bw.wit.ensure(cap_pairs))) return rc;
-    if ((rc = bw_pass(a, b, BW_PROXIMITY, dist, cap_pairs, nullptr, nullptr, a->bw.wit.d_leaf))) return rc;
-    if (n_tested) *n_tested = a->bw.state.h->n_tested;
-    rc = a->bw.results(pairs, nullptr, dists, cap_pairs, n_pairs);
-    if (rc != CD_OK && rc != CD_OVERFLOW) return rc;
-    const int rw = witness_results(a->stream, a->bw.wit, a->bw.state.h->n_pairs, cap_pairs, a, nullptr, b, nullptr, nullptr, w);
-    return rw ? rw : rc;
-}
+{ return find_ccd_between(a, verts_end_a, b, verts_end_b, dist, pairs, toi, dists, cap_pairs, n_pairs, info, nullptr); }
 int cd_find_ccd_between_witness(cd_ctx *a, const double *verts_end_a, cd_ctx *b, const double *verts_end_b, double dist, uint32_t *pairs, double *toi,
                                 double *dists, uint64_t cap_pairs, uint64_t *n_pairs, cd_ccd_info *info, const cd_witness_out *w)
-{
-    if (!witness_wanted(w)) return cd_find_ccd_between(a, verts_end_a, b, verts_end_b, dist, pairs, toi, dists, cap_pairs, n_pairs, info);
-    int rc = bw_args(a, b, pairs, cap_pairs);
-    if (rc) return rc;
-    if (!ccd_dist_ok(dist)) return CD_ERR_ARG;
-    if ((rc = bw_start(a, b, cap_pairs, true)) || (rc = a->bw.wit.ensure(cap_pairs))) return rc;
-    const double *ax1 = a->d_verts, *bx1 = b->d_verts;                     // NULL: that mesh does not move (x1 = x0)
-    if (verts_end_a) { HIPCHK(hipMemcpyAsync(a->bw_x1a.d, verts_end_a, sizeof(double) * 3 * (size_t)a->nv, hipMemcpyHostToDevice, a->stream)); ax1 = a->bw_x1a.d; }
-    if (verts_end_b) { HIPCHK(hipMemcpyAsync(a->bw_x1b.d, verts_end_b, sizeof(double) * 3 * (size_t)b->nv, hipMemcpyHostToDevice, a->stream)); bx1 = a->bw_x1b.d; }
-    if ((rc = bw_pass(a, b, BW_CCD, dist, cap_pairs, ax1, bx1, a->bw.wit.d_leaf))) return rc;
-    a->swept[1].seen = {true, b->nt, a->bw.state.h->m_bits, dist};
-    a->bw.fill_info(info);
-    rc = a->bw.results(pairs, toi, dists, cap_pairs, n_pairs);
-    if (rc != CD_OK && rc != CD_OVERFLOW) return rc;
-    const int rw = witness_results(a->stream, a->bw.wit, a->bw.state.h->n_pairs, cap_pairs, a, ax1, b, bx1, a->bw.d_toi, w);
-    return rw ? rw : rc;
-}
+{ return find_ccd_between(a, verts_end_a, b, verts_end_b, dist, pairs, toi, dists, cap_pairs, n_pairs, info, w); }
 // ---- the contour of the contact queries (cd_contour.h) ------------------------------------------------------------------------------
 // NULL, or every member NULL: no contour kernel
 static bool contour_wanted(const cd_contour_out *w) { return w && (w->faces || w->code || w->param || w->points); }
@@ -2514,22 +2484,25 @@ int cd_find_collisions_contour(cd_ctx *c, uint32_t *pairs, uint64_t cap_pairs, u
     }
     if (n_tested) *n_tested = q.state.h->n_tested;
     rc = q.results(pairs, nullptr, nullptr, cap_pairs, n_pairs);
-    if (!wanted || (rc != CD_OK && rc != CD_OVERFLOW)) return rc;
-    const int rw = contour_results(s, q.con, q.state.h->n_pairs, cap_pairs, c, c, w);
-    return rw ? rw : rc;
+    return rows_tail(wanted, rc, [&] { return contour_results(s, q.con, q.state.h->n_pairs, cap_pairs, c, c, w); });
 }
-int cd_find_collisions_between_contour(cd_ctx *a, cd_ctx *b, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested, const cd_contour_out *w)
+// The call between two meshes (cd_between.h), in a's buffers.  w without a member set (or NULL): the plain call
+static int find_collisions_between(cd_ctx *a, cd_ctx *b, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested, const cd_contour_out *w)
 {
-    if (!contour_wanted(w)) return cd_find_collisions_between(a, b, pairs, cap_pairs, n_pairs, n_tested);
     int rc = bw_args(a, b, pairs, cap_pairs);
-    if (rc || (rc = bw_start(a, b, cap_pairs, false)) || (rc = a->bw.con.ensure(cap_pairs))) return rc;
-    if ((rc = bw_pass(a, b, BW_CONTACT, 0.0, cap_pairs, nullptr, nullptr, a->bw.con.d_leaf))) return rc;
-    if (n_tested) *n_tested = a->bw.state.h->n_tested;
-    rc = a->bw.results(pairs, nullptr, nullptr, cap_pairs, n_pairs);
-    if (rc != CD_OK && rc != CD_OVERFLOW) return rc;
-    const int rw = contour_results(a->stream, a->bw.con, a->bw.state.h->n_pairs, cap_pairs, a, b, w);
-    return rw ? rw : rc;
+    if (rc) return rc;
+    const bool wanted = contour_wanted(w);
+    PairBuf<CcdState> &q = a->bw;
+    if ((rc = bw_start(a, b, cap_pairs, false)) || (wanted && (rc = q.con.ensure(cap_pairs)))) return rc;
+    if ((rc = bw_pass(a, b, BW_CONTACT, 0.0, cap_pairs, nullptr, nullptr, wanted ? q.con.d_leaf : nullptr))) return rc;
+    if (n_tested) *n_tested = q.state.h->n_tested;
+    rc = q.results(pairs, nullptr, nullptr, cap_pairs, n_pairs);
+    return rows_tail(wanted, rc, [&] { return contour_results(a->stream, q.con, q.state.h->n_pairs, cap_pairs, a, b, w); });
 }
+int cd_find_collisions_between(cd_ctx *a, cd_ctx *b, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested)
+{ return find_collisions_between(a, b, pairs, cap_pairs, n_pairs, n_tested, nullptr); }
+int cd_find_collisions_between_contour(cd_ctx *a, cd_ctx *b, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, uint64_t *n_tested, const cd_contour_out *w)
+{ return find_collisions_between(a, b, pairs, cap_pairs, n_pairs, n_tested, w); }
 int cd_tri_isect_points(const double *tri, uint64_t n, uint8_t *code, double *param, double *points)
 {
     if (!tri || !code) return CD_ERR_ARG;

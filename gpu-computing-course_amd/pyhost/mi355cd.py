@@ -300,6 +300,16 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _verts_end(v, nv, what, optional=False):
+    """The end positions of a CCD call as f64[nv, 3] (optional: None stays None, that mesh does not move)."""
+    if v is None and optional:
+        return None
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if v.shape != (nv, 3):
+        raise ValueError(f"{what} must be [{nv}, 3], got {v.shape}")
+    return v
+
+
 class CollisionDetector:
     """One cd_ctx.  Methods mirror the reference harness's stage order (main.cu:64-146)."""
 
@@ -423,189 +433,105 @@ class CollisionDetector:
             return np.zeros((0, 2), dtype=np.uint32), n.value, rc
         return (buf[:got].copy() if copy else buf[:got]), n.value, rc
 
-    def _proximity_call(self, fn, name, dist, cap):
-        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
-        dists = np.empty(max(cap, 1), dtype=np.float64)
-        n, tested = C.c_uint64(0), C.c_uint64(0)
-        rc = fn(self._ctx, float(dist), _ptr(pairs) if cap else None, _ptr(dists), cap, C.byref(n), C.byref(tested))
+    def _pair_query(self, name, pre, cap, toi=False, dists=False, ccd=False, extra=None):
+        """A pair query into fresh arrays: the C function `name` called as (*pre, pairs, [toi], [dists], cap, &n, &count, [&extra.out]),
+        count being a CdCcdInfo (ccd) or n_tested; extra: a _WitnessArrays / _ContourArrays.  Returns (count, the public tuple): the
+        arrays the call has clipped to min(n, cap) and copied, n, rc, and extra's rows."""
+        arrays = [np.empty((max(cap, 1), 2), dtype=np.uint32)] + [np.empty(max(cap, 1), dtype=np.float64) for has in (toi, dists) if has]
+        n, count = C.c_uint64(0), CdCcdInfo() if ccd else C.c_uint64(0)
+        last = () if extra is None else (C.byref(extra.out),)
+        rc = getattr(self.lib, name)(*pre, _ptr(arrays[0]) if cap else None, *map(_ptr, arrays[1:]), cap, C.byref(n), C.byref(count), *last)
         self._chk(name, rc, allow=(CD_OK, CD_OVERFLOW))
-        self.proximity_tested = tested.value
         got = min(n.value, cap)
-        return pairs[:got].copy(), dists[:got].copy(), n.value, rc
+        out = [a[:got].copy() for a in arrays] + [n.value, rc] + ([] if extra is None else [extra.take(got)])
+        return (count if ccd else count.value), tuple(out)
 
     def find_proximity(self, dist: float, cap: int = 1 << 20):
         """cd_find_proximity on the tree that is there: (pairs[n, 2] (smaller ID, larger ID), dists[n], n, rc); n may exceed cap
         (rc = CD_OVERFLOW, the first cap pairs are returned).  self.proximity_tested: exact distance evaluations made."""
-        return self._proximity_call(self.lib.cd_find_proximity, "cd_find_proximity", dist, cap)
+        self.proximity_tested, out = self._pair_query("cd_find_proximity", (self._ctx, float(dist)), cap, dists=True)
+        return out
 
     def self_proximity(self, dist: float, cap: int = 1 << 20):
         """cd_self_proximity: build the tree, then find_proximity, with one host synchronisation."""
-        return self._proximity_call(self.lib.cd_self_proximity, "cd_self_proximity", dist, cap)
+        self.proximity_tested, out = self._pair_query("cd_self_proximity", (self._ctx, float(dist)), cap, dists=True)
+        return out
 
     def find_proximity_witness(self, dist: float, cap: int = 1 << 20):
         """cd_find_proximity_witness: find_proximity's (pairs, dists, n, rc) and a Witness whose row k says where dists[k] is attained."""
-        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
-        dists = np.empty(max(cap, 1), dtype=np.float64)
-        wa = _WitnessArrays(cap)
-        n, tested = C.c_uint64(0), C.c_uint64(0)
-        rc = self.lib.cd_find_proximity_witness(self._ctx, float(dist), _ptr(pairs) if cap else None, _ptr(dists), cap, C.byref(n), C.byref(tested),
-                                                C.byref(wa.out))
-        self._chk("cd_find_proximity_witness", rc, allow=(CD_OK, CD_OVERFLOW))
-        self.proximity_tested = tested.value
-        got = min(n.value, cap)
-        return pairs[:got].copy(), dists[:got].copy(), n.value, rc, wa.take(got)
+        self.proximity_tested, out = self._pair_query("cd_find_proximity_witness", (self._ctx, float(dist)), cap, dists=True, extra=_WitnessArrays(cap))
+        return out
 
     def find_ccd_witness(self, verts_end, dist: float, cap: int = 1 << 20):
         """cd_find_ccd_witness: find_ccd's (pairs, toi, dists, n, rc) and a Witness taken at the evaluation that reported each pair."""
-        v = np.ascontiguousarray(verts_end, dtype=np.float64)
-        if v.shape != (self.nv, 3):
-            raise ValueError(f"verts_end must be [{self.nv}, 3], got {v.shape}")
-        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
-        toi = np.empty(max(cap, 1), dtype=np.float64)
-        dists = np.empty(max(cap, 1), dtype=np.float64)
-        wa = _WitnessArrays(cap)
-        n, info = C.c_uint64(0), CdCcdInfo()
-        rc = self.lib.cd_find_ccd_witness(self._ctx, _ptr(v), float(dist), _ptr(pairs) if cap else None, _ptr(toi), _ptr(dists), cap, C.byref(n),
-                                          C.byref(info), C.byref(wa.out))
-        self._chk("cd_find_ccd_witness", rc, allow=(CD_OK, CD_OVERFLOW))
-        self.ccd_info = info
-        got = min(n.value, cap)
-        return pairs[:got].copy(), toi[:got].copy(), dists[:got].copy(), n.value, rc, wa.take(got)
+        pre = (self._ctx, _ptr(_verts_end(verts_end, self.nv, "verts_end")), float(dist))
+        self.ccd_info, out = self._pair_query("cd_find_ccd_witness", pre, cap, toi=True, dists=True, ccd=True, extra=_WitnessArrays(cap))
+        return out
 
     def find_proximity_between_witness(self, other, dist: float, cap: int = 1 << 20):
         """cd_find_proximity_between_witness: find_proximity_between's (pairs, dists, n, rc) and a Witness (A: self's triangle; faces
         index each context's own face list)."""
-        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
-        dists = np.empty(max(cap, 1), dtype=np.float64)
-        wa = _WitnessArrays(cap)
-        n, tested = C.c_uint64(0), C.c_uint64(0)
-        rc = self.lib.cd_find_proximity_between_witness(self._ctx, other._ctx, float(dist), _ptr(pairs) if cap else None, _ptr(dists), cap,
-                                                        C.byref(n), C.byref(tested), C.byref(wa.out))
-        self._chk("cd_find_proximity_between_witness", rc, allow=(CD_OK, CD_OVERFLOW))
-        self.between_tested = tested.value
-        got = min(n.value, cap)
-        return pairs[:got].copy(), dists[:got].copy(), n.value, rc, wa.take(got)
+        pre = (self._ctx, other._ctx, float(dist))
+        self.between_tested, out = self._pair_query("cd_find_proximity_between_witness", pre, cap, dists=True, extra=_WitnessArrays(cap))
+        return out
 
     def find_ccd_between_witness(self, other, dist: float, verts_end=None, other_verts_end=None, cap: int = 1 << 20):
         """cd_find_ccd_between_witness: find_ccd_between's (pairs, toi, dists, n, rc) and a Witness."""
-        def end(v, nv, what):
-            if v is None:
-                return None
-            v = np.ascontiguousarray(v, dtype=np.float64)
-            if v.shape != (nv, 3):
-                raise ValueError(f"{what} must be [{nv}, 3], got {v.shape}")
-            return v
-        va = end(verts_end, self.nv, "verts_end")
-        vb = end(other_verts_end, other.nv, "other_verts_end")
-        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
-        toi = np.empty(max(cap, 1), dtype=np.float64)
-        dists = np.empty(max(cap, 1), dtype=np.float64)
-        wa = _WitnessArrays(cap)
-        n, info = C.c_uint64(0), CdCcdInfo()
-        rc = self.lib.cd_find_ccd_between_witness(self._ctx, _ptr(va), other._ctx, _ptr(vb), float(dist), _ptr(pairs) if cap else None,
-                                                  _ptr(toi), _ptr(dists), cap, C.byref(n), C.byref(info), C.byref(wa.out))
-        self._chk("cd_find_ccd_between_witness", rc, allow=(CD_OK, CD_OVERFLOW))
-        self.ccd_info = info
-        got = min(n.value, cap)
-        return pairs[:got].copy(), toi[:got].copy(), dists[:got].copy(), n.value, rc, wa.take(got)
-
-    def _ccd_call(self, fn, name, verts_end, dist, cap):
-        v = np.ascontiguousarray(verts_end, dtype=np.float64)
-        if v.shape != (self.nv, 3):
-            raise ValueError(f"verts_end must be [{self.nv}, 3], got {v.shape}")
-        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
-        toi = np.empty(max(cap, 1), dtype=np.float64)
-        dists = np.empty(max(cap, 1), dtype=np.float64)
-        n, info = C.c_uint64(0), CdCcdInfo()
-        rc = fn(self._ctx, _ptr(v), float(dist), _ptr(pairs) if cap else None, _ptr(toi), _ptr(dists), cap, C.byref(n), C.byref(info))
-        self._chk(name, rc, allow=(CD_OK, CD_OVERFLOW))
-        self.ccd_info = info
-        got = min(n.value, cap)
-        return pairs[:got].copy(), toi[:got].copy(), dists[:got].copy(), n.value, rc
+        pre = self._ccd_between_pre(other, dist, verts_end, other_verts_end)
+        self.ccd_info, out = self._pair_query("cd_find_ccd_between_witness", pre, cap, toi=True, dists=True, ccd=True, extra=_WitnessArrays(cap))
+        return out
 
     def find_ccd(self, verts_end, dist: float, cap: int = 1 << 20):
         """cd_find_ccd on the tree that is there, the vertices moving linearly to verts_end: (pairs[n, 2] (smaller ID, larger ID),
         toi[n], dists[n], n, rc); n may exceed cap (rc = CD_OVERFLOW, the first cap pairs are returned).  A returned distance > dist
         marks a pair left unresolved.  self.ccd_info: candidates, pairs through the gate, evaluations, unresolved pairs."""
-        return self._ccd_call(self.lib.cd_find_ccd, "cd_find_ccd", verts_end, dist, cap)
+        pre = (self._ctx, _ptr(_verts_end(verts_end, self.nv, "verts_end")), float(dist))
+        self.ccd_info, out = self._pair_query("cd_find_ccd", pre, cap, toi=True, dists=True, ccd=True)
+        return out
 
     def self_ccd(self, verts_end, dist: float, cap: int = 1 << 20):
         """cd_self_ccd: build the tree on the current vertices, then find_ccd, with one host synchronisation."""
-        return self._ccd_call(self.lib.cd_self_ccd, "cd_self_ccd", verts_end, dist, cap)
+        pre = (self._ctx, _ptr(_verts_end(verts_end, self.nv, "verts_end")), float(dist))
+        self.ccd_info, out = self._pair_query("cd_self_ccd", pre, cap, toi=True, dists=True, ccd=True)
+        return out
 
     # ---- queries between this mesh (a) and another context's (b): pairs (ID in self, ID in other), self's triangle first
     def find_collisions_contour(self, cap: int = 1 << 20):
         """cd_find_collisions_contour: (pairs[n, 2] (smaller ID, larger ID), n, rc, Contour) -- find_collisions' pair set from a pass of
         its own, and per pair the segment the two triangles cut each other in.  self.contour_tested: pairs that reached tri_contact.  The
         tree must be built from the current vertices."""
-        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
-        ca = _ContourArrays(cap)
-        n, tested = C.c_uint64(0), C.c_uint64(0)
-        rc = self.lib.cd_find_collisions_contour(self._ctx, _ptr(pairs) if cap else None, cap, C.byref(n), C.byref(tested), C.byref(ca.out))
-        self._chk("cd_find_collisions_contour", rc, allow=(CD_OK, CD_OVERFLOW))
-        self.contour_tested = tested.value
-        got = min(n.value, cap)
-        return pairs[:got].copy(), n.value, rc, ca.take(got)
+        self.contour_tested, out = self._pair_query("cd_find_collisions_contour", (self._ctx,), cap, extra=_ContourArrays(cap))
+        return out
 
     def find_collisions_between_contour(self, other, cap: int = 1 << 20):
         """cd_find_collisions_between_contour: find_collisions_between's (pairs, n, rc) and a Contour (A: self's triangle; faces index each
         context's own face list)."""
-        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
-        ca = _ContourArrays(cap)
-        n, tested = C.c_uint64(0), C.c_uint64(0)
-        rc = self.lib.cd_find_collisions_between_contour(self._ctx, other._ctx, _ptr(pairs) if cap else None, cap, C.byref(n), C.byref(tested),
-                                                         C.byref(ca.out))
-        self._chk("cd_find_collisions_between_contour", rc, allow=(CD_OK, CD_OVERFLOW))
-        self.between_tested = tested.value
-        got = min(n.value, cap)
-        return pairs[:got].copy(), n.value, rc, ca.take(got)
+        self.between_tested, out = self._pair_query("cd_find_collisions_between_contour", (self._ctx, other._ctx), cap, extra=_ContourArrays(cap))
+        return out
 
     def find_collisions_between(self, other, cap: int = 1 << 20):
         """cd_find_collisions_between(self, other): (pairs[n, 2] (ID in self, ID in other), n, rc); n may exceed cap (rc = CD_OVERFLOW,
         the first cap pairs are returned).  self.between_tested: pairs whose FP64 boxes overlap strictly.  Both trees must be built."""
-        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
-        n, tested = C.c_uint64(0), C.c_uint64(0)
-        rc = self.lib.cd_find_collisions_between(self._ctx, other._ctx, _ptr(pairs) if cap else None, cap, C.byref(n), C.byref(tested))
-        self._chk("cd_find_collisions_between", rc, allow=(CD_OK, CD_OVERFLOW))
-        self.between_tested = tested.value
-        got = min(n.value, cap)
-        return pairs[:got].copy(), n.value, rc
+        self.between_tested, out = self._pair_query("cd_find_collisions_between", (self._ctx, other._ctx), cap)
+        return out
 
     def find_proximity_between(self, other, dist: float, cap: int = 1 << 20):
         """cd_find_proximity_between(self, other, dist): (pairs[n, 2] (ID in self, ID in other), dists[n], n, rc).
         self.between_tested: exact distance evaluations made."""
-        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
-        dists = np.empty(max(cap, 1), dtype=np.float64)
-        n, tested = C.c_uint64(0), C.c_uint64(0)
-        rc = self.lib.cd_find_proximity_between(self._ctx, other._ctx, float(dist), _ptr(pairs) if cap else None, _ptr(dists), cap,
-                                                C.byref(n), C.byref(tested))
-        self._chk("cd_find_proximity_between", rc, allow=(CD_OK, CD_OVERFLOW))
-        self.between_tested = tested.value
-        got = min(n.value, cap)
-        return pairs[:got].copy(), dists[:got].copy(), n.value, rc
+        self.between_tested, out = self._pair_query("cd_find_proximity_between", (self._ctx, other._ctx, float(dist)), cap, dists=True)
+        return out
+
+    def _ccd_between_pre(self, other, dist, verts_end, other_verts_end):
+        va = _verts_end(verts_end, self.nv, "verts_end", optional=True)
+        vb = _verts_end(other_verts_end, other.nv, "other_verts_end", optional=True)
+        return self._ctx, _ptr(va), other._ctx, _ptr(vb), float(dist)
 
     def find_ccd_between(self, other, dist: float, verts_end=None, other_verts_end=None, cap: int = 1 << 20):
         """cd_find_ccd_between: self's vertices move to verts_end, other's to other_verts_end (None: that mesh does not move):
         (pairs[n, 2] (ID in self, ID in other), toi[n], dists[n], n, rc).  self.ccd_info: as find_ccd's."""
-        def end(v, nv, what):
-            if v is None:
-                return None
-            v = np.ascontiguousarray(v, dtype=np.float64)
-            if v.shape != (nv, 3):
-                raise ValueError(f"{what} must be [{nv}, 3], got {v.shape}")
-            return v
-        va = end(verts_end, self.nv, "verts_end")
-        vb = end(other_verts_end, other.nv, "other_verts_end")
-        pairs = np.empty((max(cap, 1), 2), dtype=np.uint32)
-        toi = np.empty(max(cap, 1), dtype=np.float64)
-        dists = np.empty(max(cap, 1), dtype=np.float64)
-        n, info = C.c_uint64(0), CdCcdInfo()
-        rc = self.lib.cd_find_ccd_between(self._ctx, _ptr(va), other._ctx, _ptr(vb), float(dist), _ptr(pairs) if cap else None,
-                                          _ptr(toi), _ptr(dists), cap, C.byref(n), C.byref(info))
-        self._chk("cd_find_ccd_between", rc, allow=(CD_OK, CD_OVERFLOW))
-        self.ccd_info = info
-        got = min(n.value, cap)
-        return pairs[:got].copy(), toi[:got].copy(), dists[:got].copy(), n.value, rc
+        pre = self._ccd_between_pre(other, dist, verts_end, other_verts_end)
+        self.ccd_info, out = self._pair_query("cd_find_ccd_between", pre, cap, toi=True, dists=True, ccd=True)
+        return out
 
     # ---- ray queries against this mesh (cd_cast_rays)
     def cast_rays(self, origins, dirs, tmax=np.inf, any_hit: bool = False):

@@ -274,6 +274,39 @@ def test_capacity_growth_and_null_outputs(ccd):
         assert all(np.all(x.view(np.uint8) == CANARY) for x in (q.points, q.bary, q.feature))
 
 
+@pytest.mark.parametrize("ccd", [False, True], ids=["proximity", "ccd"])
+def test_between_null_witness_is_the_plain_call(ccd):
+    """cd_find_proximity_between_witness / cd_find_ccd_between_witness with a NULL w, and with a w whose members are all NULL, against
+    the plain between call; then with every member set, in the same context."""
+    verts, vidx, ids, edge = wr.self_meshes()["n65"]
+    x1 = np.ascontiguousarray(br.motion(verts, 0.1 * edge, 3)) if ccd else None
+    bv, bi = br.soup(63, 0.3, 31)
+    d = 0.15                                        # between_ref on these meshes: 17 proximity pairs, 19 CCD pairs
+    with mi355cd.CollisionDetector(verts, vidx) as cd, mi355cd.CollisionDetector(bv, bi) as ob:
+        cd.build_tree()
+        ob.build_tree()
+        *plain, n0, rc0 = cd.find_ccd_between(ob, d, verts_end=x1) if ccd else cd.find_proximity_between(ob, d)
+        assert rc0 == mi355cd.CD_OK and n0 >= 8
+        plain = wr.sort_by_ids(*plain)
+        for w in (None, mi355cd.CdWitnessOut(), "own"):
+            q, n = _Raw(n0 + 8, ccd), C.c_uint64(0)
+            wp = None if w is None else C.byref(q.out if w == "own" else w)
+            if ccd:
+                rc = cd.lib.cd_find_ccd_between_witness(cd._ctx, x1.ctypes.data, ob._ctx, None, d, q.pairs.ctypes.data, q.toi.ctypes.data,
+                                                        q.dists.ctypes.data, n0, C.byref(n), None, wp)
+            else:
+                rc = cd.lib.cd_find_proximity_between_witness(cd._ctx, ob._ctx, d, q.pairs.ctypes.data, q.dists.ctypes.data, n0, C.byref(n), None, wp)
+            assert (rc, n.value) == (rc0, n0), w
+            vals = (q.toi[:n0], q.dists[:n0]) if ccd else (q.dists[:n0],)
+            for g, p in zip(wr.sort_by_ids(q.pairs[:n0], *vals), plain):
+                assert np.array_equal(g, p), w
+            assert q.untouched_from(n0)
+            if w == "own":
+                assert not np.any(np.all(q.faces[:n0].view(np.uint8) == CANARY, axis=1))      # every row written
+            else:
+                assert all(np.all(x.view(np.uint8) == CANARY) for x in (q.faces, q.points, q.bary, q.feature))
+
+
 # ---------------------------------------------------------------- state the calls leave alone
 def test_witness_calls_leave_the_context_as_it_was():
     name = "soup10k"
