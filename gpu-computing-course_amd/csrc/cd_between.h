@@ -80,8 +80,8 @@ __global__ __launch_bounds__(PROX_DESC_THREADS) void k_between_descend(const Nod
                               : box_set(load_vertex(ax0, lt.v0), load_vertex(ax0, lt.v1), load_vertex(ax0, lt.v2)), pad);
         active = w.start_root(recs_b, nb, (uint32_t)*root_name_b);
     }
-    if (SWEPT) prox_walk<HiTrue>(recs_b, nb, j, active, w, q, st->shard, cand, shard_cap);
-    else prox_walk<HiNextUp>(recs_b, nb, j, active, w, q, st->shard, cand, shard_cap);
+    if (SWEPT) prox_walk(recs_b, nb, j, active, w, BoxFilter<HiTrue>{q}, st->shard, cand, shard_cap);
+    else prox_walk(recs_b, nb, j, active, w, BoxFilter<HiNextUp>{q}, st->shard, cand, shard_cap);
 }
 
 template <int KIND, bool WIT>                          // (WIT, the witness calls: wleaf[at] = (leaf of a, leaf of b) of the hit, as k_prox_exact)

@@ -207,7 +207,7 @@ __global__ __launch_bounds__(PROX_DESC_THREADS) void k_ccd_descend(const NodeRec
         q = query_box32(swept_box(CcdMeshSrc{x0, x1, lt.v0, lt.v1, lt.v2, 0u, 0u, 0u}, 0), pad);
         w.start_behind(recs, n, j);
     }
-    prox_walk<HiTrue>(recs, n, j, active, w, q, st->shard, cand, shard_cap);
+    prox_walk(recs, n, j, active, w, BoxFilter<HiTrue>{q}, st->shard, cand, shard_cap);
 }
 
 template <bool WIT>                                    // (the witness calls: wleaf[at] = the hit's leaf positions, A's first, as k_prox_exact)

@@ -74,12 +74,20 @@ __device__ __forceinline__ QueryBox32 query_box32(const Box &b, float pad)
                       __ocml_add_rtp_f32(__double2float_ru(b.x2), pad), __ocml_add_rtp_f32(__double2float_ru(b.y2), pad), __ocml_add_rtp_f32(__double2float_ru(b.z2), pad)};
 }
 
-// The pair queries' descent, written once (k_prox_descend, k_ccd_descend, k_between_descend): the walk of cd_bvh.h from where the caller
-// started the cursor `w`, entering every subtree whose box the query box `q` meets, and its candidate queue.  Leaf hits (j, k) go through a
+// A walk's filter over a query box: prox_walk's `q` of the pair queries (Hi: how the records' hi is read)
+template <class Hi>
+struct BoxFilter {
+    QueryBox32 box;
+    __device__ __forceinline__ bool meets(const RecCursor &w) const { return box.meets<Hi>(w); }
+};
+
+// The queued descent, written once (k_prox_descend, k_ccd_descend, k_between_descend; the all-results item queries of cd_within.h): the walk
+// of cd_bvh.h from where the caller started the cursor `w`, entering every subtree the filter `q` says the query meets (q.meets(w): a query box
+// for the pair queries, BoxFilter; a point's or a ray's own box test in cd_within.h), and its candidate queue.  Leaf hits (j, k) go through a
 // wave-shared LDS queue to the workgroup's shard of `cand`, 64 at a time (nothing is written past shard_cap; the shard's counter counts all).
 // One wave per workgroup; every lane of it calls this (inactive lanes with active = false).
-template <class Hi>
-__device__ __forceinline__ void prox_walk(const NodeRec32 *__restrict__ recs, int n, uint32_t j, bool active, RecCursor w, const QueryBox32 q,
+template <class Filter>
+__device__ __forceinline__ void prox_walk(const NodeRec32 *__restrict__ recs, int n, uint32_t j, bool active, RecCursor w, const Filter q,
                                           unsigned long long *__restrict__ shard_ctr /* ProxState / CcdState ::shard */, uint2 *__restrict__ cand, unsigned long long shard_cap)
 {
     __shared__ uint2 queue[PROX_QCAP];
@@ -91,7 +99,7 @@ __device__ __forceinline__ void prox_walk(const NodeRec32 *__restrict__ recs, in
     while (__ballot(active) != 0ull) {
         bool hit = false; uint32_t k = 0;
         if (active) {
-            const bool ov = q.meets<Hi>(w);
+            const bool ov = q.meets(w);
             if (ov && w.internal(n)) active = w.descend(recs, n);
             else {
                 if (ov && w.leaf(n)) { hit = true; k = w.leaf_index(); }
@@ -136,7 +144,7 @@ __global__ __launch_bounds__(PROX_DESC_THREADS) void k_prox_descend(const NodeRe
         q = query_box32(box_set(load_vertex(verts, lt.v0), load_vertex(verts, lt.v1), load_vertex(verts, lt.v2)), pad);
         w.start_behind(recs, n, j);
     }
-    prox_walk<HiNextUp>(recs, n, j, active, w, q, st->shard, cand, shard_cap);
+    prox_walk(recs, n, j, active, w, BoxFilter<HiNextUp>{q}, st->shard, cand, shard_cap);
 }
 
 // ---------------------------------------------------------------- the exact stage's scaffold

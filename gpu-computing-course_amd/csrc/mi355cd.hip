@@ -15,6 +15,7 @@
 #include "cd_rays.h"
 #include "cd_points.h"
 #include "cd_nearest.h"
+#include "cd_within.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -247,6 +248,22 @@ struct ItemBuf {
     int ensure(uint64_t n, uint64_t bytes_per_item) { const int rc = state.ensure(); return rc ? rc : block.ensure(n, bytes_per_item); }
 };
 
+// What an all-results item query (cd_points_within, cd_cast_rays_all, cd_within.h) owns: a pair query's record -- counters, candidate
+// shards, the rows (d_pairs: item, face) and their dist / t (d_dists) -- the items, and ONE block of the rows' other values, which the
+// entry point carves
+struct ItemRowsBuf {
+    PairBuf<ProxState> q;
+    DevArray<char> items, vals;
+    void release() { q.release(); items.release(); vals.release(); }
+    int ensure(uint64_t n, uint64_t bytes_per_item, uint64_t cap_rows, uint64_t bytes_per_row)
+    {
+        int rc = q.shard_cap ? CD_OK : q.alloc_cand(WITHIN_SHARD_FIRST);     // (before q.ensure, which would size the shards by a triangle count)
+        if (!rc) rc = q.ensure(0, cap_rows);
+        if (!rc) rc = items.ensure(n, bytes_per_item);
+        return rc ? rc : vals.ensure(std::max<uint64_t>(cap_rows, 1), bytes_per_row);
+    }
+};
+
 struct cd_multi;
 struct cd_ctx {
     uint32_t nv = 0, nt = 0;
@@ -378,6 +395,10 @@ struct cd_ctx {
     // their own, na + 1 rows (the last one: CD_NEAREST_MIN's).
     // nearest.block: dist [n] | points [6 n] | bary [4 n] (doubles) | leaf pair [n] (uint2) | faces [2 n] | ids [2 n] (u32) | feature [2 n] (u8)
     ItemBuf<NearestState> nearest;
+    // all-results item queries (cd_points_within, cd_cast_rays_all, cd_within.h): buffers of their own, allocated on first use.
+    // within.items: points [4 n];   within.vals: closest [3 cap] | uv [2 cap] (doubles) | ids [cap] (u32) | feature [cap] | side [cap] (u8)
+    // rays_all.items: rays [7 n];   rays_all.vals: uv [2 cap] (doubles) | ids [cap] (u32) | side [cap] (u8)
+    ItemRowsBuf within, rays_all;
 };
 
 namespace {
@@ -406,7 +427,7 @@ void free_all(cd_ctx *c)
     hipFree(c->pp_flags); hipFree(c->pp_os);
     c->prox.release(); c->cont.release(); c->ccd.release(); c->bw.release(); c->ccd_x1.release(); c->bw_x1a.release(); c->bw_x1b.release();
     for (SweptBuf &sw : c->swept) sw.release();
-    c->rays.release(); c->points.release(); c->nearest.release();
+    c->rays.release(); c->points.release(); c->nearest.release(); c->within.release(); c->rays_all.release();
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -2525,17 +2546,23 @@ int cd_tri_isect_points(const double *tri, uint64_t n, uint8_t *code, double *pa
 // ---- ray queries (cd_rays.h) ------------------------------------------------------------------------------------------------------
 // Own buffers (rays, results, counters): nothing any other call keeps is touched.
 constexpr uint64_t RAY_BYTES = 7 * 8 + 8 + 16 + 4 + 4 + 1;                  // device bytes a ray: the ray, t, uv, face, ID, side
-int cd_cast_rays(cd_ctx *c, const double *rays, uint64_t n, int flags, uint32_t *face, uint32_t *ids, double *t, double *uv, uint8_t *side, cd_ray_info *info)
+// every ray has a finite origin and direction, a direction that is not all zero and a tmax >= 0 (a NaN tmax fails the comparison)
+static bool rays_ok(const double *rays, uint64_t n)
 {
-    const bool any = flags == CD_RAY_ANY;
-    if (!c || (flags != 0 && !any) || (n && (!rays || !face)) || (any && (ids || t || uv || side)) || n > (1ull << 37)) return CD_ERR_ARG;
-    for (uint64_t i = 0; i < n; ++i) {                                      // before anything is launched: nothing is written for a bad ray
+    for (uint64_t i = 0; i < n; ++i) {
         const double *r = rays + 7 * i;
         bool finite = true, zero = true;
         for (int k = 0; k < 6; ++k) finite = finite && std::isfinite(r[k]);
         for (int k = 3; k < 6; ++k) zero = zero && r[k] == 0.0;
-        if (!finite || zero || !(r[6] >= 0.0)) return CD_ERR_ARG;          // (a NaN tmax fails the comparison)
+        if (!finite || zero || !(r[6] >= 0.0)) return false;
     }
+    return true;
+}
+int cd_cast_rays(cd_ctx *c, const double *rays, uint64_t n, int flags, uint32_t *face, uint32_t *ids, double *t, double *uv, uint8_t *side, cd_ray_info *info)
+{
+    const bool any = flags == CD_RAY_ANY;
+    if (!c || (flags != 0 && !any) || (n && (!rays || !face)) || (any && (ids || t || uv || side)) || n > (1ull << 37)) return CD_ERR_ARG;
+    if (!rays_ok(rays, n)) return CD_ERR_ARG;                               // before anything is launched: nothing is written for a bad ray
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if (n == 0) { if (info) *info = cd_ray_info{0, 0, 0}; return CD_OK; }
     int rc = c->rays.ensure(n, RAY_BYTES);
@@ -2585,15 +2612,21 @@ int cd_ray_tri_points(const double *ray, const double *tri, uint64_t n, uint8_t 
 // ---- closest-point queries (cd_points.h) ------------------------------------------------------------------------------------------
 // Own buffers (points, results, counters): nothing any other call keeps is touched.
 constexpr uint64_t POINT_BYTES = 4 * 8 + 8 + 24 + 16 + 4 + 4 + 1 + 1;       // device bytes a point: the point, dist, closest, uv, face, ID, feature, side
+// every point has finite coordinates and an rmax >= 0 (a NaN rmax fails the comparison)
+static bool points_ok(const double *points, uint64_t n)
+{
+    for (uint64_t i = 0; i < n; ++i) {
+        const double *r = points + 4 * i;
+        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2]) || !(r[3] >= 0.0)) return false;
+    }
+    return true;
+}
 int cd_closest_points(cd_ctx *c, const double *points, uint64_t n, int flags, uint32_t *face, uint32_t *ids, double *dist, double *closest, double *uv,
                       uint8_t *feature, uint8_t *side, cd_point_info *info)
 {
     const bool any = flags == CD_POINT_ANY;
     if (!c || (flags != 0 && !any) || (n && (!points || !face)) || (any && (ids || dist || closest || uv || feature || side)) || n > (1ull << 37)) return CD_ERR_ARG;
-    for (uint64_t i = 0; i < n; ++i) {                                      // before anything is launched: nothing is written for a bad point
-        const double *r = points + 4 * i;
-        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2]) || !(r[3] >= 0.0)) return CD_ERR_ARG;   // (a NaN rmax fails the comparison)
-    }
+    if (!points_ok(points, n)) return CD_ERR_ARG;                           // before anything is launched: nothing is written for a bad point
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if (n == 0) { if (info) *info = cd_point_info{0, 0, 0}; return CD_OK; }
     int rc = c->points.ensure(n, POINT_BYTES);
@@ -2643,6 +2676,97 @@ int cd_pt_tri_points(const double *points, const double *tri, uint64_t n, double
     dev.back(feature, d_f, n);
     dev.back(side, d_s, n);
     return dev.rc();
+}
+// ---- all-results item queries (cd_within.h) -----------------------------------------------------------------------------------------
+// Own buffers (items, candidates, rows, counters): nothing any other call keeps is touched.  The pass is the pair queries': descent, exact
+// stage, the counters' read-back, one synchronisation; a shard that overflowed grows the candidate buffer and the pass runs again.
+constexpr uint64_t WITHIN_ROW_BYTES = 24 + 16 + 4 + 1 + 1;                  // device bytes a row besides (item, face) and dist: closest, uv, ID, feature, side
+constexpr uint64_t RAYS_ALL_ROW_BYTES = 16 + 4 + 1;                         // besides (item, face) and t: uv, ID, side
+// the argument rules both calls share, before the items are read
+static int item_rows_args(const cd_ctx *c, const double *items, uint64_t n, const uint32_t *rows, uint64_t cap_rows, const uint64_t *n_rows)
+{
+    return (!c || !n_rows || n > 0xffffffffull || (n && !items) || (cap_rows && !rows)) ? CD_ERR_ARG : CD_OK;   // (the item index of a row is 32 bits)
+}
+extern "C++" {                                  // (a template: the two kernels of a pass are a parameter)
+// enqueue(): memset of the counters aside, the descent and the exact stage of one pass on the stream
+template <class Enqueue> static int item_rows_pass(cd_ctx *c, ItemRowsBuf &b, const double *items, uint64_t item_doubles, uint64_t n, Enqueue enqueue)
+{
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemcpyAsync(b.items.d, items, sizeof(double) * item_doubles * n, hipMemcpyHostToDevice, s));
+    for (;;) {
+        HIPCHK(hipMemsetAsync(b.q.state.d, 0, sizeof(ProxState), s));
+        enqueue();
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(b.q.state.h, b.q.state.d, sizeof(ProxState), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        int rc = CD_OK;
+        if (!b.q.overflowed(rc)) return rc;
+    }
+}
+// after the pass: one of the rows' arrays into the caller's, if it was asked for
+template <typename T> static int row_values(T *host, const T *dev, uint64_t elems, uint64_t take)
+{
+    if (host && take) HIPCHK(hipMemcpy(host, dev, sizeof(T) * elems * take, hipMemcpyDeviceToHost));
+    return CD_OK;
+}
+}  // extern "C++"
+// workgroups a shard in the exact stage: the candidates grow with the items as well as with the tree
+static uint32_t item_rows_blocks(const cd_ctx *c, uint64_t n) { return shard_blocks((uint32_t)std::max<uint64_t>(c->nt, n)); }
+int cd_points_within(cd_ctx *c, const double *points, uint64_t n, uint32_t *rows, uint64_t cap_rows, uint64_t *n_rows, uint64_t *n_tested, const cd_point_rows *out)
+{
+    int rc = item_rows_args(c, points, n, rows, cap_rows, n_rows);
+    if (rc) return rc;
+    if (!points_ok(points, n)) return CD_ERR_ARG;                           // before anything is launched: nothing is written for a bad point
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { *n_rows = 0; if (n_tested) *n_tested = 0; return CD_OK; }
+    ItemRowsBuf &b = c->within;
+    if ((rc = b.ensure(n, 4 * 8, cap_rows, WITHIN_ROW_BYTES))) return rc;
+    const cd_point_rows want = out ? *out : cd_point_rows{};
+    const uint64_t cap = b.vals.cap;
+    double *d_pts = reinterpret_cast<double *>(b.items.d), *d_q = reinterpret_cast<double *>(b.vals.d), *d_uv = d_q + 3 * cap;
+    uint32_t *d_ids = reinterpret_cast<uint32_t *>(d_uv + 2 * cap);
+    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + cap), *d_side = d_feat + cap;
+    rc = item_rows_pass(c, b, points, 4, n, [&] {
+        k_within_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, c->stream>>>(c->d_recs32, c->d_root, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, d_pts, n,
+                                                                                         b.q.state.d, b.q.d_cand, b.q.shard_cap);
+        k_within_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, c->stream>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, d_pts, b.q.state.d,
+                                                                                                   cap_rows, b.q.d_pairs, want.ids ? d_ids : nullptr, want.dist ? b.q.d_dists : nullptr,
+                                                                                                   want.closest ? d_q : nullptr, want.uv ? d_uv : nullptr,
+                                                                                                   want.feature ? d_feat : nullptr, want.side ? d_side : nullptr);
+    });
+    if (rc) return rc;
+    const uint64_t take = std::min<uint64_t>(b.q.state.h->n_pairs, cap_rows);
+    if ((rc = row_values(want.ids, d_ids, 1, take)) || (rc = row_values(want.closest, d_q, 3, take)) || (rc = row_values(want.uv, d_uv, 2, take)) ||
+        (rc = row_values(want.feature, d_feat, 1, take)) || (rc = row_values(want.side, d_side, 1, take))) return rc;
+    if (n_tested) *n_tested = b.q.state.h->n_tested;
+    return b.q.results(rows, nullptr, want.dist, cap_rows, n_rows);
+}
+int cd_cast_rays_all(cd_ctx *c, const double *rays, uint64_t n, uint32_t *rows, uint64_t cap_rows, uint64_t *n_rows, uint64_t *n_tested, const cd_ray_rows *out)
+{
+    int rc = item_rows_args(c, rays, n, rows, cap_rows, n_rows);
+    if (rc) return rc;
+    if (!rays_ok(rays, n)) return CD_ERR_ARG;                               // before anything is launched: nothing is written for a bad ray
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { *n_rows = 0; if (n_tested) *n_tested = 0; return CD_OK; }
+    ItemRowsBuf &b = c->rays_all;
+    if ((rc = b.ensure(n, 7 * 8, cap_rows, RAYS_ALL_ROW_BYTES))) return rc;
+    const cd_ray_rows want = out ? *out : cd_ray_rows{};
+    const uint64_t cap = b.vals.cap;
+    double *d_rays = reinterpret_cast<double *>(b.items.d), *d_uv = reinterpret_cast<double *>(b.vals.d);
+    uint32_t *d_ids = reinterpret_cast<uint32_t *>(d_uv + 2 * cap);
+    uint8_t *d_side = reinterpret_cast<uint8_t *>(d_ids + cap);
+    rc = item_rows_pass(c, b, rays, 7, n, [&] {
+        k_rays_all_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, c->stream>>>(c->d_recs32, c->d_root, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, d_rays, n,
+                                                                                           b.q.state.d, b.q.d_cand, b.q.shard_cap);
+        k_rays_all_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, c->stream>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, d_rays,
+                                                                                                     b.q.state.d, cap_rows, b.q.d_pairs, want.ids ? d_ids : nullptr,
+                                                                                                     want.t ? b.q.d_dists : nullptr, want.uv ? d_uv : nullptr, want.side ? d_side : nullptr);
+    });
+    if (rc) return rc;
+    const uint64_t take = std::min<uint64_t>(b.q.state.h->n_pairs, cap_rows);
+    if ((rc = row_values(want.ids, d_ids, 1, take)) || (rc = row_values(want.uv, d_uv, 2, take)) || (rc = row_values(want.side, d_side, 1, take))) return rc;
+    if (n_tested) *n_tested = b.q.state.h->n_tested;
+    return b.q.results(rows, nullptr, want.t, cap_rows, n_rows);
 }
 // ---- nearest triangle and separation distance between two meshes (cd_nearest.h) ---------------------------------------------------
 // Everything runs on a's stream, in buffers a owns (rows, leaf pairs, witness, counters): nothing any other call keeps is touched.  Both

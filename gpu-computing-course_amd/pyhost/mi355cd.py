@@ -72,6 +72,51 @@ CD_POINT_ANY = 1
 POINT_NONE = 0xFFFFFFFF
 
 
+class CdPointRows(C.Structure):
+    _fields_ = [("ids", C.c_void_p), ("dist", C.c_void_p), ("closest", C.c_void_p), ("uv", C.c_void_p), ("feature", C.c_void_p), ("side", C.c_void_p)]
+
+
+class CdRayRows(C.Structure):
+    _fields_ = [("ids", C.c_void_p), ("t", C.c_void_p), ("uv", C.c_void_p), ("side", C.c_void_p)]
+
+
+WITHIN_SHARD_FIRST = 1 << 14        # cd_within.h: candidates a shard in the first allocation of the all-results item queries
+WITHIN_SHARDS = 64                  # cd_traverse.h NSHARD
+
+
+class _PointRowArrays:
+    """The arrays of a points_within call with room for cap rows, and the cd_point_rows that points at them."""
+
+    def __init__(self, cap):
+        n = max(cap, 1)
+        self.ids = np.empty(n, dtype=np.uint32)
+        self.dist = np.empty(n, dtype=np.float64)
+        self.closest = np.empty((n, 3), dtype=np.float64)
+        self.uv = np.empty((n, 2), dtype=np.float64)
+        self.feature = np.empty(n, dtype=np.uint8)
+        self.side = np.empty(n, dtype=np.uint8)
+        self.out = CdPointRows(self.ids.ctypes.data, self.dist.ctypes.data, self.closest.ctypes.data, self.uv.ctypes.data, self.feature.ctypes.data,
+                               self.side.ctypes.data)
+
+    def take(self, got):
+        return tuple(a[:got].copy() for a in (self.ids, self.dist, self.closest, self.uv, self.feature, self.side))
+
+
+class _RayRowArrays:
+    """The arrays of a cast_rays_all call with room for cap rows, and the cd_ray_rows that points at them."""
+
+    def __init__(self, cap):
+        n = max(cap, 1)
+        self.ids = np.empty(n, dtype=np.uint32)
+        self.t = np.empty(n, dtype=np.float64)
+        self.uv = np.empty((n, 2), dtype=np.float64)
+        self.side = np.empty(n, dtype=np.uint8)
+        self.out = CdRayRows(self.ids.ctypes.data, self.t.ctypes.data, self.uv.ctypes.data, self.side.ctypes.data)
+
+    def take(self, got):
+        return tuple(a[:got].copy() for a in (self.ids, self.t, self.uv, self.side))
+
+
 class CdNearestInfo(C.Structure):
     _fields_ = [("n_found", C.c_uint64), ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64)]
 
@@ -183,6 +228,7 @@ EXPORTS = [
     "cd_find_proximity_witness", "cd_find_proximity_between_witness", "cd_find_ccd_witness", "cd_find_ccd_between_witness", "cd_tri_witness_points",
     "cd_find_collisions_contour", "cd_find_collisions_between_contour", "cd_tri_isect_points",
     "cd_nearest_between",
+    "cd_points_within", "cd_cast_rays_all",
 ]
 
 _lib = None
@@ -276,6 +322,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_find_collisions_between_contour.argtypes = lib.cd_find_collisions_between.argtypes + [cp]
     lib.cd_tri_isect_points.argtypes = [vp, C.c_uint64, vp, vp, vp]
     lib.cd_nearest_between.argtypes = [vp, vp, C.c_double, C.c_int, vp, vp, vp, wp, C.POINTER(CdNearestInfo)]
+    lib.cd_points_within.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(CdPointRows)]
+    lib.cd_cast_rays_all.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(CdRayRows)]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -584,6 +632,30 @@ class CollisionDetector:
                                         C.byref(info))
         self._chk("cd_closest_points", rc)
         return face, ids, dist, closest, uv, feature, side, info
+
+    # ---- all-results item queries against this mesh (cd_points_within, cd_cast_rays_all)
+    def points_within(self, points, rmax, cap: int = 1 << 20):
+        """cd_points_within on the tree that is there.  points: [n, 3]; rmax: a scalar or [n].  -> (rows[n, 2] (point index, face index),
+        ids[n], dist[n], closest[n, 3], uv[n, 2], feature[n], side[n], n, rc): one row for EVERY (point, triangle) with pt_tri's
+        dist <= rmax, with pt_tri's values; n may exceed cap (rc = CD_OVERFLOW, cap rows are returned).  The vertex-face pairs of a
+        repulsion pass are  b.points_within(a_verts, thickness).  The rows come in no order; grouped by point, nearest first:
+            o = np.lexsort((rows[:, 1], ids, dist, rows[:, 0]))
+        whose first row a point is closest_points' answer.  self.within_tested: pt_tri evaluations made.  Points are walked in the
+        order given: keep spatially coherent points next to each other; a point with rmax = +inf walks the whole tree in one lane."""
+        pts = pack_points(points, rmax)
+        self.within_tested, (rows, n, rc, vals) = self._pair_query("cd_points_within", (self._ctx, _ptr(pts), pts.shape[0]), cap, extra=_PointRowArrays(cap))
+        return (rows, *vals, n, rc)
+
+    def cast_rays_all(self, origins, dirs, tmax=np.inf, cap: int = 1 << 20):
+        """cd_cast_rays_all on the tree that is there.  origins, dirs, tmax: as cast_rays takes them.  -> (rows[n, 2] (ray index, face
+        index), ids[n], t[n], uv[n, 2], side[n], n, rc): one row for EVERY (ray, triangle) that ray_tri hits over [0, tmax], with
+        ray_tri's values; n may exceed cap (rc = CD_OVERFLOW, cap rows are returned).  The rows come in no order; grouped by ray, in
+        the order the ray meets them:
+            o = np.lexsort((rows[:, 1], ids, t, rows[:, 0]))
+        whose first row a ray is cast_rays' closest hit.  self.rays_all_tested: ray_tri evaluations made."""
+        rays = pack_rays(origins, dirs, tmax)
+        self.rays_all_tested, (rows, n, rc, vals) = self._pair_query("cd_cast_rays_all", (self._ctx, _ptr(rays), rays.shape[0]), cap, extra=_RayRowArrays(cap))
+        return (rows, *vals, n, rc)
 
     # ---- nearest triangle of another mesh, and the separation distance (cd_nearest_between)
     def nearest_between(self, other, rmax=np.inf, minimum: bool = False, witness: bool = False):

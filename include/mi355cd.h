@@ -709,6 +709,41 @@ int cd_closest_points(cd_ctx *ctx, const double *points, uint64_t n, int flags, 
 int cd_pt_tri_points(const double *points, const double *tri, uint64_t n, double *dist, double *closest, double *uv,
                      uint8_t *feature, uint8_t *side);
 
+/* ---- all-results point and ray queries: everything within a radius, every hit (not reference behaviour) ----
+ * The complete sets behind cd_closest_points and cd_cast_rays: every triangle within a point's radius (vertex-face proximity for a
+ * repulsion pass, radius selection) and every triangle a ray or segment crosses (entry and exit, crossing counts, ordered hits).
+ * points is n x 4 doubles, exactly as cd_closest_points takes them (x, y, z, rmax with 0 <= rmax <= +inf); rays is n x 7 doubles,
+ * exactly as cd_cast_rays takes them (origin, direction, tmax).
+ *
+ * cd_points_within: one row for every (point k, face f) of this context with pt_tri(p_k; f).dist <= rmax_k (closed).
+ * cd_cast_rays_all: one row for every (ray k, face f) that ray_tri hits over [0, tmax_k].
+ * Each (k, f) appears exactly once.  Row r: rows[2 r] = k, rows[2 r + 1] = f, the index in cd_create's face list.  The order of the
+ * rows is free, as it is for cd_find_collisions; callers that want them grouped sort them.  out (may be NULL, and so may each of its
+ * members), per row: ids[r] the face's ID; dist[r], closest[3 r ..], uv[2 r], uv[2 r + 1], feature[r], side[r]: pt_tri's values for
+ * (k, f); t[r], uv[2 r], uv[2 r + 1], side[r]: ray_tri's.
+ * *n_rows is the size of the set.  When it exceeds cap_rows the call returns CD_OVERFLOW with the true *n_rows; nothing is written at
+ * or past cap_rows in any array, and the rows that are written are distinct rows of the true set.  rows may be NULL with cap_rows 0:
+ * the count-only call.  n_tested (may be NULL): exact evaluations made -- a number of this tree, not of the mesh.
+ * Guarantee: the set of rows and every value in a row depend on the mesh and the items only -- not on the Morton frame,
+ * CD_OPT_TRAVERSAL, CD_OPT_CELL_TABLE, the build variant or the order of the items.  Consistency with the single-answer calls is by
+ * definition: for item k the row with the smallest (dist, ID, face) -- for rays (t, ID, face) -- is bit for bit what cd_closest_points /
+ * cd_cast_rays with flags = 0 returns for k, and the items with no row are exactly those calls' 0xFFFFFFFF items.
+ * Items are walked in the order given, one lane each, neighbours in one wave: coherent items should be neighbours.  An item whose bound
+ * meets every box (rmax = +inf) walks the whole tree in one lane: correct, bounded, and slow.
+ * Needs a tree built from the current vertices (CD_ERR_ORDER otherwise, including after cd_update_vertices without a rebuild).
+ * CD_ERR_ARG: a NULL context; NULL n_rows; n > 0xFFFFFFFF (the item index of a row is 32 bits; checked before the items are read); NULL
+ * items with n > 0; NULL rows with cap_rows > 0; and what the single-answer call rejects in the items: a non-finite coordinate, an rmax
+ * or tmax that is NaN or negative, an all-zero direction -- checked on the host before anything is launched, and nothing is written
+ * then.  n = 0 returns CD_OK with *n_rows = 0.  The calls leave cd_stats, the last pair list, the order hint, a captured CD_OPT_GRAPH
+ * step and every other query's buffers as they were; they keep device buffers of their own (grown on demand, the candidate buffer
+ * by running the pass again; cd_destroy frees them) and run on the context's stream. */
+typedef struct cd_point_rows { uint32_t *ids; double *dist; double *closest; double *uv; uint8_t *feature; uint8_t *side; } cd_point_rows;
+int cd_points_within(cd_ctx *ctx, const double *points, uint64_t n, uint32_t *rows, uint64_t cap_rows,
+                     uint64_t *n_rows, uint64_t *n_tested, const cd_point_rows *out);
+typedef struct cd_ray_rows { uint32_t *ids; double *t; double *uv; uint8_t *side; } cd_ray_rows;
+int cd_cast_rays_all(cd_ctx *ctx, const double *rays, uint64_t n, uint32_t *rows, uint64_t cap_rows,
+                     uint64_t *n_rows, uint64_t *n_tested, const cd_ray_rows *out);
+
 /* ---- nearest triangle and separation distance between two meshes (not reference behaviour) ----
  * The threshold-free between-mesh question: how far is mesh a from mesh b, and where are they closest?  The per-pair functions are
  * tri_distance (the proximity section) and tri_witness (the witness section), a's triangle as the first argument, as in every
