@@ -544,6 +544,7 @@ int cd_multi_step(cd_multi *m, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_
     // tree, nothing of the local traversal -- the two descents share the chip and the latency-bound ends of the two passes
     // (exact tests, reports) overlap.  ONE wait for both.
     uint64_t n_local = 0, n_cross = 0, tested = 0;
+    uint32_t overflows = 0;                                                   // deferred items of the step: both passes', like n_pairs and pairs_tested
     int rc_l = CD_OK, rc_x = CD_OK;
     bool need_general_l = !fast_path, need_general_x = !fast_path;
     for (int redo = 0;; ++redo) {
@@ -608,7 +609,7 @@ int cd_multi_step(cd_multi *m, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_
         uint64_t nl = 0;
         rc_l = run_traversal(c, t0, nullptr, 0, pairs, cap, &nl);
         if (rc_l < 0) return late(rc_l);
-        n_local = nl; tested += c->stats.pairs_tested; syncs += 1;
+        n_local = nl; tested += c->stats.pairs_tested; overflows += c->stats.stack_overflows; syncs += 1;
     }
     if (need_general_x && recvd) {
         LATE_HIP(hipStreamWaitEvent(s, m->ev_payload, 0));
@@ -616,10 +617,14 @@ int cd_multi_step(cd_multi *m, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_
         uint64_t nx = 0;
         rc_x = run_traversal(c, t1, m->d_recv, recvd, pairs ? pairs + 2 * used : nullptr, cap - used, &nx);
         if (rc_x < 0) return late(rc_x);
-        n_cross = nx; tested += c->stats.pairs_tested; syncs += 1;
+        n_cross = nx; tested += c->stats.pairs_tested; overflows += c->stats.stack_overflows; syncs += 1;
     }
+    // A rank of ONE triangle has no tree to walk: its local pass tests nothing (as the reference on a one-triangle mesh).  In the single tree of all
+    // ranks' triangles that leaf meets itself like every other (collision.cuh:31-32 on its own box, strictly): counted here, so that the ranks' sum stays
+    // the single tree's.  (A world of one rank IS the one-triangle mesh: nothing to add.)
+    if (c->nt == 1 && W > 1) { const double *b = m->h_roots + 6 * (size_t)me; if (b[0] != b[1] && b[2] != b[3] && b[4] != b[5]) tested += 1; }
     // (the payload exchange has drained: the second stream was waited for above)
-    c->stats.n_pairs = n_local + n_cross; c->stats.pairs_tested = tested;
+    c->stats.n_pairs = n_local + n_cross; c->stats.pairs_tested = tested; c->stats.stack_overflows = overflows;   // (not the last pass's alone, nor an earlier step's)
     c->last_pairs_on_device = 0;                                              // two lists: cd_sorted_pairs does not apply to a multi step
     if (n_pairs) *n_pairs = n_local + n_cross;
     if (info) {

@@ -203,6 +203,8 @@ __global__ __launch_bounds__(TRAV_THREADS) void k_traverse(QuerySrc src, uint32_
         int32_t *gstack = DEEP ? deep_stacks + (size_t)gi * DEEP_STACK : nullptr;
         int sptr = 0;
         int32_t node = DEEP ? (int32_t)src.list[gi].y : ((n > 1) ? 0 : -1); // root = internal[0]
+        // a one-triangle tree has no internal node: a query from ANOTHER mesh meets its only leaf here (the multi-GPU step's rank of one triangle)
+        if (EXTERNAL && !DEEP && n == 1 && box_overlap(qbox, load_box(boxes, 0))) { ++tested; leaf_hit(q_id, qa, qb, qc, P1, P2, P3, leaf[0], verts, pairs, cap, st, vbase); }
         while (node != -1) {
             ++visits;
             const NodeMeta m = meta[node];
@@ -360,6 +362,19 @@ __global__ __launch_bounds__(DESC_THREADS) void k_descend(QuerySrc src, uint32_t
     uint32_t qcertain = 0;                              // CAND_CERTAIN if the query box is exact in fp32
     int32_t *gstack = DEEP ? deep_stacks + ((size_t)wave_id * 64 + lane) * DEEP_STACK : nullptr;
     const int stack_cap = DEEP ? DEEP_STACK : WQ_STACK;
+
+    // A one-triangle tree has no records to walk: leaf 0 is the whole tree.  Queries from ANOTHER mesh (the multi-GPU step's rank of one
+    // triangle) all become candidates against it, undecided: k_exact tests the FP64 boxes, counts the hit and applies the filters.
+    if (EXTERNAL && !DEEP && n == 1) {
+        for (uint32_t q0 = chunk_begin; q0 < chunk_end; q0 += 64u) {      // (wave-uniform bounds)
+            const bool cnd = q0 + lane < chunk_end;
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(cnd);
+            if (cnd) queue[w][qcount + __popcll(m & lt_mask)] = Candidates{q0 + lane, 0u};
+            qcount += __popcll(m);
+            flush(qcount);
+        }
+        return;
+    }
 
     // shared root path (below): only for a wave whose queries are 64 consecutive leaves of the tree itself
     constexpr bool SHARED_PATH = !EXTERNAL && !DEEP && !REFILL;

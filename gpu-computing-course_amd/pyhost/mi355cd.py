@@ -1046,15 +1046,25 @@ class MultiStep:
             raise CdError(name, rc)
         self._pairs = None
 
-    def step(self, cap: int = 1 << 22):
-        if self._pairs is None or self._pairs.shape[0] < cap:
-            self._pairs = np.empty((cap, 2), dtype=np.uint32)
+    def step(self, cap: int = 1 << 22, pairs: np.ndarray | None = None):
+        """pairs: the caller's own C-contiguous uint32 array of at least cap rows of 2, written in place (rows behind cap are the
+        caller's: a test keeps a canary there); None: a buffer the object keeps -- and with cap 0 a NULL pointer (count only)."""
+        if pairs is not None:
+            if pairs.dtype != np.uint32 or pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] < cap or not pairs.flags.c_contiguous or not pairs.flags.writeable:
+                raise ValueError("pairs must be a writable C-contiguous uint32 array of shape [>= cap, 2]")
+            buf, ptr = pairs, C.c_void_p(pairs.ctypes.data)
+        elif cap == 0:
+            buf, ptr = np.empty((0, 2), dtype=np.uint32), C.c_void_p(None)
+        else:
+            if self._pairs is None or self._pairs.shape[0] < cap:
+                self._pairs = np.empty((cap, 2), dtype=np.uint32)
+            buf, ptr = self._pairs, C.c_void_p(self._pairs.ctypes.data)
         n = C.c_uint64(0)
         info = CdMultiInfo()
-        rc = self.lib.cd_multi_step(self._m, self._pairs.ctypes.data, cap, C.byref(n), C.byref(info))
+        rc = self.lib.cd_multi_step(self._m, ptr, cap, C.byref(n), C.byref(info))
         if rc < 0:
             raise CdError("cd_multi_step", rc)
-        return self._pairs[: min(n.value, cap)], int(n.value), rc, info
+        return buf[: min(n.value, cap)], int(n.value), rc, info
 
     def set_flags(self, flags: int):
         rc = self.lib.cd_multi_set_flags(self._m, flags)

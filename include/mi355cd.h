@@ -367,6 +367,11 @@ typedef struct cd_multi_info {
     uint32_t attempts;             /* 1 + collective repeats (slabs grown)                                    */
     uint32_t failed_rank_plus1;    /* a step that returned CD_ERR_PEER / a local error: 1 + the lowest rank that published a failure, else 0 */
     uint64_t sent_queries, recv_queries, local_pairs, cross_pairs, pairs_tested, query_cap;
+                                   /* pairs_tested (here and in cd_stats after the step): both passes', and summed over the ranks what ONE tree of  */
+                                   /* all their triangles tests.  For that sum a rank of a single triangle -- no tree, its local pass tests nothing -- */
+                                   /* adds the one hit of that leaf on itself (when its box has an interior) that the single tree's walk counts.     */
+                                   /* cd_stats.stack_overflows after the step: the deferred items of both passes of THIS step (0 when neither       */
+                                   /* pass deferred), not the last traversal's alone.                                                                */
     float ms_tree, ms_allgather, ms_pack, ms_counts, ms_exchange, ms_local, ms_cross;   /* CD_MULTI_TIMING; -1 = not measured.  NOT additive: */
                                    /* first stream: tree (Morton keys .. fused build), local (own traversal); second stream, beside them: allgather  */
                                    /* (from the step's start: box of the triangles + its all-gather), pack, counts (all-gather + copy to the host),  */
