@@ -16,6 +16,7 @@
 #include "cd_points.h"
 #include "cd_nearest.h"
 #include "cd_within.h"
+#include "cd_sweep.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -264,6 +265,19 @@ struct ItemRowsBuf {
     }
 };
 
+// What the swept-point queries (cd_sweep_points_all, cd_sweep_points, cd_sweep.h) own: an all-results item query's record for the rows,
+// the CCD counters their swept refit and exact stage write (M; evaluations, unresolved rows), swept records of their own (swept[0] and
+// swept[1] stay the last CCD pass's), x1, the items' skip_vertex, and the first-contact call's counters and block
+struct SweepBuf {
+    ItemRowsBuf rows;
+    StateWords<CcdState> cst;
+    SweptBuf swept;
+    DevArray<double> x1;
+    DevArray<uint32_t> skip;
+    ItemBuf<PointState> first;
+    void release() { rows.release(); cst.release(); swept.release(); x1.release(); skip.release(); first.release(); }
+};
+
 struct cd_multi;
 struct cd_ctx {
     uint32_t nv = 0, nt = 0;
@@ -399,6 +413,10 @@ struct cd_ctx {
     // within.items: points [4 n];   within.vals: closest [3 cap] | uv [2 cap] (doubles) | ids [cap] (u32) | feature [cap] | side [cap] (u8)
     // rays_all.items: rays [7 n];   rays_all.vals: uv [2 cap] (doubles) | ids [cap] (u32) | side [cap] (u8)
     ItemRowsBuf within, rays_all;
+    // swept-point queries (cd_sweep_points_all, cd_sweep_points, cd_sweep.h): buffers of their own, allocated on first use.
+    // sweep.rows.items: items [7 n];   sweep.rows.vals: toi [cap] | closest [3 cap] | uv [2 cap] (doubles) | ids [cap] (u32) | feature [cap] | side [cap] (u8)
+    // sweep.first.block: items [7 n] | toi [n] | dist [n] | closest [3 n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | feature [n] | side [n] (u8)
+    SweepBuf sweep;
 };
 
 namespace {
@@ -427,7 +445,7 @@ void free_all(cd_ctx *c)
     hipFree(c->pp_flags); hipFree(c->pp_os);
     c->prox.release(); c->cont.release(); c->ccd.release(); c->bw.release(); c->ccd_x1.release(); c->bw_x1a.release(); c->bw_x1b.release();
     for (SweptBuf &sw : c->swept) sw.release();
-    c->rays.release(); c->points.release(); c->nearest.release(); c->within.release(); c->rays_all.release();
+    c->rays.release(); c->points.release(); c->nearest.release(); c->within.release(); c->rays_all.release(); c->sweep.release();
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -2767,6 +2785,150 @@ int cd_cast_rays_all(cd_ctx *c, const double *rays, uint64_t n, uint32_t *rows, 
     if ((rc = row_values(want.ids, d_ids, 1, take)) || (rc = row_values(want.uv, d_uv, 2, take)) || (rc = row_values(want.side, d_side, 1, take))) return rc;
     if (n_tested) *n_tested = b.q.state.h->n_tested;
     return b.q.results(rows, nullptr, want.t, cap_rows, n_rows);
+}
+// ---- swept-point queries (cd_sweep.h) -------------------------------------------------------------------------------------------------
+// Own buffers (items, skip_vertex, x1, swept records and their counters, candidates, rows): nothing any other call keeps is touched --
+// swept[0] / swept[1] and what cd_debug_swept reports of them included.  The all-rows call is the all-results item queries' pass with
+// the swept refit in front of the descent; the first-contact call is one kernel behind the refit.
+constexpr uint64_t SWEEP_ROW_BYTES = 8 + 24 + 16 + 4 + 1 + 1;               // device bytes a row besides (item, face) and dist: toi, closest, uv, ID, feature, side
+constexpr uint64_t SWEEP_FIRST_BYTES = 7 * 8 + 8 + 8 + 24 + 16 + 4 + 4 + 1 + 1;   // device bytes an item: the item, toi, dist, closest, uv, face, ID, feature, side
+// every item has six finite coordinates and a dist that is finite and > 0 (ccd_dist_ok: a NaN fails)
+static bool sweeps_ok(const double *items, uint64_t n)
+{
+    for (uint64_t i = 0; i < n; ++i) {
+        const double *r = items + 7 * i;
+        for (int k = 0; k < 6; ++k) if (!std::isfinite(r[k])) return false;
+        if (!ccd_dist_ok(r[6])) return false;
+    }
+    return true;
+}
+// x1 (NULL: the context's own vertices, the mesh does not move) and skip_vertex (NULL: none) on the device, uploads on the stream
+static int sweep_inputs(cd_ctx *c, const double *verts_end, const uint32_t *skip_vertex, uint64_t n, const double *&x1, const uint32_t *&skip)
+{
+    SweepBuf &b = c->sweep;
+    int rc = b.cst.ensure();
+    if (!rc && c->nt >= 2) rc = b.swept.ensure(c->nt);
+    if (!rc && verts_end) rc = b.x1.ensure(c->nv, 3);
+    if (!rc && skip_vertex) rc = b.skip.ensure(n, 1);
+    if (rc) return rc;
+    x1 = c->d_verts; skip = nullptr;
+    if (verts_end) { HIPCHK(hipMemcpyAsync(b.x1.d, verts_end, sizeof(double) * 3 * (size_t)c->nv, hipMemcpyHostToDevice, c->stream)); x1 = b.x1.d; }
+    if (skip_vertex) { HIPCHK(hipMemcpyAsync(b.skip.d, skip_vertex, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream)); skip = b.skip.d; }
+    return CD_OK;
+}
+// the counters zeroed and, for a tree with records, the swept refit into this query's own records (M lands in the counters)
+static int sweep_refit(cd_ctx *c, const double *x1)
+{
+    SweepBuf &b = c->sweep;
+    HIPCHK(hipMemsetAsync(b.cst.d, 0, sizeof(CcdState), c->stream));
+    return c->nt >= 2 ? enqueue_swept_refit(c->stream, c, x1, b.swept, b.cst.d) : CD_OK;
+}
+int cd_sweep_points_all(cd_ctx *c, const double *verts_end, const double *items, uint64_t n, const uint32_t *skip_vertex, uint32_t *rows, uint64_t cap_rows,
+                        uint64_t *n_rows, const cd_sweep_rows *out, cd_ccd_info *info)
+{
+    int rc = item_rows_args(c, items, n, rows, cap_rows, n_rows);
+    if (rc) return rc;
+    if (!sweeps_ok(items, n)) return CD_ERR_ARG;                            // before anything is launched: nothing is written for a bad item
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { *n_rows = 0; if (info) *info = cd_ccd_info{0, 0, 0, 0}; return CD_OK; }
+    SweepBuf &sb = c->sweep;
+    ItemRowsBuf &b = sb.rows;
+    if ((rc = b.ensure(n, 7 * 8, cap_rows, SWEEP_ROW_BYTES))) return rc;
+    const double *x1 = nullptr; const uint32_t *d_skip = nullptr;
+    if ((rc = sweep_inputs(c, verts_end, skip_vertex, n, x1, d_skip))) return rc;
+    const cd_sweep_rows want = out ? *out : cd_sweep_rows{};
+    const uint64_t cap = b.vals.cap;
+    double *d_items = reinterpret_cast<double *>(b.items.d), *d_toi = reinterpret_cast<double *>(b.vals.d), *d_q = d_toi + cap, *d_uv = d_q + 3 * cap;
+    uint32_t *d_ids = reinterpret_cast<uint32_t *>(d_uv + 2 * cap);
+    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + cap), *d_side = d_feat + cap;
+    int erc = CD_OK;                                                        // the first error of a pass's own enqueues
+    rc = item_rows_pass(c, b, items, 7, n, [&] {
+        hipStream_t s = c->stream;
+        if ((erc = sweep_refit(c, x1))) return;
+        k_sweep_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(sb.swept.d_recs, c->d_root, (int)c->nt, c->d_os_ticket + 8, d_items, n, sb.cst.d,
+                                                                                 b.q.state.d, b.q.d_cand, b.q.shard_cap);
+        k_sweep_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, x1, d_items, d_skip,
+                                                                                          b.q.state.d, sb.cst.d, cap_rows, b.q.d_pairs, want.ids ? d_ids : nullptr,
+                                                                                          want.toi ? d_toi : nullptr, want.dist ? b.q.d_dists : nullptr,
+                                                                                          want.closest ? d_q : nullptr, want.uv ? d_uv : nullptr,
+                                                                                          want.feature ? d_feat : nullptr, want.side ? d_side : nullptr);
+        const hipError_t e = hipMemcpyAsync(sb.cst.h, sb.cst.d, sizeof(CcdState), hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) erc = -(int)e;
+    });
+    if (rc || (rc = erc)) return rc;
+    const uint64_t take = std::min<uint64_t>(b.q.state.h->n_pairs, cap_rows);
+    if ((rc = row_values(want.ids, d_ids, 1, take)) || (rc = row_values(want.toi, d_toi, 1, take)) || (rc = row_values(want.closest, d_q, 3, take)) ||
+        (rc = row_values(want.uv, d_uv, 2, take)) || (rc = row_values(want.feature, d_feat, 1, take)) || (rc = row_values(want.side, d_side, 1, take))) return rc;
+    if (info) {
+        uint64_t cand = 0;
+        for (int i = 0; i < NSHARD; ++i) cand += b.q.state.h->shard[i * PROX_SHARD_STRIDE];
+        *info = cd_ccd_info{cand, b.q.state.h->n_tested, sb.cst.h->n_evals, sb.cst.h->n_unresolved};
+    }
+    return b.q.results(rows, nullptr, want.dist, cap_rows, n_rows);
+}
+int cd_sweep_points(cd_ctx *c, const double *verts_end, const double *items, uint64_t n, const uint32_t *skip_vertex, int flags, uint32_t *face, uint32_t *ids,
+                    double *toi, double *dist, double *closest, double *uv, uint8_t *feature, uint8_t *side, cd_point_info *info)
+{
+    if (!c || flags != 0 || (n && (!items || !face)) || n > 0xffffffffull) return CD_ERR_ARG;
+    if (!sweeps_ok(items, n)) return CD_ERR_ARG;                            // before anything is launched: nothing is written for a bad item
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { if (info) *info = cd_point_info{0, 0, 0}; return CD_OK; }
+    SweepBuf &sb = c->sweep;
+    int rc = sb.first.ensure(n, SWEEP_FIRST_BYTES);
+    if (rc) return rc;
+    const double *x1 = nullptr; const uint32_t *d_skip = nullptr;
+    if ((rc = sweep_inputs(c, verts_end, skip_vertex, n, x1, d_skip))) return rc;
+    hipStream_t s = c->stream;
+    const uint64_t cap = sb.first.block.cap;
+    double *d_items = reinterpret_cast<double *>(sb.first.block.d), *d_toi = d_items + 7 * cap, *d_dist = d_toi + cap, *d_q = d_dist + cap, *d_uv = d_q + 3 * cap;
+    uint32_t *d_face = reinterpret_cast<uint32_t *>(d_uv + 2 * cap), *d_ids = d_face + cap;
+    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + cap), *d_side = d_feat + cap;
+    HIPCHK(hipMemcpyAsync(d_items, items, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(sb.first.state.d, 0, sizeof(PointState), s));
+    if ((rc = sweep_refit(c, x1))) return rc;
+    k_sweep_first<<<cdiv(n, SWEEP_THREADS), SWEEP_THREADS, 0, s>>>(sb.swept.d_recs, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, x1, (int)c->nt, c->d_os_ticket + 8,
+                                                                   d_items, d_skip, n, sb.cst.d, sb.first.state.d, d_face, ids ? d_ids : nullptr, toi ? d_toi : nullptr,
+                                                                   dist ? d_dist : nullptr, closest ? d_q : nullptr, uv ? d_uv : nullptr,
+                                                                   feature ? d_feat : nullptr, side ? d_side : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sb.first.state.h, sb.first.state.d, sizeof(PointState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(face, d_face, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    if (toi) HIPCHK(hipMemcpyAsync(toi, d_toi, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    if (closest) HIPCHK(hipMemcpyAsync(closest, d_q, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+    if (uv) HIPCHK(hipMemcpyAsync(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, s));
+    if (feature) HIPCHK(hipMemcpyAsync(feature, d_feat, n, hipMemcpyDeviceToHost, s));
+    if (side) HIPCHK(hipMemcpyAsync(side, d_side, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (info) { info->n_found = sb.first.state.h->n_found; info->node_visits = sb.first.state.h->node_visits; info->tri_tests = sb.first.state.h->tri_tests; }
+    return CD_OK;
+}
+int cd_pt_advance_points(const double *items, const double *tri, uint64_t n, double *toi, double *dist, double *closest, double *uv, uint8_t *feature, uint8_t *side,
+                         uint32_t *evals)
+{
+    if (!items || !tri || !toi) return CD_ERR_ARG;
+    if (!sweeps_ok(items, n)) return CD_ERR_ARG;
+    if (n == 0) return CD_OK;
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_i = dev.in(items, 7 * n), *d_t = dev.in(tri, 18 * n);
+    double *d_toi = dev.out<double>(n), *d_d = dev.out<double>(n), *d_q = dev.out<double>(3 * n);
+    double *d_uv = dev.out<double>(2 * n);
+    uint8_t *d_fs = dev.out<uint8_t>(2 * n);
+    uint32_t *d_e = dev.out<uint32_t>(n);
+    if (dev.e == hipSuccess) {
+        k_pt_advance_points<<<strided_grid(n, CCD_THREADS), CCD_THREADS>>>(d_i, d_t, n, d_toi, d_d, d_q, d_uv, d_fs, d_fs + n, d_e);
+        dev.e = hipGetLastError();
+    }
+    dev.back(toi, d_toi, n);
+    dev.back(dist, d_d, n);
+    dev.back(closest, d_q, 3 * n);
+    dev.back(uv, d_uv, 2 * n);
+    dev.back(feature, d_fs, n);
+    dev.back(side, d_fs + n, n);
+    dev.back(evals, d_e, n);
+    return dev.rc();
 }
 // ---- nearest triangle and separation distance between two meshes (cd_nearest.h) ---------------------------------------------------
 // Everything runs on a's stream, in buffers a owns (rows, leaf pairs, witness, counters): nothing any other call keeps is touched.  Both

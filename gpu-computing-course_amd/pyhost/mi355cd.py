@@ -117,6 +117,33 @@ class _RayRowArrays:
         return tuple(a[:got].copy() for a in (self.ids, self.t, self.uv, self.side))
 
 
+class CdSweepRows(C.Structure):
+    _fields_ = [("ids", C.c_void_p), ("toi", C.c_void_p), ("dist", C.c_void_p), ("closest", C.c_void_p), ("uv", C.c_void_p), ("feature", C.c_void_p),
+                ("side", C.c_void_p)]
+
+
+SWEEP_NONE = 0xFFFFFFFF
+
+
+class _SweepRowArrays:
+    """The arrays of a sweep_points_all call with room for cap rows, and the cd_sweep_rows that points at them."""
+
+    def __init__(self, cap):
+        n = max(cap, 1)
+        self.ids = np.empty(n, dtype=np.uint32)
+        self.toi = np.empty(n, dtype=np.float64)
+        self.dist = np.empty(n, dtype=np.float64)
+        self.closest = np.empty((n, 3), dtype=np.float64)
+        self.uv = np.empty((n, 2), dtype=np.float64)
+        self.feature = np.empty(n, dtype=np.uint8)
+        self.side = np.empty(n, dtype=np.uint8)
+        self.out = CdSweepRows(self.ids.ctypes.data, self.toi.ctypes.data, self.dist.ctypes.data, self.closest.ctypes.data, self.uv.ctypes.data,
+                               self.feature.ctypes.data, self.side.ctypes.data)
+
+    def take(self, got):
+        return tuple(a[:got].copy() for a in (self.ids, self.toi, self.dist, self.closest, self.uv, self.feature, self.side))
+
+
 class CdNearestInfo(C.Structure):
     _fields_ = [("n_found", C.c_uint64), ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64)]
 
@@ -229,6 +256,7 @@ EXPORTS = [
     "cd_find_collisions_contour", "cd_find_collisions_between_contour", "cd_tri_isect_points",
     "cd_nearest_between",
     "cd_points_within", "cd_cast_rays_all",
+    "cd_sweep_points_all", "cd_sweep_points", "cd_pt_advance_points",
 ]
 
 _lib = None
@@ -324,6 +352,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_nearest_between.argtypes = [vp, vp, C.c_double, C.c_int, vp, vp, vp, wp, C.POINTER(CdNearestInfo)]
     lib.cd_points_within.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(CdPointRows)]
     lib.cd_cast_rays_all.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(CdRayRows)]
+    lib.cd_sweep_points_all.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p, C.POINTER(CdSweepRows), C.POINTER(CdCcdInfo)]
+    lib.cd_sweep_points.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CdPointInfo)]
+    lib.cd_pt_advance_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -656,6 +687,57 @@ class CollisionDetector:
         rays = pack_rays(origins, dirs, tmax)
         self.rays_all_tested, (rows, n, rc, vals) = self._pair_query("cd_cast_rays_all", (self._ctx, _ptr(rays), rays.shape[0]), cap, extra=_RayRowArrays(cap))
         return (rows, *vals, n, rc)
+
+    # ---- swept-point queries against this mesh as it moves (cd_sweep_points_all, cd_sweep_points)
+    def _sweep_pre(self, p0, p1, dist, verts_end, skip_vertex):
+        items = pack_sweeps(p0, p1, dist)
+        n = items.shape[0]
+        x1 = _verts_end(verts_end, self.nv, "verts_end", optional=True)
+        skip = None
+        if skip_vertex is not None:
+            skip = np.ascontiguousarray(skip_vertex, dtype=np.uint32).reshape(-1)
+            if skip.shape[0] != n:
+                raise ValueError(f"skip_vertex must be [{n}], got {skip.shape}")
+        return items, n, x1, skip
+
+    def sweep_points_all(self, p0, p1, dist, verts_end=None, skip_vertex=None, cap: int = 1 << 20):
+        """cd_sweep_points_all on the tree that is there.  p0, p1: [n, 3], the points at the start and the end of the step; dist: a scalar
+        or [n], finite and > 0; verts_end: [nv, 3], the mesh at the end of the step (None: it does not move); skip_vertex: [n] vertex
+        indices (SWEEP_NONE = 0xFFFFFFFF: none) whose triangles are not tested for that item.  -> (rows[n, 2] (item index, face index),
+        ids[n], toi[n], dist[n], closest[n, 3], uv[n, 2], feature[n], side[n], n, rc): one row for EVERY (item, triangle) the
+        advancement reports, with toi and pt_tri's values of the reporting evaluation; n may exceed cap (rc = CD_OVERFLOW, cap rows are
+        returned).  A row with dist > the item's dist is unresolved.  self.sweep_info (CdCcdInfo): candidates, pairs through the gate,
+        pt_tri evaluations, unresolved rows.  The vertex-face half of a cloth's own CCD pass is
+            cd.sweep_points_all(x0, x1, thickness, verts_end=x1, skip_vertex=np.arange(nv))."""
+        items, n, x1, skip = self._sweep_pre(p0, p1, dist, verts_end, skip_vertex)
+        rows = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        arrays = _SweepRowArrays(cap)
+        nrows, info = C.c_uint64(0), CdCcdInfo()
+        rc = self.lib.cd_sweep_points_all(self._ctx, _ptr(x1), _ptr(items), n, _ptr(skip), _ptr(rows) if cap else None, cap, C.byref(nrows), C.byref(arrays.out),
+                                          C.byref(info))
+        self._chk("cd_sweep_points_all", rc, allow=(CD_OK, CD_OVERFLOW))
+        self.sweep_info = info
+        got = min(nrows.value, cap)
+        return (rows[:got].copy(), *arrays.take(got), nrows.value, rc)
+
+    def sweep_points(self, p0, p1, dist, verts_end=None, skip_vertex=None):
+        """cd_sweep_points on the tree that is there; arguments as sweep_points_all takes them.  -> (face[n] (SWEEP_NONE = 0xFFFFFFFF: the
+        point comes within dist of no triangle), ids[n], toi[n] (+inf then), dist[n], closest[n, 3], uv[n, 2], feature[n], side[n], info):
+        per item the row of sweep_points_all with the smallest (toi, ID, face index)."""
+        items, n, x1, skip = self._sweep_pre(p0, p1, dist, verts_end, skip_vertex)
+        face = np.empty(n, dtype=np.uint32)
+        ids = np.empty(n, dtype=np.uint32)
+        toi = np.empty(n, dtype=np.float64)
+        d = np.empty(n, dtype=np.float64)
+        closest = np.empty((n, 3), dtype=np.float64)
+        uv = np.empty((n, 2), dtype=np.float64)
+        feature = np.empty(n, dtype=np.uint8)
+        side = np.empty(n, dtype=np.uint8)
+        info = CdPointInfo()
+        rc = self.lib.cd_sweep_points(self._ctx, _ptr(x1), _ptr(items), n, _ptr(skip), 0, _ptr(face), _ptr(ids), _ptr(toi), _ptr(d), _ptr(closest), _ptr(uv),
+                                      _ptr(feature), _ptr(side), C.byref(info))
+        self._chk("cd_sweep_points", rc)
+        return face, ids, toi, d, closest, uv, feature, side, info
 
     # ---- nearest triangle of another mesh, and the separation distance (cd_nearest_between)
     def nearest_between(self, other, rmax=np.inf, minimum: bool = False, witness: bool = False):
@@ -997,6 +1079,41 @@ def pt_tri_points(points, tris):
     if rc != CD_OK:
         raise CdError("cd_pt_tri_points", rc)
     return dist, closest, uv, feature, side
+
+
+def pack_sweeps(p0, p1, dist) -> np.ndarray:
+    """[n, 7] doubles (p0, p1, dist), the layout cd_sweep_points_all, cd_sweep_points and cd_pt_advance_points take."""
+    a = np.asarray(p0, dtype=np.float64).reshape(-1, 3)
+    b = np.asarray(p1, dtype=np.float64).reshape(-1, 3)
+    if a.shape != b.shape:
+        raise ValueError(f"p0 {a.shape} and p1 {b.shape} differ")
+    items = np.empty((a.shape[0], 7), dtype=np.float64)
+    items[:, 0:3] = a
+    items[:, 3:6] = b
+    items[:, 6] = dist
+    return items
+
+
+def pt_advance_points(items, tris):
+    """pt_advance (the per-pair function of the swept-point queries) on explicit operands, on the device (cd_pt_advance_points): items
+    [n, 7] (p0, p1, dist), tris [n, 6, 3] (a0 a1 a2 at the start, b0 b1 b2 at the end) -> (toi[n] (+inf: not reported), dist[n],
+    closest[n, 3], uv[n, 2], feature[n], side[n], evals[n]), the values those of the last evaluation made."""
+    it = np.ascontiguousarray(np.asarray(items, dtype=np.float64).reshape(-1, 7))
+    t = np.ascontiguousarray(np.asarray(tris, dtype=np.float64).reshape(-1, 18))
+    if it.shape[0] != t.shape[0]:
+        raise ValueError(f"{it.shape[0]} items against {t.shape[0]} triangles")
+    n = it.shape[0]
+    toi = np.zeros(n, dtype=np.float64)
+    dist = np.zeros(n, dtype=np.float64)
+    closest = np.zeros((n, 3), dtype=np.float64)
+    uv = np.zeros((n, 2), dtype=np.float64)
+    feature = np.zeros(n, dtype=np.uint8)
+    side = np.zeros(n, dtype=np.uint8)
+    ev = np.zeros(n, dtype=np.uint32)
+    rc = load_library().cd_pt_advance_points(_ptr(it), _ptr(t), n, _ptr(toi), _ptr(dist), _ptr(closest), _ptr(uv), _ptr(feature), _ptr(side), _ptr(ev))
+    if rc != CD_OK:
+        raise CdError("cd_pt_advance_points", rc)
+    return toi, dist, closest, uv, feature, side, ev
 
 
 def ccd_points(tri, dist: float):

@@ -779,6 +779,54 @@ enum { CD_NEAREST_MIN = 1 };
 int cd_nearest_between(cd_ctx *a, cd_ctx *b, double rmax, int flags, uint32_t *faces, uint32_t *ids, double *dist,
                        const cd_witness_out *w, cd_nearest_info *info);
 
+/* ---- swept-point queries: moving points against the moving mesh (not reference behaviour) ----
+ * The moving question for a point: a particle, a strand node, a grain with a radius, a garment vertex against a body that deforms in
+ * the same step, the vertex-face half of a cloth's own CCD pass.  items is n x 7 doubles: p0, p1 (the point moves linearly from p0 to
+ * p1 during the step) and the item's own dist, finite and > 0; all six coordinates finite.  The mesh moves linearly from the context's
+ * vertices x0 (the tree's) to verts_end = x1, in cd_find_ccd's layout; x1 is uploaded by the call and never installed; NULL: the mesh
+ * does not move (x1 = x0).  skip_vertex (may be NULL): n vertex indices, 0xFFFFFFFF for none; the triangles with that index among
+ * their three are not tested for item k (the neighbour filter of a mesh's own vertices swept against the mesh), before the gate.
+ *
+ * pt_advance, the per-pair function (FP64, fixed operation order, no contraction; tests/sweep_ref.py restates it): every coordinate
+ * moves as a + t (b - a), the difference, the product and the sum each rounded.  L = max_i |(b_i - a_i) - (p1 - p0)| (1 + 2^-20) over
+ * the triangle's three vertices, |v| = sqrt((x x + y y) + z z); h = dist / 2.  At t = 0, on p0 and x0 themselves, r = pt_tri (the
+ * closest-point section).  r.dist <= dist: reported at this t.  Else, with the evaluation on x1 done or L == 0: not reported.  Else,
+ * after 1024 evaluations: reported UNRESOLVED at this t, with r.dist > dist.  Else t' = t + (r.dist - h) / L; t' >= 1: one evaluation
+ * on p1 and x1 themselves, reported at toi = 1 when within dist; otherwise t = t' and again.  A reported pair returns toi, r of the
+ * reporting evaluation (dist, u, v, feature, side and q, the closest point on the triangle as it stands at toi) and the evaluation count.
+ * The gate decides which pairs are evaluated at all: the box of {p0, p1} and the box of the triangle's six points, each widened by dist
+ * (lo - dist, hi + dist), overlap (closed).
+ * Guarantee: with M the largest |coordinate| of the point and the triangle over both ends and delta = 2^-38 M, a
+ * point that comes closer than h - delta to the exactly moving triangle at some t* is reported with toi <= t*, and stays at least
+ * h - delta away before toi.
+ *
+ * cd_sweep_points_all: one row for every (item k, face f) that passes the filter and the gate and that pt_advance reports.  Row r:
+ * rows[2 r] = k, rows[2 r + 1] = f, the index in cd_create's face list; each (k, f) once, in free order.  out (may be NULL, and so may
+ * each member), per row: the face's ID, toi, and dist, closest, uv, feature, side of the reporting evaluation.  CD_OVERFLOW with the
+ * true *n_rows when it exceeds cap_rows; nothing is written at or past cap_rows; cap_rows = 0 (rows may be NULL) counts only.  info (may
+ * be NULL): candidates of the walk (a number of this tree), pairs through the gate, pt_tri evaluations, unresolved rows.
+ * cd_sweep_points: per item the row of cd_sweep_points_all with the smallest (toi, ID, face index), bit for bit, by definition;
+ * without one face[k] = 0xFFFFFFFF, toi[k] = +inf and zeros elsewhere.  face is required, the others may be NULL.  flags must be 0.
+ * info (may be NULL): items with a row, records visited, pt_tri evaluations -- numbers of this tree and this run's item order.
+ * The rows and every value in them depend on the mesh, x1 and the items only -- not on the Morton frame, CD_OPT_TRAVERSAL,
+ * CD_OPT_CELL_TABLE, the build variant or the order of the items.  Items are walked in the order given, one lane each.
+ * Needs a tree built from the current vertices (CD_ERR_ORDER otherwise).  CD_ERR_ARG: a NULL context; NULL n_rows / face; n >
+ * 0xFFFFFFFF; NULL items with n > 0; NULL rows with cap_rows > 0; a non-finite coordinate; a dist that is not finite and > 0; flags
+ * other than 0 -- checked on the host before anything is launched, and nothing is written then.  n = 0 returns CD_OK.  The calls
+ * leave cd_stats, the last pair list, the order hint, a captured CD_OPT_GRAPH step, cd_debug_swept's view of the last CCD pass and
+ * every other query's buffers as they were; they keep device buffers of their own, swept records included (cd_destroy frees them).
+ *
+ * cd_pt_advance_points: pt_advance on explicit operands, host pointers, no context and no gate: items n x 7, tri n x 18 (a0 a1 a2 at
+ * x0, then b0 b1 b2 at x1).  toi = +inf: not reported; the other outputs (each may be NULL) are those of the last evaluation made. */
+typedef struct cd_sweep_rows { uint32_t *ids; double *toi; double *dist; double *closest; double *uv; uint8_t *feature; uint8_t *side; } cd_sweep_rows;
+int cd_sweep_points_all(cd_ctx *ctx, const double *verts_end, const double *items, uint64_t n, const uint32_t *skip_vertex,
+                        uint32_t *rows, uint64_t cap_rows, uint64_t *n_rows, const cd_sweep_rows *out, cd_ccd_info *info);
+int cd_sweep_points(cd_ctx *ctx, const double *verts_end, const double *items, uint64_t n, const uint32_t *skip_vertex, int flags,
+                    uint32_t *face, uint32_t *ids, double *toi, double *dist, double *closest, double *uv, uint8_t *feature,
+                    uint8_t *side, cd_point_info *info);
+int cd_pt_advance_points(const double *items, const double *tri, uint64_t n, double *toi, double *dist, double *closest, double *uv,
+                         uint8_t *feature, uint8_t *side, uint32_t *evals);
+
 /* Library / build identification: "mi355cd <version> gfx950". */
 const char *cd_version(void);
 
