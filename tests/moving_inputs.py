@@ -23,7 +23,9 @@ import oracle
 import point_ref as ptr
 import proximity_ref as pr
 import ray_ref as rr
+import sweep_ref as sw
 import swept_ref as sr
+import within_ref as wn
 import witness_ref as wr
 from test_between_gpu import _same_ccd as same_between_ccd, _same_contact as same_between_contact, _same_prox as same_between_prox  # noqa: F401
 from test_ccd_gpu import _same as _same_ccd
@@ -328,6 +330,107 @@ def want_contour(name, f):
     return ir.contour_pairs(s.frames[f], s.vidx, brute=_brute(s))
 
 
+# ---------------------------------------------------------------- the all-results item queries and the swept points, frame by frame
+INF_EVERY = 16                  # every 16th point of cd_points_within has no radius: every triangle is a row of it
+GROWTH_AT, GROWTH_ITEMS, GROWTH_EDGES = 1024, 64, 3.0
+SELF_SWEEP = ("slide", "float_double")          # the sequences with shared vertices: the mesh's own vertices as swept items
+SELF_SWEEP_ITEMS = 1000
+
+
+def _growth_block(name, f):
+    """jitter's dense frame only: (p0, p1) of GROWTH_ITEMS items at the collapsed cluster's centroid (+ N(0, 0.1 e)), appended as items
+    GROWTH_AT .. GROWTH_AT + 63 -- ONE whole 64-item block of the descent, whose candidates all go to one shard (number 16) of the
+    candidate buffer; at a radius / dist of GROWTH_EDGES edges the block has more ROWS than the shard's first WITHIN_SHARD_FIRST slots
+    (tests/test_moving_inputs.py), so the pass must grow the buffer and run again.  None on every other frame."""
+    if (name, f) != ("jitter", JITTER_DENSE_FRAME):
+        return None
+    s, e = seq(name), edge_at(name, f)
+    c0 = s.frames[f].reshape(-1, 3, 3)[:JITTER_DENSE].mean(axis=(0, 1))
+    p0 = c0 + np.random.default_rng(1).normal(size=(GROWTH_ITEMS, 3)) * 0.1 * e
+    return p0, p0 + np.random.default_rng(2).normal(size=(GROWTH_ITEMS, 3)) * 0.6 * e
+
+
+def _filler(name, f):
+    """The items NQ .. GROWTH_AT - 1 in front of the growth block: points a hundred edges and more beyond the mesh (no rows)."""
+    s, e = seq(name), edge_at(name, f)
+    return s.frames[f].max(axis=0) + 100.0 * e * (1.0 + np.arange(GROWTH_AT - NQ))[:, None]
+
+
+@functools.lru_cache(maxsize=None)
+def within_items(name, f):
+    """(points [n, 3], radii [n]) of cd_points_within on frame f: points(name, f) at radius edge_at, every INF_EVERY-th at +inf; on
+    jitter's dense frame the filler and the growth block behind them (n = 1088 there, NQ elsewhere)."""
+    s, e = seq(name), edge_at(name, f)
+    assert _brute(s) or s.nt <= 3000                                            # (63 points x every triangle: the restatement's rows)
+    pts, r = points(name, f), np.full(NQ, e)
+    r[::INF_EVERY] = np.inf
+    blk = _growth_block(name, f)
+    if blk is not None:
+        pts = np.concatenate([pts, _filler(name, f), blk[0]])
+        r = np.concatenate([r, np.full(GROWTH_AT - NQ, e), np.full(GROWTH_ITEMS, GROWTH_EDGES * e)])
+    return np.ascontiguousarray(pts), np.ascontiguousarray(r)
+
+
+@functools.lru_cache(maxsize=None)
+def want_within(name, f) -> wn.PointRows:
+    s = seq(name)
+    return wn.points_within_ref(s.frames[f], s.vidx, None, *within_items(name, f))
+
+
+@functools.lru_cache(maxsize=None)
+def want_rays_all(name, f) -> wn.RayRows:
+    """cd_cast_rays_all's rows of rays(name, f)."""
+    s = seq(name)
+    return wn.cast_rays_all_ref(s.frames[f], s.vidx, None, rays(name, f))
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_items(name, f):
+    """The items [n, 7] of the swept-point queries on frame f: points(name, f) moving by N(0, 0.6 edge_at) a coordinate, dist an eighth,
+    a quarter and a half of edge_at by i % 3 (a lane that reads its neighbour's dist gets another one); on jitter's dense frame the
+    filler (at rest) and the growth block behind them.  The mesh moves to x1(name, f), the CCD queries' end positions."""
+    s, e = seq(name), edge_at(name, f)
+    p0 = points(name, f)
+    p1 = p0 + np.random.default_rng(s.seed + f).normal(size=p0.shape) * 0.6 * e
+    dist = np.array([e / 8, e / 4, e / 2])[np.arange(NQ) % 3]
+    blk = _growth_block(name, f)
+    if blk is not None:
+        pad = _filler(name, f)
+        p0, p1 = np.concatenate([p0, pad, blk[0]]), np.concatenate([p1, pad, blk[1]])
+        dist = np.concatenate([dist, np.full(GROWTH_AT - NQ, e / 4), np.full(GROWTH_ITEMS, GROWTH_EDGES * e)])
+    return mi355cd.pack_sweeps(p0, p1, dist)
+
+
+@functools.lru_cache(maxsize=None)
+def want_sweep(name, f):
+    """(sweep_ref's SweepRows, (pairs through the gate, evaluations, unresolved rows)) of sweep_items(name, f) against frame f moving to x1(name, f)."""
+    s = seq(name)
+    return sw.sweep_rows_ref(s.frames[f], x1(name, f), s.vidx, None, sweep_items(name, f), counts=True)
+
+
+@functools.lru_cache(maxsize=None)
+def want_sweep_still(name, f):
+    """The same items against frame f at rest (verts_end = None)."""
+    s = seq(name)
+    return sw.sweep_rows_ref(s.frames[f], None, s.vidx, None, sweep_items(name, f), counts=True)
+
+
+@functools.lru_cache(maxsize=None)
+def self_sweep_items(name, f):
+    """The vertex-face half of the mesh's own CCD pass: its first SELF_SWEEP_ITEMS vertices moving to x1 -> (items, skip_vertex)."""
+    assert name in SELF_SWEEP
+    v, e = seq(name).frames[f], x1(name, f)
+    k = SELF_SWEEP_ITEMS
+    return mi355cd.pack_sweeps(v[:k], e[:k], edge_at(name, f) / 4), np.arange(k, dtype=np.uint32)
+
+
+@functools.lru_cache(maxsize=None)
+def want_self_sweep(name, f):
+    s = seq(name)
+    items, skip = self_sweep_items(name, f)
+    return sw.sweep_rows_ref(s.frames[f], x1(name, f), s.vidx, None, items, skip=skip, counts=True)
+
+
 def _pipeline(mode, v, vidx):
     if mode == "auto":
         off, span, lay = oracle.auto_frame(v, vidx)
@@ -552,6 +655,45 @@ def same_contour(got, want: ir.Rows, what="", tested=None):
         _same_bytes(getattr(g, k), getattr(want, k), (what, k))
     if tested is not None and want.tested is not None:
         assert tested == want.tested, (what, tested, want.tested)
+
+
+def item_rows(got):
+    """The tuple of cd_points_within / cd_cast_rays_all / cd_sweep_points_all -- (rows, values ..., n, rc) -- as within_ref's PointRows /
+    RayRows or sweep_ref's SweepRows (told apart by their number of columns), sorted by (item, face); the call fitted its capacity."""
+    *cols, n, rc = got
+    assert rc == 0 and n == cols[0].shape[0], (rc, n, cols[0].shape[0])
+    kind = {len(t._fields): t for t in (wn.PointRows, wn.RayRows, sw.SweepRows)}[len(cols)]
+    return kind(*wn.sort_rows(*cols))
+
+
+def item_call(rows, rc=0):
+    """What an all-results call that found `rows` returns."""
+    return tuple(rows) + (rows.rows.shape[0], rc)
+
+
+def same_item_rows(got, want, what=""):
+    """got: an all-results call's tuple; want: the restatement's rows (or item_rows of another call).  The return code, the count, the
+    set of (item, face), then every column of the rows in that order bit for bit (within_ref.same_rows)."""
+    n, rc = got[-2], got[-1]
+    assert rc == 0 and n == want.rows.shape[0] == got[0].shape[0], (what, rc, n, want.rows.shape[0], got[0].shape[0])
+    assert len(got) - 2 == len(want), what
+    wn.same_rows(got[:-2], want, what)
+
+
+def first_contact_call(rows: sw.SweepRows, n):
+    """What cd_sweep_points returns on n items whose rows are `rows`."""
+    first = sw.first_of(rows, n)
+    return first + (mi355cd.CdPointInfo(int((first[0] != sw.NONE).sum()), 0, 0),)
+
+
+def same_first_contact(got, rows: sw.SweepRows, n, what=""):
+    """got: cd_sweep_points' (face, ids, toi, dist, closest, uv, feature, side, info); rows: the restatement's rows of the same n items.
+    All eight outputs are sweep_ref.first_of of the rows, by their bytes, and n_found is the number of items with a row."""
+    want = sw.first_of(rows, n)
+    for k, (a, b) in enumerate(zip(got[:8], want)):
+        _same_bytes(a, b, (what, "first contact, output", k))
+    found = int(np.unique(rows.rows[:, 0]).size)
+    assert got[8].n_found == found, (what, got[8].n_found, found)
 
 
 def unordered_pairs(pairs):

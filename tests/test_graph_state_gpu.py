@@ -16,6 +16,10 @@ import pytest
 import mi355_synth as synth
 import mi355cd
 import oracle
+import point_ref as ptr
+import ray_ref as rr
+import sweep_ref as sr
+import within_ref as wr
 
 pytestmark = pytest.mark.gpu
 
@@ -572,6 +576,117 @@ def test_call_between_replays(op):
     try:
         for _ in range(2):
             INTERLEAVED[op](t)
+            t.steps(3)
+        assert t.eligible()
+    finally:
+        t.close()
+
+
+# ---- 4b. item queries between replays ---------------------------------------------------------------------------------------------
+# cd_cast_rays, cd_closest_points, cd_points_within, cd_cast_rays_all, cd_sweep_points_all and cd_sweep_points read what the captured step
+# rewrites (d_root, d_leaf, d_perm[0], the ticket words) and enqueue their own work on the context's stream.  None of them changes what a
+# step would enqueue (change=False): the replays after them go on, and stay right.
+
+NITEMS = 256
+CLOTH_EDGE = 2.88 / 100
+
+
+def _items(t, kind):
+    """256 rays / points / swept items derived from t.verts, with the restatement's answer; computed once per vertex array."""
+    key = ("items", kind, t.vver)
+    if key not in t._cache:
+        if kind == "rays":
+            rays = rr.mesh_rays(t.verts, t.vidx, NITEMS, seed=5)
+            t._cache[key] = (rays, rr.cast_rays_ref(t.verts, t.vidx, t.ids, rays), wr.cast_rays_all_ref(t.verts, t.vidx, t.ids, rays))
+        elif kind == "points":
+            pts = ptr.mesh_points(t.verts, t.vidx, NITEMS, seed=5, edge=CLOTH_EDGE)
+            rows = wr.points_within_ref(t.verts, t.vidx, t.ids, pts, 3 * CLOTH_EDGE)
+            t._cache[key] = (pts, ptr.closest_points_ref(t.verts, t.vidx, t.ids, pts), rows)
+        else:
+            p0 = ptr.mesh_points(t.verts, t.vidx, NITEMS, seed=5, edge=CLOTH_EDGE)
+            it = mi355cd.pack_sweeps(p0, p0 + np.random.default_rng(6).normal(size=p0.shape) * 0.6 * CLOTH_EDGE, CLOTH_EDGE / 4)
+            end = t.verts + 1e-3 * np.sin(7.0 * t.verts[:, [2, 0, 1]])          # _op_ccd's end positions
+            t._cache[key] = (it, end) + sr.sweep_rows_ref(t.verts, end, t.vidx, t.ids, it, counts=True)
+    return t._cache[key]
+
+
+def _same_columns(got, want, what):
+    for k, (a, b) in enumerate(zip(got, want)):
+        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (what, "column", k)
+
+
+def _same_row_sets(g, s, want, what):
+    """Two all-results calls' tuples (rows, values ..., n, rc): CD_OK, G's and S's rows bit-identical after sorting, and the restatement's."""
+    for name, got in (("G", g), ("S", s)):
+        assert got[-1] == mi355cd.CD_OK and got[-2] == got[0].shape[0] == want.rows.shape[0], (what, name, got[-2:], want.rows.shape[0])
+        wr.same_rows(got[:-2], want, f"{what}: {name} against the restatement")
+    _same_columns(wr.sort_rows(*g[:-2]), wr.sort_rows(*s[:-2]), what + ": G against S")
+
+
+def _op_cast_rays(t):
+    rays, want, _ = _items(t, "rays")
+    g, s = t.both("cast_rays()", lambda cd: cd.cast_rays(rays[:, 0:3], rays[:, 3:6], rays[:, 6]), change=False)
+    _same_columns(g[:5], s[:5], "cast_rays: G against S")
+    _same_columns(g[:5], want, "cast_rays against the restatement")
+    assert g[5].n_hits == s[5].n_hits == int((want[0] != mi355cd.RAY_MISS).sum()) > NITEMS // 8
+
+
+def _op_closest_points(t):
+    pts, want, _ = _items(t, "points")
+    g, s = t.both("closest_points()", lambda cd: cd.closest_points(pts), change=False)
+    _same_columns(g[:7], s[:7], "closest_points: G against S")
+    _same_columns(g[:7], want, "closest_points against the restatement")
+    assert g[7].n_found == s[7].n_found == NITEMS
+
+
+def _op_points_within(t):
+    pts, _, want = _items(t, "points")
+    g, s = t.both("points_within()", lambda cd: cd.points_within(pts, 3 * CLOTH_EDGE, cap=CAP) + (cd.within_tested,), change=False)
+    assert g[-1] == s[-1] >= want.rows.shape[0] > NITEMS
+    _same_row_sets(g[:-1], s[:-1], want, "points_within")
+
+
+def _op_cast_rays_all(t):
+    rays, _, want = _items(t, "rays")
+    g, s = t.both("cast_rays_all()", lambda cd: cd.cast_rays_all(rays[:, 0:3], rays[:, 3:6], rays[:, 6], cap=CAP) + (cd.rays_all_tested,), change=False)
+    assert g[-1] == s[-1] >= want.rows.shape[0] > NITEMS // 8
+    _same_row_sets(g[:-1], s[:-1], want, "cast_rays_all")
+
+
+def _op_sweep_points_all(t):
+    it, end, want, counts = _items(t, "sweeps")
+    g, s = t.both("sweep_points_all()", lambda cd: cd.sweep_points_all(it[:, 0:3], it[:, 3:6], it[:, 6], verts_end=end, cap=CAP) + (bytes(cd.sweep_info),), change=False)
+    assert want.rows.shape[0] > NITEMS // 8 and counts[2] == 0
+    _same_row_sets(g[:-1], s[:-1], want, "sweep_points_all")
+    info = mi355cd.CdCcdInfo.from_buffer_copy(g[-1])
+    assert g[-1] == s[-1] and (info.n_tested, info.n_evals, info.n_unresolved) == counts, (info.n_tested, info.n_evals, info.n_unresolved, counts)
+
+
+def _op_sweep_points(t):
+    it, end, want, _ = _items(t, "sweeps")
+    g, s = t.both("sweep_points()", lambda cd: cd.sweep_points(it[:, 0:3], it[:, 3:6], it[:, 6], verts_end=end), change=False)
+    _same_columns(g[:8], s[:8], "sweep_points: G against S")
+    _same_columns(g[:8], sr.first_of(want, NITEMS), "sweep_points against first_of of the restatement's rows")
+    assert g[8].n_found == s[8].n_found == np.unique(want.rows[:, 0]).size > NITEMS // 8
+
+
+ITEM_QUERIES = {
+    "cast_rays": _op_cast_rays, "closest_points": _op_closest_points, "points_within": _op_points_within, "cast_rays_all": _op_cast_rays_all,
+    "sweep_points_all": _op_sweep_points_all, "sweep_points": _op_sweep_points,
+}
+
+
+@pytest.mark.parametrize("op", list(ITEM_QUERIES))
+def test_item_query_between_replays(op):
+    """Two rounds of one item query on both twins and three steps: G's and S's results are bit-identical and the restatement's on the
+    current vertices, and the steps after the query are replays again (Twin.step's anti-vacuity rule, unchanged: the query is no change)
+    that still match the stream context and the oracle."""
+    verts, vidx = _cloth()
+    t = _twin(verts, vidx)
+    try:
+        for _ in range(2):
+            ITEM_QUERIES[op](t)
             t.steps(3)
         assert t.eligible()
     finally:

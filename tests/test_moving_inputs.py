@@ -1,7 +1,9 @@
 """The motion sequences of tests/moving_inputs.py can catch stale state, shown on the CPU: consecutive frames have different right
 answers, each sequence does what it is named for, and every comparison helper of tests/test_moving_mesh_gpu.py raises when it is fed
 frame f - 1's expected result against frame f's (the planted error: a device that kept the previous frame's state), and the
-comparisons of the witness, contour and nearest-triangle rows also when one field of one row of the right frame's result is changed."""
+comparisons of the witness, contour, nearest-triangle, all-within, every-hit and swept-point rows also when one field of one row of the
+right frame's result is changed.  The conditions the all-results and swept-point queries need of their items -- items without a row,
+items with several, contacts strictly inside the step, a block that overflows its shard -- are asserted here too."""
 from __future__ import annotations
 
 import numpy as np
@@ -12,7 +14,9 @@ import nearest_ref as nr
 import oracle
 import proximity_ref as pr
 import scale_inputs as si
+import sweep_ref as sw
 import swept_ref as sr
+import within_ref as wn
 import witness_ref as wr
 
 
@@ -194,6 +198,127 @@ def test_every_comparison_raises_on_the_previous_frames_result(name):
         if st0["stats"].n_pairs or st["stats"].n_pairs:
             with pytest.raises(AssertionError):
                 mi.same_step(st0["pairs"], st0["stats"].n_pairs, 0, st0["stats"].pairs_tested, st, what)
+
+
+@pytest.mark.parametrize("name", mi.NAMES)
+def test_item_row_comparisons_raise_on_the_previous_frames_result(name):
+    """cd_points_within, cd_cast_rays_all, cd_sweep_points_all and cd_sweep_points: same_item_rows and same_first_contact pass on the
+    frame's own restatement and raise on the one of the frame before it, in every frame of every sequence."""
+    s = mi.seq(name)
+    for f in range(1, len(s)):
+        what = f"{name} frame {f}"
+        n = mi.sweep_items(name, f).shape[0]
+        sets = [(mi.want_within(name, f - 1), mi.want_within(name, f)), (mi.want_rays_all(name, f - 1), mi.want_rays_all(name, f)),
+                (mi.want_sweep(name, f - 1)[0], mi.want_sweep(name, f)[0]), (mi.want_sweep_still(name, f - 1)[0], mi.want_sweep_still(name, f)[0])]
+        if name in mi.SELF_SWEEP:
+            sets.append((mi.want_self_sweep(name, f - 1)[0], mi.want_self_sweep(name, f)[0]))
+        for w0, w1 in sets:
+            mi.same_item_rows(mi.item_call(w1), w1, what)
+            mi.same_item_rows(mi.item_call(w1), mi.item_rows(mi.item_call(w1)), what)      # (the form the fresh context's result is compared in)
+            if w0.rows.shape[0] or w1.rows.shape[0]:
+                with pytest.raises(AssertionError):
+                    mi.same_item_rows(mi.item_call(w0), w1, what)
+            with pytest.raises(AssertionError):                                 # the return code
+                mi.same_item_rows(mi.item_call(w1, rc=1), w1, what)
+        w0, w1 = mi.want_sweep(name, f - 1)[0], mi.want_sweep(name, f)[0]
+        mi.same_first_contact(mi.first_contact_call(w1, n), w1, n, what)
+        if w0.rows.shape[0] or w1.rows.shape[0]:
+            with pytest.raises(AssertionError):
+                mi.same_first_contact(mi.first_contact_call(w0, mi.sweep_items(name, f - 1).shape[0]), w1, n, what)
+        assert mi.want_sweep(name, f - 1)[1] != mi.want_sweep(name, f)[1], what     # ... and so do the counts compared beside the rows
+    # the swept rows depend on the end positions: the same items against the mesh at rest are another row set
+    assert any(mi.want_sweep(name, f)[0].rows.shape != mi.want_sweep_still(name, f)[0].rows.shape
+               or not np.array_equal(mi.want_sweep(name, f)[0].toi, mi.want_sweep_still(name, f)[0].toi) for f in range(len(s))), name
+
+
+def test_one_corrupted_field_of_an_item_row_raises():
+    """The right frame's rows with one bit of one value, one ID, or one face of one row changed; one row dropped; a first contact that
+    is the item's SECOND row."""
+    name, f = "jitter", 1
+    for rows in (mi.want_within(name, f), mi.want_rays_all(name, f), mi.want_sweep(name, f)[0]):
+        k = rows.rows.shape[0] // 2
+        for field in rows._fields[1:]:
+            bad = _copy(rows)
+            a = getattr(bad, field)
+            if a.dtype == np.float64:
+                _flip_lowest_bit(a.reshape(a.shape[0], -1), (k, 0))
+            else:
+                a[k] ^= 1
+            with pytest.raises(AssertionError):
+                mi.same_item_rows(mi.item_call(bad), rows, field)
+        bad = _copy(rows)
+        bad.rows[k, 1] ^= 1
+        with pytest.raises(AssertionError):
+            mi.same_item_rows(mi.item_call(bad), rows, "face")
+        with pytest.raises(AssertionError):
+            mi.same_item_rows(mi.item_call(type(rows)(*(np.delete(a, k, axis=0) for a in rows))), rows, "a row less")
+    rows, n = mi.want_sweep(name, f)[0], mi.sweep_items(name, f).shape[0]
+    first = sw.first_of(rows, n)
+    item = int(np.flatnonzero(wn.rows_per_item(rows, n) >= 2)[0])
+    rest = type(rows)(*(a[~((rows.rows[:, 0] == item) & (rows.rows[:, 1] == first[0][item]))] for a in rows))     # the rows without that item's first
+    with pytest.raises(AssertionError):
+        mi.same_first_contact(mi.first_contact_call(rest, n), rows, n, "the second row")
+    got = mi.first_contact_call(rows, n)
+    with pytest.raises(AssertionError):                                         # n_found alone
+        mi.same_first_contact(got[:8] + (mi.mi355cd.CdPointInfo(got[8].n_found + 1, 0, 0),), rows, n, "n_found")
+
+
+@pytest.mark.parametrize("name", mi.LARGE)
+def test_item_queries_have_items_without_rows_and_items_with_several(name):
+    """Per sequence, pooled over its frames (F frames of n items): at least F n / 8 items with no row and at least F n / 16 with two or
+    more, for each of the three row sets; at least 4 swept rows with 0 < toi < 1; nothing unresolved."""
+    s = mi.seq(name)
+    none, several, items = np.zeros(3, dtype=np.int64), np.zeros(3, dtype=np.int64), np.zeros(3, dtype=np.int64)
+    inside = unresolved = 0
+    for f in range(len(s)):
+        sweep, counts = mi.want_sweep(name, f)
+        for k, (rows, n) in enumerate(((mi.want_within(name, f), mi.within_items(name, f)[0].shape[0]), (mi.want_rays_all(name, f), mi.NQ),
+                                       (sweep, mi.sweep_items(name, f).shape[0]))):
+            c = wn.rows_per_item(rows, n)
+            none[k] += (c == 0).sum(); several[k] += (c >= 2).sum(); items[k] += n
+        inside += int(((sweep.toi > 0) & (sweep.toi < 1)).sum())
+        unresolved += counts[2] + mi.want_sweep_still(name, f)[1][2]
+        if name in mi.SELF_SWEEP:
+            own, own_counts = mi.want_self_sweep(name, f)
+            assert own.rows.shape[0] > 100 and own_counts[2] == 0 and ((own.toi > 0) & (own.toi < 1)).sum() >= 4, (name, f)
+            assert not (s.vidx[own.rows[:, 1]] == own.rows[:, 0:1]).any()       # no face of the vertex itself
+        r = mi.within_items(name, f)[1]
+        assert np.isinf(r[:mi.NQ:mi.INF_EVERY]).all() and (wn.rows_per_item(mi.want_within(name, f), r.shape[0])[:mi.NQ:mi.INF_EVERY] == s.nt).all()
+        d = mi.sweep_items(name, f)[:mi.NQ, 6]
+        assert len({*d[0:3]}) == 3 and (d[3:] == d[:-3]).all()                 # three dists, by i % 3
+    print(f"{name}: (all within, every hit, swept points) items with no row {none.tolist()}, with several {several.tolist()}, of {items.tolist()}; "
+          f"{inside} swept rows with 0 < toi < 1")
+    assert (none * 8 >= items).all() and (several * 16 >= items).all(), (name, none, several, items)
+    assert inside >= 4 and unresolved == 0, (name, inside, unresolved)
+
+
+def test_tiny_sequences_have_item_rows_in_some_frame():
+    for n in mi.TINY:
+        name = f"tiny{n}"
+        rows = [(mi.want_within(name, f).rows.shape[0], mi.want_rays_all(name, f).rows.shape[0], mi.want_sweep(name, f)[0].rows.shape[0])
+                for f in range(len(mi.seq(name)))]
+        print(f"{name}: (all within, every hit, swept points) rows a frame: {rows}")
+        assert all(max(r[k] for r in rows) > 0 for k in range(3)), (name, rows)
+
+
+def test_the_growth_block_has_more_rows_than_a_shard_of_the_first_candidate_buffer():
+    """Items GROWTH_AT .. GROWTH_AT + 63 of jitter's dense frame are ONE block of the descent (one shard), and their rows alone -- rows
+    never exceed candidates -- are more than the shard's first WITHIN_SHARD_FIRST slots: the pass must grow its buffer and run again.
+    A condition on the inputs; the restatement gives 18 325 all-within rows and 18 842 swept rows."""
+    f = mi.JITTER_DENSE_FRAME
+    assert mi.GROWTH_AT % 64 == 0 and mi.GROWTH_ITEMS == 64 and mi.GROWTH_AT >= mi.NQ
+    pts, r = mi.within_items("jitter", f)
+    it = mi.sweep_items("jitter", f)
+    assert pts.shape[0] == it.shape[0] == mi.GROWTH_AT + mi.GROWTH_ITEMS
+    figures = []
+    for rows in (mi.want_within("jitter", f), mi.want_sweep("jitter", f)[0], mi.want_sweep_still("jitter", f)[0]):
+        blk = int((rows.rows[:, 0] >= mi.GROWTH_AT).sum())
+        fill = int(((rows.rows[:, 0] >= mi.NQ) & (rows.rows[:, 0] < mi.GROWTH_AT)).sum())
+        figures.append(blk)
+        assert blk > mi.mi355cd.WITHIN_SHARD_FIRST and fill == 0, (blk, fill)
+    print("jitter's growth block: rows (all within, swept points, swept points at rest)", figures, "of", mi.mi355cd.WITHIN_SHARD_FIRST, "slots")
+    for g in range(len(mi.seq("jitter"))):                                      # no other frame has the block: its buffers stay as the dense frame left them
+        assert (mi.within_items("jitter", g)[0].shape[0] == mi.NQ) == (mi.sweep_items("jitter", g).shape[0] == mi.NQ) == (g != f)
 
 
 def test_between_comparisons_raise_on_the_previous_frames_result():

@@ -10,12 +10,25 @@ triangle and CD_NEAREST_MIN, at two radii and at +inf) in both roles of every sc
 (face a, face b) and every column is compared by its bytes; their buffers get twice the frame's row count, so they grow on a dense
 frame and are reused, oversized, on the sparse frames after it.
 
+So do the all-results item queries and the swept points: cd_points_within ("all within": the frame's points at radius edge, every 16th
+at +inf), cd_cast_rays_all ("every hit") and cd_sweep_points_all / cd_sweep_points ("swept points": the points moving by 0.6 edges,
+three dists by i % 3, the mesh moving to the CCD queries' end positions -- the x1 cd_self_ccd has just refit swept[0] to in that entry,
+another x1 or none in the others -- once more with the mesh at rest behind every entry but self_ccd, and on `slide` and `float_double`
+the mesh's own first 1000 vertices with skip_vertex) are in the permuted list, against within_ref's and sweep_ref's all-pairs
+restatements: the set of (item, face), then every column bit for bit.  Their smallest row per item is the device's own
+cd_closest_points / cd_cast_rays answer; cd_sweep_points is sweep_ref.first_of of the restatement's rows; cd_debug_swept reads the same
+bytes after the sweeps as before them.  On jitter's dense frame one whole 64-item block at the collapsed cluster has more rows than its
+shard of the first candidate buffer holds (WITHIN_SHARD_FIRST): the pass grows the buffer and runs again, with CD_OK and the exact rows,
+and the sparse frames after it run on the grown buffers.
+
 Counters that are NOT compared with the fresh context's: node_visits and tri_tests of cd_cast_rays / cd_closest_points /
-cd_nearest_between (the last also not with a restatement: nearest_ref has no walk), and the collision step's node_visits and
+cd_sweep_points / cd_nearest_between (the last also not with a restatement: nearest_ref has no walk), and the collision step's node_visits and
 wave_steps -- they count the walk, which may legitimately differ with the options the entry left behind (traversal bookkeeping, the
 order hint; cd_nearest_between's shared bound makes them differ from run to run: test_nearest_gpu.py).  pairs_tested of a collision step is
 compared with the oracle's, proximity's and CCD's evaluation counts with the restatement's and the fresh context's, n_candidates with
-swept_ref's count and the fresh context's, the contour calls' n_tested with isect_ref's, cd_nearest_between's n_found with nearest_ref's."""
+swept_ref's count and the fresh context's, the contour calls' n_tested with isect_ref's, cd_nearest_between's n_found with nearest_ref's;
+within_tested and rays_all_tested with the fresh context's; cd_sweep_points_all's n_tested, n_evals and n_unresolved with sweep_ref's counts
+and the fresh context's, its n_candidates -- a function of the swept records and the items -- with the fresh context's."""
 from __future__ import annotations
 
 import ctypes as C
@@ -28,6 +41,7 @@ import mi355cd
 import moving_inputs as mi
 import proximity_ref as pr
 import swept_ref as sr
+import within_ref as wn
 
 pytestmark = pytest.mark.gpu
 
@@ -89,8 +103,9 @@ def _equal_bytes(a, b, what):
         assert np.array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8)), (what, k)
 
 
-def _queries(cd, fresh, name, f):
-    """The queries of frame f as (label, callable): each compares the long-lived context with the reference and with the fresh one."""
+def _queries(cd, fresh, name, f, entry=None):
+    """The queries of frame f as (label, callable): each compares the long-lived context with the reference and with the fresh one.
+    entry: the rebuild entry the frame went through (the sweep's extra call at rest is made behind every entry but self_ccd)."""
     s = mi.seq(name)
     v, vidx = s.frames[f], s.vidx
     what = f"{name} frame {f}"
@@ -193,8 +208,85 @@ def _queries(cd, fresh, name, f):
         assert gf[2] == mi355cd.CD_OK, what
         mi.same_contour(got, mi.contour_rows(gf, fresh.contour_tested), what + " contour against the fresh context", tested)
 
+    room = lambda rows: max(1, 2 * rows.rows.shape[0])                         # the item queries' row buffers, in the same way
+
+    def all_within():
+        pts, rad = mi.within_items(name, f)
+        want = mi.want_within(name, f)
+        got = cd.points_within(pts, rad, cap=room(want))
+        tested = cd.within_tested
+        mi.same_item_rows(got, want, what + " all within")
+        gf = fresh.points_within(pts, rad, cap=room(want))
+        mi.same_item_rows(got, mi.item_rows(gf), what + " all within against the fresh context")
+        assert tested == fresh.within_tested and tested >= got[-2], (what, tested, fresh.within_tested)
+        single = cd.closest_points(pts, rad)                                    # (pinned by point_queries) per point the smallest row
+        _equal_bytes(wn.closest_of(mi.item_rows(got), pts.shape[0]), single[:7], what + " all within: the smallest row a point against closest_points")
+        if pts.shape[0] > mi.NQ:                                                # the dense frame: the growth block alone overflows its shard
+            assert int((got[0][:, 0] >= mi.GROWTH_AT).sum()) > mi355cd.WITHIN_SHARD_FIRST, what
+
+    def every_hit():
+        want = mi.want_rays_all(name, f)
+        call = lambda c: c.cast_rays_all(rays[:, 0:3], rays[:, 3:6], rays[:, 6], cap=room(want))
+        got = call(cd)
+        tested = cd.rays_all_tested
+        mi.same_item_rows(got, want, what + " every hit")
+        mi.same_item_rows(got, mi.item_rows(call(fresh)), what + " every hit against the fresh context")
+        assert tested == fresh.rays_all_tested and tested >= got[-2], (what, tested, fresh.rays_all_tested)
+        _equal_bytes(wn.first_hit_of(mi.item_rows(got), rays.shape[0]), cast(cd)[:5], what + " every hit: the smallest row a ray against cast_rays")
+
+    def swept_points():
+        it, e = mi.sweep_items(name, f), mi.x1(name, f)
+        n = it.shape[0]
+        want, counts = mi.want_sweep(name, f)
+        before = _swept(cd)
+        sweep = lambda c, items, end, rows, skip=None: c.sweep_points_all(items[:, 0:3], items[:, 3:6], items[:, 6], verts_end=end, skip_vertex=skip, cap=room(rows))
+        tally = lambda i: (i.n_tested, i.n_evals, i.n_unresolved)
+        got = sweep(cd, it, e, want)
+        info = cd.sweep_info
+        mi.same_item_rows(got, want, what + " swept points")
+        assert tally(info) == counts and info.n_candidates >= info.n_tested, (what, tally(info), counts, info.n_candidates)
+        gf = sweep(fresh, it, e, want)
+        fi = fresh.sweep_info
+        mi.same_item_rows(got, mi.item_rows(gf), what + " swept points against the fresh context")
+        assert bytes(info) == bytes(fi), (what, [(k, getattr(info, k), getattr(fi, k)) for k, _ in mi355cd.CdCcdInfo._fields_])
+        if n > mi.NQ:
+            assert int((got[0][:, 0] >= mi.GROWTH_AT).sum()) > mi355cd.WITHIN_SHARD_FIRST, what
+        first = cd.sweep_points(it[:, 0:3], it[:, 3:6], it[:, 6], verts_end=e)
+        mi.same_first_contact(first, want, n, what + " swept points")
+        ff = fresh.sweep_points(it[:, 0:3], it[:, 3:6], it[:, 6], verts_end=e)
+        _equal_bytes(first[:8], ff[:8], what + " first contact against the fresh context")
+        assert first[8].n_found == ff[8].n_found, what
+        if entry != "self_ccd":                                                 # the mesh at rest: the swept records of the vertices themselves
+            still, still_counts = mi.want_sweep_still(name, f)
+            got = sweep(cd, it, None, still)
+            mi.same_item_rows(got, still, what + " swept points, the mesh at rest")
+            assert tally(cd.sweep_info) == still_counts, (what, tally(cd.sweep_info), still_counts)
+        if name in mi.SELF_SWEEP:                                               # the mesh's own vertices against its own faces
+            (items, skip), (own, own_counts) = mi.self_sweep_items(name, f), mi.want_self_sweep(name, f)
+            got = sweep(cd, items, e, own, skip)
+            mi.same_item_rows(got, own, what + " swept points, the mesh's own vertices")
+            assert tally(cd.sweep_info) == own_counts, (what, tally(cd.sweep_info), own_counts)
+            mi.same_item_rows(got, mi.item_rows(sweep(fresh, items, e, own, skip)), what + " the mesh's own vertices against the fresh context")
+            mi.same_first_contact(cd.sweep_points(items[:, 0:3], items[:, 3:6], items[:, 6], verts_end=e, skip_vertex=skip), own, items.shape[0],
+                                  what + " the mesh's own vertices")
+        after = _swept(cd)                                                      # swept[0] is the CCD pass's: no sweep may touch it
+        assert (before is None) == (after is None), what
+        if before is not None:
+            _equal_bytes(before[:3], after[:3], what + " the CCD pass's swept tree after the sweeps")
+            assert before[3] == after[3] and sr.bits1(before[4]) == sr.bits1(after[4]), what
+
     return [("proximity", proximity), ("ccd", ccd), ("rays", ray_queries), ("points", point_queries), ("root box", box),
-            ("proximity witness", proximity_witness), ("ccd witness", ccd_witness), ("contour", contour)]
+            ("proximity witness", proximity_witness), ("ccd witness", ccd_witness), ("contour", contour),
+            ("all within", all_within), ("every hit", every_hit), ("swept points", swept_points)]
+
+
+def _swept(cd):
+    """cd_debug_swept of the context's own swept tree, or None before its first CCD pass (CD_ERR_ORDER)."""
+    try:
+        return cd.debug_swept()
+    except mi355cd.CdError as e:
+        assert e.rc == mi355cd.CD_ERR_ORDER
+        return None
 
 
 def _new(verts, vidx, mode):
@@ -222,7 +314,7 @@ def _run(name, schedule):
                 assert form == (1 if f in mi.FRAME_EXIT_OUT else 0) or (f == len(s) - 2 and form == 1), (f, form)
             with _new(v, s.vidx, s.frame_mode) as fresh:
                 fresh.build_tree()
-                qs = _queries(cd, fresh, name, f)
+                qs = _queries(cd, fresh, name, f, entry)
                 for k in order.permutation(len(qs)):                           # no query's result depends on which one ran before it
                     qs[k][1]()
     if schedule == "rotate" and len(s) >= len(ENTRIES):

@@ -12,6 +12,8 @@ import pytest
 import mi355_synth as synth
 import mi355cd
 import oracle
+import point_ref as ptr
+import scale_inputs as si
 import sweep_ref as sr
 import within_ref as wr
 
@@ -471,3 +473,65 @@ def test_leaves_the_context_as_it_was_and_errors_write_nothing():
         assert new.rows.shape != want.rows.shape or not np.array_equal(new.rows, want.rows)      # the answer did change
         wr.same_rows(_sweep(cd, it, x1, "moved"), new, "after update_vertices and a rebuild")
         _same_tuple(_first(cd, it, x1)[:8], sr.first_of(new, it.shape[0]), "first contact after update_vertices and a rebuild")
+
+
+# ---------------------------------------------------------------- 9: the fp32 range ends, and a translated mesh
+SCALE_MESHES = si.meshes()
+NSCALE = 512
+
+
+@functools.lru_cache(maxsize=None)
+def _scale_case(name):
+    """512 points of the mesh moved by N(0, 0.6 edge) a coordinate, dist a quarter edge, the mesh moving to scale_inputs.motion: the
+    restatement's rows and counts at k = 0."""
+    v, vidx, edge = SCALE_MESHES[name]
+    vv = np.asarray(v, dtype=np.float64).reshape(-1, 3)
+    p0 = ptr.mesh_points(vv, vidx, NSCALE, seed=3, edge=edge)
+    it = mi355cd.pack_sweeps(p0, p0 + np.random.default_rng(21).normal(size=p0.shape) * 0.6 * edge, 0.25 * edge)
+    x1 = si.motion(vv, edge)
+    want, counts = sr.sweep_rows_ref(vv, x1, vidx, None, it, counts=True)
+    return vv, vidx, x1, it, want, counts
+
+
+@pytest.mark.parametrize("k", si.SCALES)
+@pytest.mark.parametrize("name", list(SCALE_MESHES))
+def test_fp32_range(name, k):
+    """Mesh, end positions and all seven columns of the items scaled by 2^k, past both fp32 ends (the band of tests/scale_inputs.py):
+    the k = 0 rows, IDs, toi bits, u, v, feature and side, dist and closest times 2^k exactly, and the k = 0 counts; at the scales of
+    scale_inputs.EDGES also the restatement on the scaled inputs themselves; first contact: first_of of those rows.  The descent and
+    the first-contact kernel filter in fp32 with a pad of their own, 2 dist + 2 dist 2^-20 + M 2^-20 rounded up: +inf at the upper end
+    of the band, a subnormal or 0 at the lower."""
+    vv, vidx, x1, it, want, counts = _scale_case(name)
+    per = np.bincount(want.rows[:, 0].astype(np.int64), minlength=NSCALE)
+    inside = int(((want.toi > 0) & (want.toi < 1)).sum())
+    assert (per == 0).sum() >= 64 and (per >= 2).sum() >= 32 and inside >= 4 and counts[2] == 0, ((per == 0).sum(), (per >= 2).sum(), inside, counts)
+    what = f"{name} 2^{k}"
+    ws = want._replace(dist=si.scaled(want.dist, k), closest=si.scaled(want.closest, k))
+    vs, xs, its = si.scaled(vv, k), si.scaled(x1, k), si.scaled(it, k)
+    with _ctx(vs, vidx) as cd:
+        rows = _sweep(cd, its, xs, what)
+        wr.same_rows(rows, ws, what)
+        assert _counts(cd) == counts, (what, _counts(cd), counts)
+        if k in si.EDGES:
+            direct, direct_counts = sr.sweep_rows_ref(vs, xs, vidx, None, its, counts=True)
+            wr.same_rows(rows, direct, what + ", the restatement on the scaled inputs")
+            assert _counts(cd) == direct_counts, (what, _counts(cd), direct_counts)
+        _same_tuple(_first(cd, its, xs)[:8], sr.first_of(ws, NSCALE), what + ", first contact")
+
+
+@pytest.mark.parametrize("name", list(SCALE_MESHES))
+def test_translated_mesh_gives_the_restatement(name):
+    """Mesh, end positions, p0 and p1 translated by 2^20 + 0.37: M is 2^20 while the motion is a fraction of an edge, so the pad's
+    M 2^-20 term (about 1) decides which candidates pass the fp32 filters."""
+    vv, vidx, x1, it, _, _ = _scale_case(name)
+    off = 2.0 ** 20 + 0.37
+    vt, xt, itt = vv + off, x1 + off, it.copy()
+    itt[:, 0:6] += off
+    want, counts = sr.sweep_rows_ref(vt, xt, vidx, None, itt, counts=True)
+    per = np.bincount(want.rows[:, 0].astype(np.int64), minlength=NSCALE)
+    print(f"{name} translated: {want.rows.shape[0]} rows, {int((per == 0).sum())} of {NSCALE} items with none, {int((per >= 2).sum())} with several, counts {counts}")
+    assert (per == 0).sum() >= 64 and (per >= 2).sum() >= 32
+    with _ctx(vt, vidx) as cd:
+        wr.same_rows(_sweep(cd, itt, xt, name), want, f"{name} translated")
+        assert _counts(cd) == counts, (name, _counts(cd), counts)
+        _same_tuple(_first(cd, itt, xt)[:8], sr.first_of(want, NSCALE), f"{name} translated, first contact")

@@ -14,6 +14,7 @@ import mi355cd
 import oracle
 import point_ref as ptr
 import proximity_ref as pr
+import ray_ref as rr
 import scale_inputs as si
 import within_ref as wr
 
@@ -341,6 +342,47 @@ def test_translated_mesh_gives_the_restatement(name):
     with _ctx(vt, vidx) as cd:
         wr.same_rows(_points(cd, pts, rm, name), want, f"{name} translated")
     print(f"{name} translated: {want.rows.shape[0]} rows, {int((wr.rows_per_item(want, NSCALE) == 0).sum())} of {NSCALE} points with none")
+
+
+@functools.lru_cache(maxsize=None)
+def _ray_scale_case(name):
+    v, vidx, edge = SCALE_MESHES[name]
+    vv = np.asarray(v, dtype=np.float64).reshape(-1, 3)
+    rays = rr.mesh_rays(vv, vidx, NSCALE, seed=3)
+    return vv, vidx, rays, wr.cast_rays_all_ref(vv, vidx, None, rays)
+
+
+BAND = tuple(k for k in si.SCALES if abs(k) <= 300) + (-300, 300)             # tests/test_rays_gpu.py's: the band include/mi355cd.h states for ray_tri
+
+
+@pytest.mark.parametrize("k", BAND)
+@pytest.mark.parametrize("name", list(SCALE_MESHES))
+def test_rays_fp32_range(name, k):
+    """cd_cast_rays_all with mesh, origins and directions scaled by 2^k, past both fp32 ends (tmax is a parameter value and stays): the
+    k = 0 rows, IDs, t bits, u, v and side; at the scales of scale_inputs.EDGES also the restatement on the scaled inputs themselves."""
+    vv, vidx, rays, want = _ray_scale_case(name)
+    c = wr.rows_per_item(want, NSCALE)
+    assert (c == 0).sum() >= 64 and (c >= 2).sum() >= 32, ((c == 0).sum(), (c >= 2).sum())
+    rs = rays.copy()
+    rs[:, 0:6] = si.scaled(rays[:, 0:6], k)
+    with _ctx(si.scaled(vv, k), vidx) as cd:
+        rows = _rays(cd, rs, name)
+    wr.same_rows(rows, want, f"{name} 2^{k}")
+    if k in si.EDGES:
+        wr.same_rows(rows, wr.cast_rays_all_ref(si.scaled(vv, k), vidx, None, rs), f"{name} 2^{k}, the restatement on the scaled inputs")
+
+
+@pytest.mark.parametrize("name", list(SCALE_MESHES))
+def test_rays_on_a_translated_mesh_give_the_restatement(name):
+    vv, vidx, _, _ = _ray_scale_case(name)
+    vt = vv + (2.0 ** 20 + 0.37)
+    rt = rr.mesh_rays(vt, vidx, NSCALE, seed=5)
+    want = wr.cast_rays_all_ref(vt, vidx, None, rt)
+    c = wr.rows_per_item(want, NSCALE)
+    print(f"{name} translated: {want.rows.shape[0]} hits, {int((c == 0).sum())} of {NSCALE} rays with none, {int((c >= 2).sum())} with several")
+    assert (c == 0).sum() >= 64 and (c >= 2).sum() >= 32
+    with _ctx(vt, vidx) as cd:
+        wr.same_rows(_rays(cd, rt, name), want, f"{name} translated")
 
 
 # ---------------------------------------------------------------- 9: a mesh that moves
