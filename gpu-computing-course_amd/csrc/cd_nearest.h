@@ -1,5 +1,6 @@
 // cd_nearest.h -- nearest-triangle and separation-distance queries between two meshes: for every triangle of context a the nearest
-// triangle of context b, and the nearest pair of all.  Not reference behaviour.  The per-pair predicate is
+// triangle of context b, and the nearest pair of all.  Not reference behaviour.  The self form -- one mesh against
+// itself, k_nearest_self -- is below, before k_nearest_min.  The per-pair predicate is
 // tri_distance (cd_math.h), a's triangle first; the witness is k_pair_witness's (cd_witness.h) over the leaf pairs left here.
 //   k_nearest_between<MIN> : one lane per leaf of a in a's SORTED order (neighbours in a wave are neighbours in space); the row is
 //       written at perm_a[j], the triangle's index in cd_create's face list.  The lane walks b's records as k_closest_points walks
@@ -147,6 +148,129 @@ __global__ __launch_bounds__(NEAREST_THREADS) void k_nearest_between(const NodeR
         ids[2 * (size_t)i] = found ? A.id : 0u; ids[2 * (size_t)i + 1] = found ? bid : 0u;
         dist[i] = found ? best : __builtin_inf();
         wleaf[i] = make_uint2(found ? j : NEAREST_NONE, bleaf);
+    }
+    item_counters_add(mine && found, visits, tests, &st->n_found, &st->node_visits, &st->tri_tests);
+}
+
+// ---- the self form: the nearest non-neighbouring triangle of the SAME mesh (cd_nearest_self) ----------------------
+//   k_nearest_self<MIN> : k_nearest_between with one tree on both sides -- the same box_box2 and pad (both roots are the one root), the
+//       same two-halved loop around the ONE inline site of tri_distance, the same acceptance on d <= rmax, the same shared word.  What
+//       differs:
+//       EXCLUSION  a leaf the walk enters is tested BEFORE it becomes pending: leaf j itself and every leaf that shares a vertex index
+//              with j (neighbor_count >= 1, cd_find_proximity's rule) are passed over.  That costs one LeafTri load in the walk and
+//              saves the wave-wide evaluation pass; an excluded leaf is not an evaluation.
+//       ORDER  tri_distance(A, B) and tri_distance(B, A) differ in their last bits, so the two triangles are swapped into
+//              k_prox_exact's order before the call: A is the one with the smaller (ID, face index).  Both rows that hold a pair hold
+//              the same bits, cd_find_proximity's.  wleaf keeps the PLAYED order, so that k_pair_witness evaluates the same call.
+//       SEED   a greedy descent of the own tree ends at leaf j.  The first bound comes from an ADMISSIBLE leaf near j in Morton order
+//              instead: of j + 1, j - 1, j + 2, ... up to NEAREST_SELF_SEED steps each side, the admissible leaf whose FP64 box is
+//              nearest to A's (the first of equals; the first admissible leaf alone is a poor seed where the Morton curve jumps:
+//              DESIGN.md section 21 has the counts); none found: no seed, the bound stays rmax.  The seed only tightens the bound (it
+//              is a candidate like any other; the walk passes over it when it meets it again), so the rows do not depend on it.
+//       n == 1 has no partner and no records: nothing is read.  n == 2 is one record, two leaf children.
+#ifndef CD_NEAREST_SELF_SEED
+#define CD_NEAREST_SELF_SEED 16                       // (0: the no-seed build of the seed decision)
+#endif
+constexpr uint32_t NEAREST_SELF_SEED = CD_NEAREST_SELF_SEED;
+
+// the squared distance between two FP64 boxes (0 when they meet): the seed's choice only, never a filter
+__device__ __forceinline__ double box_gap2(const Box &a, const Box &b)
+{
+    const double gx = fmax2(fmax2(b.x1 - a.x2, a.x1 - b.x2), 0.0), gy = fmax2(fmax2(b.y1 - a.y2, a.y1 - b.y2), 0.0), gz = fmax2(fmax2(b.z1 - a.z2, a.z1 - b.z2), 0.0);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
+template <bool MIN>
+__global__ __launch_bounds__(NEAREST_THREADS) void k_nearest_self(const NodeRec32 *__restrict__ recs, const int32_t *__restrict__ root_name,
+                                                                  const LeafTri *__restrict__ leaf, const uint32_t *__restrict__ perm,
+                                                                  const double *__restrict__ verts, const double *__restrict__ root_box, int n,
+                                                                  double rmax, NearestState *__restrict__ st, uint32_t *__restrict__ faces,
+                                                                  uint32_t *__restrict__ ids, double *__restrict__ dist, uint2 *__restrict__ wleaf)
+{
+    const uint32_t j = blockIdx.x * NEAREST_THREADS + threadIdx.x;
+    const bool mine = (int)j < n;
+    LeafTri A{};
+    Box abox{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    uint32_t own = 0;                                                    // the row: leaf j's index in cd_create's face list
+    if (mine) {
+        A = leaf[j];
+        own = perm[j];
+        abox = box_set(load_vertex(verts, A.v0), load_vertex(verts, A.v1), load_vertex(verts, A.v2));
+    }
+    const double pad = root_max_abs(root_box) * PROX_SLACK;
+    double best = rmax;                                                  // own bound: min(rmax, the best candidate's dist)
+    double bound = best;                                                 // MIN: min(best, the shared word); else best
+    if (MIN) bound = fmin2(bound, __longlong_as_double((long long)st->min_bits));
+    double bound2 = bound * bound;
+    uint32_t bleaf = NEAREST_NONE, bface = NEAREST_NONE, bid = 0u;
+    uint32_t visits = 0, tests = 0;
+    RecCursor w{};
+    bool walking = mine && n > 1;                                        // (n == 1: no partner, no records)
+    if (walking) walking = w.start_root(recs, n, (uint32_t)*root_name);  // (no tree: nothing is read; nothing is found)
+    // SEED: of the admissible leaves j + 1, j - 1, j + 2, ... the one whose box is nearest to A's (the first of equals)
+    uint32_t seeded = NEAREST_NONE;                                      // the seed's leaf, not evaluated a second time
+    if (walking) {
+        double near2 = 0.0;
+        for (uint32_t step = 0; step < 2u * NEAREST_SELF_SEED; ++step) {
+            const uint32_t off = (step >> 1) + 1u;
+            const bool up = !(step & 1u);
+            if (up ? off >= (uint32_t)n - j : off > j) continue;
+            const uint32_t c = up ? j + off : j - off;
+            const LeafTri S = leaf[c];
+            if (neighbor_count(A.v0, A.v1, A.v2, S.v0, S.v1, S.v2) >= 1) continue;
+            const double g2 = box_gap2(abox, box_set(load_vertex(verts, S.v0), load_vertex(verts, S.v1), load_vertex(verts, S.v2)));
+            if (seeded == NEAREST_NONE || g2 < near2) { seeded = c; near2 = g2; }
+        }
+    }
+    bool pending = seeded != NEAREST_NONE;
+    uint32_t k = seeded;
+    while (walking || pending) {
+        // every lane walks until it holds a pending leaf or is done
+        while (walking && !pending) {
+            ++visits;
+            const bool enter = !(box_box2(w.h0, w.h1, abox, pad) > bound2);   // CLOSED; a NaN enters
+            if (enter && w.internal(n)) {
+                walking = w.descend(recs, n);
+                continue;
+            }
+            if (enter && w.leaf(n)) {
+                k = w.leaf_index();
+                if (k != j && k != seeded) {                             // the exclusions, before the leaf becomes pending
+                    const LeafTri B = leaf[k];
+                    pending = neighbor_count(A.v0, A.v1, A.v2, B.v0, B.v1, B.v2) < 1;   // collision.cuh:38
+                }
+            }
+            walking = w.next(recs, n);                                   // (the cursor moves on before the leaf is evaluated: its path does not depend on the bound)
+        }
+        // the wave evaluates all pending leaves in one pass
+        if (pending) {
+            pending = false;
+            ++tests;
+            const LeafTri B = leaf[k];
+            const uint32_t f = perm[k];
+            const bool swap = B.id < A.id || (B.id == A.id && f < own);  // A: the smaller ID (then face index), as k_prox_exact
+            const LeafTri P = swap ? B : A, Q = swap ? A : B;
+            const double d = tri_distance(load_vertex(verts, P.v0), load_vertex(verts, P.v1), load_vertex(verts, P.v2),
+                                          load_vertex(verts, Q.v0), load_vertex(verts, Q.v1), load_vertex(verts, Q.v2));
+            if (d <= rmax) {
+                // the smallest (dist, ID, face index)
+                if (bface == NEAREST_NONE || d < best || (d == best && (B.id < bid || (B.id == bid && f < bface)))) {
+                    bleaf = k; bface = f; bid = B.id; best = d;
+                    if (MIN) atomicMin(&st->min_bits, (unsigned long long)__double_as_longlong(d));
+                }
+            }
+            bound = best;
+            if (MIN) bound = fmin2(bound, __longlong_as_double((long long)__hip_atomic_load(&st->min_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
+            bound2 = bound * bound;
+        }
+    }
+    const bool found = bface != NEAREST_NONE;
+    if (mine) {
+        const bool swap = found && (bid < A.id || (bid == A.id && bface < own));
+        faces[2 * (size_t)own] = found ? own : NEAREST_NONE; faces[2 * (size_t)own + 1] = bface;
+        ids[2 * (size_t)own] = found ? A.id : 0u; ids[2 * (size_t)own + 1] = found ? bid : 0u;
+        dist[own] = found ? best : __builtin_inf();
+        wleaf[own] = found ? (swap ? make_uint2(bleaf, j) : make_uint2(j, bleaf)) : make_uint2(NEAREST_NONE, NEAREST_NONE);   // the played order
     }
     item_counters_add(mine && found, visits, tests, &st->n_found, &st->node_visits, &st->tri_tests);
 }

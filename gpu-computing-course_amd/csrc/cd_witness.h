@@ -15,7 +15,7 @@
 namespace cd {
 
 constexpr int WITNESS_THREADS = 256;
-constexpr uint32_t WITNESS_NO_PAIR = 0xffffffffu;     // in wleaf[k].x: row k has no pair (only cd_nearest_between leaves such rows)
+constexpr uint32_t WITNESS_NO_PAIR = 0xffffffffu;     // in wleaf[k].x: row k has no pair (only the nearest queries leave such rows)
 
 // every output may be NULL
 __device__ __forceinline__ void witness_store(const TriWitness &w, unsigned long long k, double *__restrict__ points, double *__restrict__ bary,

@@ -409,6 +409,9 @@ struct cd_ctx {
     // their own, na + 1 rows (the last one: CD_NEAREST_MIN's).
     // nearest.block: dist [n] | points [6 n] | bary [4 n] (doubles) | leaf pair [n] (uint2) | faces [2 n] | ids [2 n] (u32) | feature [2 n] (u8)
     ItemBuf<NearestState> nearest;
+    // the same against the mesh itself (cd_nearest_self): nt + 1 rows of its own, with the faces that played A and B behind the IDs
+    // nearest_self.block: dist [n] | points [6 n] | bary [4 n] | leaf pair [n] | faces [2 n] | ids [2 n] | played faces [2 n] | feature [2 n]
+    ItemBuf<NearestState> nearest_self;
     // all-results item queries (cd_points_within, cd_cast_rays_all, cd_within.h): buffers of their own, allocated on first use.
     // within.items: points [4 n];   within.vals: closest [3 cap] | uv [2 cap] (doubles) | ids [cap] (u32) | feature [cap] | side [cap] (u8)
     // rays_all.items: rays [7 n];   rays_all.vals: uv [2 cap] (doubles) | ids [cap] (u32) | side [cap] (u8)
@@ -445,7 +448,7 @@ void free_all(cd_ctx *c)
     hipFree(c->pp_flags); hipFree(c->pp_os);
     c->prox.release(); c->cont.release(); c->ccd.release(); c->bw.release(); c->ccd_x1.release(); c->bw_x1a.release(); c->bw_x1b.release();
     for (SweptBuf &sw : c->swept) sw.release();
-    c->rays.release(); c->points.release(); c->nearest.release(); c->within.release(); c->rays_all.release(); c->sweep.release();
+    c->rays.release(); c->points.release(); c->nearest.release(); c->nearest_self.release(); c->within.release(); c->rays_all.release(); c->sweep.release();
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -2974,6 +2977,61 @@ int cd_nearest_between(cd_ctx *a, cd_ctx *b, double rmax, int flags, uint32_t *f
     HIPCHK(hipMemcpyAsync(h, st, sizeof(NearestState), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(faces, d_faces + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
     if (w && w->faces) HIPCHK(hipMemcpyAsync(w->faces, d_faces + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
+    if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
+    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist + first, sizeof(double) * rows, hipMemcpyDeviceToHost, s));
+    if (w && w->points) HIPCHK(hipMemcpyAsync(w->points, d_points + 6 * first, sizeof(double) * 6 * rows, hipMemcpyDeviceToHost, s));
+    if (w && w->bary) HIPCHK(hipMemcpyAsync(w->bary, d_bary + 4 * first, sizeof(double) * 4 * rows, hipMemcpyDeviceToHost, s));
+    if (w && w->feature) HIPCHK(hipMemcpyAsync(w->feature, d_feat + 2 * first, sizeof(uint8_t) * 2 * rows, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (info) { info->n_found = h->n_found; info->node_visits = h->node_visits; info->tri_tests = h->tri_tests; }
+    return CD_OK;
+}
+// ---- nearest non-neighbouring triangle of the same mesh, and the mesh's clearance (cd_nearest.h) ----------------------------------------
+// cd_nearest_between's host side with one context: buffers of its own, the context's stream, ONE synchronisation.  w->faces are the faces
+// that PLAYED A and B (not own, partner): k_pair_witness writes them from the leaf pairs, so it runs whenever w asks for anything -- for
+// faces alone it evaluates nothing.
+constexpr uint64_t NEAREST_SELF_BYTES = NEAREST_BYTES + 8;                  // ... and the played faces
+#ifndef CD_NEAREST_SELF_SHARED_BOUND
+#define CD_NEAREST_SELF_SHARED_BOUND 1                                      // (0: CD_NEAREST_MIN from the plain kernel's rows -- the build the shared bound was measured against)
+#endif
+int cd_nearest_self(cd_ctx *c, double rmax, int flags, uint32_t *faces, uint32_t *ids, double *dist, const cd_witness_out *w, cd_nearest_info *info)
+{
+    const bool mn = flags == CD_NEAREST_MIN;
+    if (!c || !faces || !(rmax >= 0.0) || (flags != 0 && !mn)) return CD_ERR_ARG;   // (a NaN rmax fails the comparison)
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    const uint64_t nt = c->nt;
+    int rc = c->nearest_self.ensure(nt + 1, NEAREST_SELF_BYTES);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const uint64_t cap = c->nearest_self.block.cap;
+    double *d_dist = reinterpret_cast<double *>(c->nearest_self.block.d), *d_points = d_dist + cap, *d_bary = d_points + 6 * cap;
+    uint2 *d_leaf = reinterpret_cast<uint2 *>(d_bary + 4 * cap);
+    uint32_t *d_faces = reinterpret_cast<uint32_t *>(d_leaf + cap), *d_ids = d_faces + 2 * cap, *d_played = d_ids + 2 * cap;
+    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_played + 2 * cap);
+    NearestState *st = c->nearest_self.state.d, *h = c->nearest_self.state.h;
+    *h = NearestState{};
+    std::memcpy(&h->min_bits, &rmax, sizeof rmax);                          // the shared bound starts at rmax
+    HIPCHK(hipMemcpyAsync(st, h, sizeof(NearestState), hipMemcpyHostToDevice, s));
+    const uint32_t grid = cdiv(nt, NEAREST_THREADS);
+    if (mn) {
+        k_nearest_self<CD_NEAREST_SELF_SHARED_BOUND != 0><<<grid, NEAREST_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)nt,
+                                                                                           rmax, st, d_faces, d_ids, d_dist, d_leaf);
+        k_nearest_min<<<1, NEAREST_MIN_THREADS, 0, s>>>(nt, nt, st, d_faces, d_ids, d_dist, d_leaf);
+    } else {
+        k_nearest_self<false><<<grid, NEAREST_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)nt, rmax, st,
+                                                               d_faces, d_ids, d_dist, d_leaf);
+    }
+    const uint64_t first = mn ? nt : 0, rows = mn ? 1 : nt;                 // the rows the caller gets
+    if (w && (w->faces || w->points || w->bary || w->feature))
+        k_pair_witness<false><<<cdiv(rows, WITNESS_THREADS), WITNESS_THREADS, 0, s>>>(d_leaf + first, rows, c->d_leaf, c->d_perm[0], c->d_verts, nullptr,
+                                                                                      c->d_leaf, c->d_perm[0], c->d_verts, nullptr, nullptr,
+                                                                                      w->faces ? d_played + 2 * first : nullptr,
+                                                                                      w->points ? d_points + 6 * first : nullptr, w->bary ? d_bary + 4 * first : nullptr,
+                                                                                      w->feature ? d_feat + 2 * first : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h, st, sizeof(NearestState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(faces, d_faces + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
+    if (w && w->faces) HIPCHK(hipMemcpyAsync(w->faces, d_played + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
     if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
     if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist + first, sizeof(double) * rows, hipMemcpyDeviceToHost, s));
     if (w && w->points) HIPCHK(hipMemcpyAsync(w->points, d_points + 6 * first, sizeof(double) * 6 * rows, hipMemcpyDeviceToHost, s));

@@ -254,7 +254,7 @@ EXPORTS = [
     "cd_closest_points", "cd_pt_tri_points",
     "cd_find_proximity_witness", "cd_find_proximity_between_witness", "cd_find_ccd_witness", "cd_find_ccd_between_witness", "cd_tri_witness_points",
     "cd_find_collisions_contour", "cd_find_collisions_between_contour", "cd_tri_isect_points",
-    "cd_nearest_between",
+    "cd_nearest_between", "cd_nearest_self",
     "cd_points_within", "cd_cast_rays_all",
     "cd_sweep_points_all", "cd_sweep_points", "cd_pt_advance_points",
 ]
@@ -350,6 +350,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_find_collisions_between_contour.argtypes = lib.cd_find_collisions_between.argtypes + [cp]
     lib.cd_tri_isect_points.argtypes = [vp, C.c_uint64, vp, vp, vp]
     lib.cd_nearest_between.argtypes = [vp, vp, C.c_double, C.c_int, vp, vp, vp, wp, C.POINTER(CdNearestInfo)]
+    lib.cd_nearest_self.argtypes = [vp, C.c_double, C.c_int, vp, vp, vp, wp, C.POINTER(CdNearestInfo)]
     lib.cd_points_within.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(CdPointRows)]
     lib.cd_cast_rays_all.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(CdRayRows)]
     lib.cd_sweep_points_all.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p, C.POINTER(CdSweepRows), C.POINTER(CdCcdInfo)]
@@ -754,6 +755,24 @@ class CollisionDetector:
         rc = self.lib.cd_nearest_between(self._ctx, other._ctx, float(rmax), CD_NEAREST_MIN if minimum else 0, _ptr(faces), _ptr(ids), _ptr(dist),
                                          C.byref(wa.out) if witness else None, C.byref(info))
         self._chk("cd_nearest_between", rc)
+        return Nearest(faces, ids, dist, wa.take(n) if witness else None, info)
+
+    # ---- nearest non-neighbouring triangle of the mesh itself, and its clearance (cd_nearest_self)
+    def nearest_self(self, rmax=np.inf, minimum: bool = False, witness: bool = False):
+        """cd_nearest_self on the tree that is there.  -> Nearest(faces, ids, dist, witness, info): one row per triangle in face-list
+        order -- of the triangles that share no vertex index with it and have tri_distance <= rmax the smallest (dist, ID, face index);
+        the pair's distance is cd_find_proximity's, bit for bit -- or, with minimum, the ONE row of the mesh's clearance: the smallest
+        (dist, own ID, own face, partner ID, partner face).  Nothing within rmax: faces NEAREST_NONE, dist +inf, everything else 0.
+        witness: a Witness of the rows' pairs (else None); its faces are the ones that played A and B, not (own, partner)."""
+        n = 1 if minimum else self.nt
+        faces = np.empty((n, 2), dtype=np.uint32)
+        ids = np.empty((n, 2), dtype=np.uint32)
+        dist = np.empty(n, dtype=np.float64)
+        wa = _WitnessArrays(n) if witness else None
+        info = CdNearestInfo()
+        rc = self.lib.cd_nearest_self(self._ctx, float(rmax), CD_NEAREST_MIN if minimum else 0, _ptr(faces), _ptr(ids), _ptr(dist),
+                                      C.byref(wa.out) if witness else None, C.byref(info))
+        self._chk("cd_nearest_self", rc)
         return Nearest(faces, ids, dist, wa.take(n) if witness else None, info)
 
     def find_collisions(self, cap: int = 1 << 20):

@@ -779,6 +779,37 @@ enum { CD_NEAREST_MIN = 1 };
 int cd_nearest_between(cd_ctx *a, cd_ctx *b, double rmax, int flags, uint32_t *faces, uint32_t *ids, double *dist,
                        const cd_witness_out *w, cd_nearest_info *info);
 
+/* ---- nearest non-neighbouring triangle of the same mesh, and the mesh's clearance (not reference behaviour) ----
+ * The threshold-free self question: how near does this mesh come to itself, and where?  A CCD dist or a step size for a garment whose
+ * clearance is not known yet, a per-triangle self-clearance map, a "nothing of this mesh is near itself" test.  rmax is a search
+ * radius, 0 <= rmax <= +inf.
+ *
+ * Admissible pairs: the unordered pairs (i, f) of distinct faces with no shared vertex index (cd_find_proximity's neighbour rule; equal
+ * IDs do not exclude a pair).  The distance of a pair is tri_distance(A, B) with A the face with the smaller (ID, face index),
+ * cd_find_proximity's rule: both rows that hold a pair hold the same bits, and they are cd_find_proximity's dists for that pair.
+ *
+ * flags = 0, per triangle: nt rows; row i belongs to face i of cd_create's face list.  Of the faces f admissible with i and with
+ * distance <= rmax (closed) the winner is the one with the smallest (dist, ID of f, f).  faces[2 i] = i, faces[2 i + 1] = f;
+ * ids[2 i], ids[2 i + 1]: the IDs of i and f; dist[i]: that distance.  When nothing is within rmax both faces are 0xFFFFFFFF,
+ * dist[i] = +inf and every other output of the row is 0 (cd_nearest_between's "nothing" row).
+ * flags = CD_NEAREST_MIN, the clearance of the mesh: exactly ONE row, the lexicographic minimum of the flags = 0 rows by
+ * (dist, own ID, own face, partner ID, partner face), or the "nothing" row.
+ * ids and dist may be NULL.  w (may be NULL, and so may each of its members): points, bary and feature of a row are
+ * tri_witness(A, B) of the row's pair in the order that was PLAYED; w->faces[2 row], w->faces[2 row + 1] are the faces that played
+ * A and B -- not (own, partner): cd_find_proximity_witness's convention.  The witness's dist is dist[row] bit for bit; a pair in
+ * contact has features 7 / 7 and zeros; a "nothing" row has w->faces 0xFFFFFFFF, features 0 / 0 and zeros.
+ * info (may be NULL): rows that found a partner, boxes tested, tri_distance evaluations (an excluded triangle is not one) -- numbers
+ * of this run and this tree; with CD_NEAREST_MIN the last two may differ from run to run, the result may not.
+ * Guarantee: the result depends on the mesh and rmax only -- not on the Morton frame, CD_OPT_TRAVERSAL, CD_OPT_CELL_TABLE, the build
+ * variant or the run -- over the band of coordinate magnitudes of cd_find_proximity.  The context is left as it was: cd_stats, the
+ * last pair list, the order hint, a captured CD_OPT_GRAPH step and every other query's buffers.  The call keeps device buffers of its
+ * own (grown on demand; cd_destroy frees them) and runs on the context's stream with one host synchronisation.
+ * CD_ERR_ARG: a NULL context; rmax NaN or negative; flags other than 0 / CD_NEAREST_MIN; NULL faces -- checked on the host before
+ * anything is launched, and nothing is written then.  CD_ERR_ORDER unless the context has a tree of its current vertices.  There is
+ * no CD_OVERFLOW: the row count is fixed. */
+int cd_nearest_self(cd_ctx *ctx, double rmax, int flags, uint32_t *faces, uint32_t *ids, double *dist,
+                    const cd_witness_out *w, cd_nearest_info *info);
+
 /* ---- swept-point queries: moving points against the moving mesh (not reference behaviour) ----
  * The moving question for a point: a particle, a strand node, a grain with a radius, a garment vertex against a body that deforms in
  * the same step, the vertex-face half of a cloth's own CCD pass.  items is n x 7 doubles: p0, p1 (the point moves linearly from p0 to
