@@ -531,6 +531,63 @@ __device__ __forceinline__ PtTri pt_tri(const d3 p, const d3 p0, const d3 p1, co
     return r;
 }
 
+// ---------------------------------------------------------------- column against triangle (not reference behaviour)
+// column_tri(p, c; v0, v1, v2): does the line through p parallel to axis c (the COLUMN) cross the triangle, with which orientation, and
+// above or below p?  FP64 with this operation order, no contraction; every difference, product and sum is rounded on its own.
+// With a = (c + 1) % 3, b = (c + 2) % 3 the triangle is projected onto the (a, b) plane:
+//   gate : p_a within [min, max] of the three v_a and p_b within those of v_b, CLOSED, exact comparisons of the inputs; else no cover.
+//   edge l -> h : la = l_a - p_a, lb = l_b - p_b, ha = h_a - p_a, hb = h_b - p_b, E = la hb - lb ha  (swapping l and h negates E exactly:
+//          the two faces on a shared edge see opposite values, with no canonical order of the edge's ends);
+//          E0 = E(v1 -> v2), E1 = E(v2 -> v0), E2 = E(v0 -> v1): E_i over their sum is v_i's barycentric weight of p's projection.
+//   sign of an edge: the sign of E where E != 0; else the sign of l_b - h_b (the ORIGINAL coordinates, an exact comparison); else the
+//          sign of h_a - l_a; else 0.  That is the sign E would have with p moved by (eps, eps^2) in (a, b), eps > 0 as small as needed:
+//          E(p + (eps, eps^2)) = E + eps (l_b - h_b) + eps^2 (h_a - l_a).  The moved point lies on no edge and under no vertex, so of
+//          the faces around an edge or a vertex under p exactly those it really lies under cover: ONE owner per crossing of a surface.
+//   cover: o = +1 when the three signs are +, o = -1 when they are -, else 0 (a face whose projection is a line or a point has two
+//          edges of opposite sign, or a 0: it never covers).
+//   height: z_i = v_i,c - p_c, S = (E0 + E1) + E2, zc = (E0 z0 + E1 z1) + E2 z2: zc / S is the face's height over p on the column.
+//          S == 0: not counted.  above when (zc > 0 and S > 0) or (zc < 0 and S < 0); else below -- zc == 0 (p on the face) is below.
+// Every comparison is written so that a NaN fails it: a NaN in E gives the sign 0, a NaN in S or zc a face that is not counted.
+// Where every computed E has its true sign or is a true zero the result is exactly the moved point's; a wrong sign -- possible only
+// for a point within rounding of an edge's projection -- can put a count off by one.  Exact (adaptive) arithmetic is not attempted.
+// Scaling p and the triangle by 2^k changes nothing while no nonzero product or sum leaves the normal range.
+struct ColumnTri { int o; bool counted, above; double e0, e1, e2, zc, s; };
+__device__ __forceinline__ double axis3(const d3 v, const int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
+__device__ __forceinline__ int column_edge_sign(const double la, const double lb, const double ha, const double hb, const double pa, const double pb, double &E)
+{
+    const double dla = la - pa, dlb = lb - pb, dha = ha - pa, dhb = hb - pb;
+    E = dla * dhb - dlb * dha;
+    if (E > 0.0) return 1;
+    if (E < 0.0) return -1;
+    if (!(E == 0.0)) return 0;
+    if (lb > hb) return 1;
+    if (lb < hb) return -1;
+    if (ha > la) return 1;
+    if (ha < la) return -1;
+    return 0;
+}
+__device__ __forceinline__ ColumnTri column_tri(const d3 p, const int c, const d3 v0, const d3 v1, const d3 v2)
+{
+    ColumnTri r{0, false, false, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int a = c == 2 ? 0 : c + 1, b = c == 0 ? 2 : c - 1;
+    const double pa = axis3(p, a), pb = axis3(p, b);
+    const double a0 = axis3(v0, a), a1 = axis3(v1, a), a2 = axis3(v2, a), b0 = axis3(v0, b), b1 = axis3(v1, b), b2 = axis3(v2, b);
+    // min <= p <= max without forming min and max: a NaN vertex coordinate takes no part here (its edges' E are NaN: no cover)
+    const bool gate = (a0 <= pa || a1 <= pa || a2 <= pa) && (a0 >= pa || a1 >= pa || a2 >= pa) && (b0 <= pb || b1 <= pb || b2 <= pb) && (b0 >= pb || b1 >= pb || b2 >= pb);
+    const int s0 = column_edge_sign(a1, b1, a2, b2, pa, pb, r.e0);
+    const int s1 = column_edge_sign(a2, b2, a0, b0, pa, pb, r.e1);
+    const int s2 = column_edge_sign(a0, b0, a1, b1, pa, pb, r.e2);
+    const double pc = axis3(p, c);
+    const double z0 = axis3(v0, c) - pc, z1 = axis3(v1, c) - pc, z2 = axis3(v2, c) - pc;
+    r.s = (r.e0 + r.e1) + r.e2;
+    r.zc = (r.e0 * z0 + r.e1 * z1) + r.e2 * z2;
+    if (!gate) return r;
+    r.o = (s0 > 0 && s1 > 0 && s2 > 0) ? 1 : ((s0 < 0 && s1 < 0 && s2 < 0) ? -1 : 0);
+    r.counted = r.o != 0 && (r.s > 0.0 || r.s < 0.0) && r.zc == r.zc;
+    r.above = r.counted && ((r.zc > 0.0 && r.s > 0.0) || (r.zc < 0.0 && r.s < 0.0));
+    return r;
+}
+
 // morton.h:7-29
 __device__ __forceinline__ uint64_t expand64(uint64_t v)
 {

@@ -17,6 +17,7 @@
 #include "cd_nearest.h"
 #include "cd_within.h"
 #include "cd_sweep.h"
+#include "cd_inside.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -420,6 +421,12 @@ struct cd_ctx {
     // sweep.rows.items: items [7 n];   sweep.rows.vals: toi [cap] | closest [3 cap] | uv [2 cap] (doubles) | ids [cap] (u32) | feature [cap] | side [cap] (u8)
     // sweep.first.block: items [7 n] | toi [n] | dist [n] | closest [3 n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | feature [n] | side [n] (u8)
     SweepBuf sweep;
+    // inside / outside and signed distance (cd_points_inside, cd_signed_distance, cd_inside.h): buffers of their own, allocated on first use.
+    // inside.block: points [3 n] (doubles) | n_above [n] | n_below [n] (u32) | w_above [n] | w_below [n] (i32) | inside [n] (u8)
+    // sdist.block: points [4 n] | dist [n] | closest [3 n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | feature [n] | inside [n] (u8);
+    // sdist.state: the closest-point kernel's counters, sdist_in: k_points_inside's
+    ItemBuf<PointState> inside, sdist;
+    StateWords<PointState> sdist_in;
 };
 
 namespace {
@@ -449,6 +456,7 @@ void free_all(cd_ctx *c)
     c->prox.release(); c->cont.release(); c->ccd.release(); c->bw.release(); c->ccd_x1.release(); c->bw_x1a.release(); c->bw_x1b.release();
     for (SweptBuf &sw : c->swept) sw.release();
     c->rays.release(); c->points.release(); c->nearest.release(); c->nearest_self.release(); c->within.release(); c->rays_all.release(); c->sweep.release();
+    c->inside.release(); c->sdist.release(); c->sdist_in.release();
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -3040,6 +3048,122 @@ int cd_nearest_self(cd_ctx *c, double rmax, int flags, uint32_t *faces, uint32_t
     HIPCHK(hipStreamSynchronize(s));
     if (info) { info->n_found = h->n_found; info->node_visits = h->node_visits; info->tri_tests = h->tri_tests; }
     return CD_OK;
+}
+// ---- inside / outside and signed distance (cd_inside.h) ---------------------------------------------------------------------------
+// Own buffers (points, results, counters): nothing any other call keeps is touched.
+constexpr uint64_t INSIDE_BYTES = 3 * 8 + 4 * 4 + 1;                        // device bytes a point: the point, the four counts, inside
+constexpr uint64_t SDIST_BYTES = 4 * 8 + 8 + 24 + 16 + 4 + 4 + 1 + 1;       // the point with its rmax, dist, closest, uv, face, ID, feature, inside
+// what both calls reject before anything else is looked at: 0 when the arguments are in order
+static int inside_args(const cd_ctx *c, const double *points, uint64_t n, int axis, int flags, const void *required)
+{
+    if (!c || axis < 0 || axis > 2 || (flags & ~CD_INSIDE_PARITY) || (n && (!points || !required)) || n > (1ull << 37)) return CD_ERR_ARG;
+    for (uint64_t i = 0; i < 3 * n; ++i) if (!std::isfinite(points[i])) return CD_ERR_ARG;   // before anything is launched: nothing is written for a bad point
+    return c->stage < ST_REFIT ? CD_ERR_ORDER : CD_OK;
+}
+static void launch_points_inside(cd_ctx *c, int axis, const double *d_pts, int stride, uint64_t n, int parity, PointState *st, uint8_t *inside, uint32_t *n_above,
+                                 uint32_t *n_below, int32_t *w_above, int32_t *w_below)
+{
+    const uint32_t grid = cdiv(n, INSIDE_THREADS);
+#define CD_INSIDE_LAUNCH(C) k_points_inside<C><<<grid, INSIDE_THREADS, 0, c->stream>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_verts, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, \
+                                                                                     d_pts, stride, n, parity, st, inside, n_above, n_below, w_above, w_below)
+    if (axis == 0) CD_INSIDE_LAUNCH(0);
+    else if (axis == 1) CD_INSIDE_LAUNCH(1);
+    else CD_INSIDE_LAUNCH(2);
+#undef CD_INSIDE_LAUNCH
+}
+int cd_points_inside(cd_ctx *c, const double *points, uint64_t n, int axis, int flags, uint8_t *inside, uint32_t *n_above, uint32_t *n_below, int32_t *w_above,
+                     int32_t *w_below, cd_inside_info *info)
+{
+    int rc = inside_args(c, points, n, axis, flags, inside);
+    if (rc) return rc;
+    if (n == 0) { if (info) *info = cd_inside_info{0, 0, 0}; return CD_OK; }
+    rc = c->inside.ensure(n, INSIDE_BYTES);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const uint64_t cap = c->inside.block.cap;
+    double *d_pts = reinterpret_cast<double *>(c->inside.block.d);
+    uint32_t *d_na = reinterpret_cast<uint32_t *>(d_pts + 3 * cap), *d_nb = d_na + cap;
+    int32_t *d_wa = reinterpret_cast<int32_t *>(d_nb + cap), *d_wb = d_wa + cap;
+    uint8_t *d_in = reinterpret_cast<uint8_t *>(d_wb + cap);
+    PointState *st = c->inside.state.d, *h = c->inside.state.h;
+    HIPCHK(hipMemcpyAsync(d_pts, points, sizeof(double) * 3 * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(st, 0, sizeof(PointState), s));
+    launch_points_inside(c, axis, d_pts, 3, n, flags & CD_INSIDE_PARITY, st, d_in, n_above ? d_na : nullptr, n_below ? d_nb : nullptr, w_above ? d_wa : nullptr,
+                         w_below ? d_wb : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h, st, sizeof(PointState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(inside, d_in, n, hipMemcpyDeviceToHost, s));
+    if (n_above) HIPCHK(hipMemcpyAsync(n_above, d_na, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    if (n_below) HIPCHK(hipMemcpyAsync(n_below, d_nb, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    if (w_above) HIPCHK(hipMemcpyAsync(w_above, d_wa, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    if (w_below) HIPCHK(hipMemcpyAsync(w_below, d_wb, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (info) { info->n_inside = h->n_found; info->node_visits = h->node_visits; info->tri_tests = h->tri_tests; }
+    return CD_OK;
+}
+// k_closest_points<false> with rmax = +inf and k_points_inside on the same uploaded rows, one synchronisation; the sign is set on the host
+int cd_signed_distance(cd_ctx *c, const double *points, uint64_t n, int axis, int flags, double *sdist, uint32_t *face, uint32_t *ids, double *closest, double *uv,
+                       uint8_t *feature, uint8_t *inside, cd_point_info *info)
+{
+    int rc = inside_args(c, points, n, axis, flags, sdist);
+    if (rc) return rc;
+    if (n == 0) { if (info) *info = cd_point_info{0, 0, 0}; return CD_OK; }
+    rc = c->sdist.ensure(n, SDIST_BYTES);
+    if (!rc) rc = c->sdist_in.ensure();
+    if (rc) return rc;
+    std::vector<double> rows;                                               // cd_closest_points' rows: the point and rmax = +inf
+    std::vector<uint8_t> in_host;
+    try { rows.resize(4 * n); in_host.resize(inside ? 0 : n); } catch (const std::bad_alloc &) { return -(int)hipErrorOutOfMemory; }
+    uint8_t *in = inside ? inside : in_host.data();
+    for (uint64_t i = 0; i < n; ++i) { rows[4 * i] = points[3 * i]; rows[4 * i + 1] = points[3 * i + 1]; rows[4 * i + 2] = points[3 * i + 2]; rows[4 * i + 3] = HUGE_VAL; }
+    hipStream_t s = c->stream;
+    const uint64_t cap = c->sdist.block.cap;
+    double *d_pts = reinterpret_cast<double *>(c->sdist.block.d), *d_dist = d_pts + 4 * cap, *d_q = d_dist + cap, *d_uv = d_q + 3 * cap;
+    uint32_t *d_face = reinterpret_cast<uint32_t *>(d_uv + 2 * cap), *d_ids = d_face + cap;
+    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + cap), *d_in = d_feat + cap;
+    PointState *st = c->sdist.state.d, *h = c->sdist.state.h, *st_in = c->sdist_in.d, *h_in = c->sdist_in.h;
+    HIPCHK(hipMemcpyAsync(d_pts, rows.data(), sizeof(double) * 4 * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(st, 0, sizeof(PointState), s));
+    HIPCHK(hipMemsetAsync(st_in, 0, sizeof(PointState), s));
+    k_closest_points<false><<<cdiv(n, POINT_THREADS), POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_pts, n, st,
+                                                                            d_face, ids ? d_ids : nullptr, d_dist, closest ? d_q : nullptr, uv ? d_uv : nullptr,
+                                                                            feature ? d_feat : nullptr, nullptr);
+    launch_points_inside(c, axis, d_pts, 4, n, flags & CD_INSIDE_PARITY, st_in, d_in, nullptr, nullptr, nullptr, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h, st, sizeof(PointState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_in, st_in, sizeof(PointState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sdist, d_dist, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(in, d_in, n, hipMemcpyDeviceToHost, s));
+    if (face) HIPCHK(hipMemcpyAsync(face, d_face, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    if (closest) HIPCHK(hipMemcpyAsync(closest, d_q, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
+    if (uv) HIPCHK(hipMemcpyAsync(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, s));
+    if (feature) HIPCHK(hipMemcpyAsync(feature, d_feat, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint64_t i = 0; i < n; ++i) if (in[i] && sdist[i] > 0.0) sdist[i] = -sdist[i];   // (a dist of 0 stays +0)
+    if (info) { info->n_found = h->n_found; info->node_visits = h->node_visits + h_in->node_visits; info->tri_tests = h->tri_tests + h_in->tri_tests; }
+    return CD_OK;
+}
+int cd_column_tri_points(const double *points, const double *tri, uint64_t n, int axis, int8_t *cover, uint8_t *above, double *E, double *zc, double *S)
+{
+    if (!points || !tri || !cover || axis < 0 || axis > 2) return CD_ERR_ARG;
+    if (n == 0) return CD_OK;
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_p = dev.in(points, 3 * n), *d_t = dev.in(tri, 9 * n);
+    int8_t *d_c = dev.out<int8_t>(n);
+    uint8_t *d_a = dev.out<uint8_t>(n);
+    double *d_e = dev.out<double>(3 * n), *d_z = dev.out<double>(n), *d_s = dev.out<double>(n);
+    if (dev.e == hipSuccess) {
+        k_column_tri_points<<<strided_grid(n, 256), 256>>>(d_p, d_t, n, axis, d_c, d_a, d_e, d_z, d_s);
+        dev.e = hipGetLastError();
+    }
+    dev.back(cover, d_c, n);
+    dev.back(above, d_a, n);
+    dev.back(E, d_e, 3 * n);
+    dev.back(zc, d_z, n);
+    dev.back(S, d_s, n);
+    return dev.rc();
 }
 }  // extern "C"
 

@@ -152,6 +152,13 @@ CD_NEAREST_MIN = 1
 NEAREST_NONE = 0xFFFFFFFF
 
 
+class CdInsideInfo(C.Structure):
+    _fields_ = [("n_inside", C.c_uint64), ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64)]
+
+
+CD_INSIDE_PARITY = 1
+
+
 class Nearest(collections.namedtuple("Nearest", "faces ids dist witness info")):
     """cd_nearest_between's rows: faces u32[n, 2] (face of self, face of other; NEAREST_NONE twice when nothing is within rmax),
     ids u32[n, 2], dist f64[n] (+inf then), witness (a Witness over the same rows, or None), info (CdNearestInfo)."""
@@ -257,6 +264,7 @@ EXPORTS = [
     "cd_nearest_between", "cd_nearest_self",
     "cd_points_within", "cd_cast_rays_all",
     "cd_sweep_points_all", "cd_sweep_points", "cd_pt_advance_points",
+    "cd_points_inside", "cd_signed_distance", "cd_column_tri_points",
 ]
 
 _lib = None
@@ -356,6 +364,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_sweep_points_all.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p, C.POINTER(CdSweepRows), C.POINTER(CdCcdInfo)]
     lib.cd_sweep_points.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CdPointInfo)]
     lib.cd_pt_advance_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
+    lib.cd_points_inside.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.POINTER(CdInsideInfo)]
+    lib.cd_signed_distance.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CdPointInfo)]
+    lib.cd_column_tri_points.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, vp, vp, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -775,6 +786,47 @@ class CollisionDetector:
         self._chk("cd_nearest_self", rc)
         return Nearest(faces, ids, dist, wa.take(n) if witness else None, info)
 
+    # ---- inside / outside and signed distance for points (cd_points_inside, cd_signed_distance)
+    def points_inside(self, points, axis: int = 2, parity: bool = False):
+        """cd_points_inside on the tree that is there.  points: [n, 3]; axis: the direction of the line through each point along which
+        the surface's crossings are counted.  -> (inside[n] (bool), n_above[n], n_below[n], w_above[n], w_below[n], info): the faces
+        that cover the point above / below it along the axis, each crossing owned by exactly one face, and the sums of their
+        orientations.  inside = w_above != 0 (the winding number), or with parity n_above odd.  On a closed, consistently oriented
+        mesh w_above + w_below == 0; a point where it is not had a hole or an open mesh on its line.  A contained object that
+        find_collisions_between cannot see:  body.points_inside(object_verts).all().
+        Points are walked in the order given, each along its whole line: keep spatially coherent points next to each other."""
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+        n = pts.shape[0]
+        inside = np.empty(n, dtype=np.uint8)
+        n_above = np.empty(n, dtype=np.uint32)
+        n_below = np.empty(n, dtype=np.uint32)
+        w_above = np.empty(n, dtype=np.int32)
+        w_below = np.empty(n, dtype=np.int32)
+        info = CdInsideInfo()
+        rc = self.lib.cd_points_inside(self._ctx, _ptr(pts), n, int(axis), CD_INSIDE_PARITY if parity else 0, _ptr(inside), _ptr(n_above), _ptr(n_below),
+                                       _ptr(w_above), _ptr(w_below), C.byref(info))
+        self._chk("cd_points_inside", rc)
+        return inside.astype(bool), n_above, n_below, w_above, w_below, info
+
+    def signed_distance(self, points, axis: int = 2, parity: bool = False):
+        """cd_signed_distance on the tree that is there.  points: [n, 3].  -> (sdist[n], face[n], ids[n], closest[n, 3], uv[n, 2],
+        feature[n], inside[n] (bool), info): closest_points' nearest triangle for every point with the distance negated where
+        points_inside(points, axis, parity) says inside (a distance of 0 stays +0); closest is the push-out target."""
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+        n = pts.shape[0]
+        sdist = np.empty(n, dtype=np.float64)
+        face = np.empty(n, dtype=np.uint32)
+        ids = np.empty(n, dtype=np.uint32)
+        closest = np.empty((n, 3), dtype=np.float64)
+        uv = np.empty((n, 2), dtype=np.float64)
+        feature = np.empty(n, dtype=np.uint8)
+        inside = np.empty(n, dtype=np.uint8)
+        info = CdPointInfo()
+        rc = self.lib.cd_signed_distance(self._ctx, _ptr(pts), n, int(axis), CD_INSIDE_PARITY if parity else 0, _ptr(sdist), _ptr(face), _ptr(ids),
+                                         _ptr(closest), _ptr(uv), _ptr(feature), _ptr(inside), C.byref(info))
+        self._chk("cd_signed_distance", rc)
+        return sdist, face, ids, closest, uv, feature, inside.astype(bool), info
+
     def find_collisions(self, cap: int = 1 << 20):
         return self._pairs_call(self.lib.cd_find_collisions, "cd_find_collisions", cap)
 
@@ -1098,6 +1150,25 @@ def pt_tri_points(points, tris):
     if rc != CD_OK:
         raise CdError("cd_pt_tri_points", rc)
     return dist, closest, uv, feature, side
+
+
+def column_tri_points(points, tris, axis: int = 2):
+    """column_tri (the per-pair predicate of cd_points_inside) on explicit operands, on the device (cd_column_tri_points): points
+    [n, 3], tris [n, 3, 3], axis 0..2 -> (cover[n] (int8: 0 / +1 / -1), above[n] (bool), E[n, 3], zc[n], S[n])."""
+    q = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+    p = np.ascontiguousarray(np.asarray(tris, dtype=np.float64).reshape(-1, 9))
+    if q.shape[0] != p.shape[0]:
+        raise ValueError(f"{q.shape[0]} points against {p.shape[0]} triangles")
+    n = q.shape[0]
+    cover = np.zeros(n, dtype=np.int8)
+    above = np.zeros(n, dtype=np.uint8)
+    E = np.zeros((n, 3), dtype=np.float64)
+    zc = np.zeros(n, dtype=np.float64)
+    S = np.zeros(n, dtype=np.float64)
+    rc = load_library().cd_column_tri_points(_ptr(q), _ptr(p), n, int(axis), _ptr(cover), _ptr(above), _ptr(E), _ptr(zc), _ptr(S))
+    if rc != CD_OK:
+        raise CdError("cd_column_tri_points", rc)
+    return cover, above.astype(bool), E, zc, S
 
 
 def pack_sweeps(p0, p1, dist) -> np.ndarray:

@@ -858,6 +858,64 @@ int cd_sweep_points(cd_ctx *ctx, const double *verts_end, const double *items, u
 int cd_pt_advance_points(const double *items, const double *tri, uint64_t n, double *toi, double *dist, double *closest, double *uv,
                          uint8_t *feature, uint8_t *side, uint32_t *evals);
 
+/* ---- inside / outside and signed distance for points (not reference behaviour) ----
+ * Is a point inside the closed surface this context's mesh forms?  The contained object that produces no colliding pair, a garment
+ * vertex that has passed through the body, the sign of a distance field.  A point is three finite doubles; axis (0, 1 or 2) picks the
+ * COLUMN, the line through the point parallel to that axis, along which the surface's crossings are counted.
+ * column_tri(p, c; triangle v0 v1 v2), FP64 with a fixed operation order and no contraction, every difference, product and sum
+ * rounded on its own (csrc/cd_math.h); a = (c + 1) % 3, b = (c + 2) % 3:
+ *   gate:  p_a within [min, max] of the three v_a and p_b within those of v_b, closed, exact comparisons; else the face does not cover;
+ *   edge l -> h:  la = l_a - p_a, lb = l_b - p_b, ha = h_a - p_a, hb = h_b - p_b, E = la hb - lb ha;
+ *          E0 = E(v1 -> v2), E1 = E(v2 -> v0), E2 = E(v0 -> v1);
+ *   the sign of an edge: that of E where E != 0; else that of l_b - h_b; else that of h_a - l_a (the input coordinates, compared
+ *          exactly); else 0 -- the sign E would have for p moved by (eps, eps^2) in (a, b);
+ *   cover: o = +1 when the three signs are +, -1 when they are -, else 0;
+ *   height: z_i = v_i,c - p_c, S = (E0 + E1) + E2, zc = (E0 z0 + E1 z1) + E2 z2; S == 0: not counted; above when (zc > 0 and S > 0) or
+ *          (zc < 0 and S < 0), else below (zc == 0, the point on the face, is below).  A NaN anywhere: not counted.
+ * Swapping an edge's ends negates E exactly and reverses both tie comparisons, so the two faces on an edge see opposite signs: a point
+ * exactly under an edge or a vertex is covered by the faces its moved copy is under and by no other -- one owner per crossing.  Where
+ * every computed E has its true sign or is a true zero the counts are exactly the moved point's.  The arithmetic is not exact: for a
+ * point within rounding of an edge's projection a sign can be wrong and a count off by one.
+ *
+ * cd_points_inside, per point k over the faces of this context: n_above[k] / n_below[k]: the faces counted above / below p;
+ * w_above[k] / w_below[k]: the sums of their o.  On a closed, consistently oriented mesh w_above + w_below == 0 and w_above is the
+ * winding number of p: +1 inside a body whose faces are counter-clockwise seen from outside, -1 inside an inverted one, 0 outside
+ * and between a shell and an inverted shell inside it.  inside[k] = w_above[k] != 0; with CD_INSIDE_PARITY inside[k] = n_above[k] odd,
+ * which needs no consistent orientation.  w_above[k] + w_below[k] != 0 tells the caller that the column passed through a hole or an
+ * open mesh: the answer for k then means nothing, and another axis may avoid the hole.  inside is required; the four count arrays
+ * may each be NULL.  info (may be NULL): points inside, boxes tested, column_tri evaluations -- numbers of this tree, not of the mesh.
+ *
+ * cd_signed_distance: cd_closest_points with rmax = +inf and cd_points_inside on the same points in one call, one host
+ * synchronisation.  sdist[k] = -dist when inside[k], else dist; a dist of 0 stays +0.  face, ids, closest, uv, feature: bit for bit
+ * cd_closest_points' values for k (|sdist[k]| its dist); inside: cd_points_inside's for this axis and these flags.  sdist is
+ * required, the rest may be NULL.  info (may be NULL): points that found a triangle, and the boxes tested and exact evaluations of
+ * both kernels together.
+ *
+ * Limits.  An open mesh (a cloth) has no inside.  A point ON the surface gets whichever side the arithmetic gives.  One lane walks
+ * its point's whole column through the mesh, and neighbours in the array share a wave: points that are neighbours in space should be
+ * neighbours in the array; the library does not sort them.
+ * Guarantee: the result depends on the mesh, the points, the axis and the flags only -- not on the Morton frame, CD_OPT_TRAVERSAL,
+ * CD_OPT_CELL_TABLE, the build variant or the order of the points.  Scaling mesh and points by 2^k changes no count while no nonzero
+ * product leaves the normal FP64 range.
+ * Needs a tree built from the current vertices (CD_ERR_ORDER otherwise, including after cd_update_vertices without a rebuild).
+ * CD_ERR_ARG: a NULL context; NULL points, inside (cd_points_inside) or sdist (cd_signed_distance) with n > 0; an axis outside 0..2;
+ * flags other than 0 / CD_INSIDE_PARITY; a non-finite coordinate -- checked on the host before anything is launched, and nothing is
+ * written then.  n = 0 returns CD_OK.  The calls leave cd_stats, the last pair list, the order hint, a captured CD_OPT_GRAPH step and
+ * every other query's buffers as they were; they keep device buffers of their own (grown on demand; cd_destroy frees them) and run on
+ * the context's stream with one host synchronisation. */
+enum { CD_INSIDE_PARITY = 1 };
+typedef struct cd_inside_info { uint64_t n_inside, node_visits, tri_tests; } cd_inside_info;
+int cd_points_inside(cd_ctx *ctx, const double *points /* n x 3 */, uint64_t n, int axis, int flags, uint8_t *inside,
+                     uint32_t *n_above, uint32_t *n_below, int32_t *w_above, int32_t *w_below, cd_inside_info *info);
+int cd_signed_distance(cd_ctx *ctx, const double *points /* n x 3 */, uint64_t n, int axis, int flags, double *sdist, uint32_t *face,
+                       uint32_t *ids, double *closest, double *uv, uint8_t *feature, uint8_t *inside, cd_point_info *info);
+/* column_tri on explicit operands (host pointers; no context): points is n x 3 doubles, tri n x 9 (v0, v1, v2), axis 0..2.  cover[k]:
+ * o (0 / +1 / -1, the gate included); above[k]: 1 when the face is counted above; E[3 k ..]: E0, E1, E2; zc[k], S[k].  A face with
+ * cover != 0 and above == 0 is counted below unless S == 0 or zc is NaN.  E, zc and S are computed whatever the gate says.  Every
+ * output except cover may be NULL.  No argument is checked for finiteness: the arithmetic decides.  The pin of the device function. */
+int cd_column_tri_points(const double *points, const double *tri, uint64_t n, int axis, int8_t *cover, uint8_t *above, double *E,
+                         double *zc, double *S);
+
 /* Library / build identification: "mi355cd <version> gfx950". */
 const char *cd_version(void);
 
