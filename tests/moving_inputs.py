@@ -15,10 +15,12 @@ import numpy as np
 
 import between_ref as br
 import ccd_ref as cr
+import column_ref as cref
 import isect_ref as ir
 import mi355_synth as synth
 import mi355cd
 import nearest_ref as nr
+import nearest_self_ref as ns
 import oracle
 import point_ref as ptr
 import proximity_ref as pr
@@ -29,6 +31,7 @@ import within_ref as wn
 import witness_ref as wr
 from test_between_gpu import _same_ccd as same_between_ccd, _same_contact as same_between_contact, _same_prox as same_between_prox  # noqa: F401
 from test_ccd_gpu import _same as _same_ccd
+from test_inside_gpu import _same as same_inside  # noqa: F401
 from test_points_gpu import _same as same_points
 from test_proximity_gpu import _same as _same_prox
 from test_rays_gpu import _same as same_rays  # noqa: F401
@@ -431,6 +434,71 @@ def want_self_sweep(name, f):
     return sw.sweep_rows_ref(s.frames[f], x1(name, f), s.vidx, None, items, skip=skip, counts=True)
 
 
+# ---------------------------------------------------------------- the mesh against itself and points inside it, frame by frame
+NEAREST_SELF_EDGES = 1.0        # cd_nearest_self's radius in edges of the frame: at least half of a frame's rows have a partner within it
+NEAREST_SELF_INF = {"scale_walk": (2, SCALE_WALK_OFFSET_FRAME), "collapse": (COLLAPSE_FRAMES[0], COLLAPSE_FRAMES[0] + 1)}
+UNDER_VERTICES = 300            # about that many of a frame's vertices get a point under them
+
+
+def nearest_self_r(name, f):
+    return NEAREST_SELF_EDGES * edge_at(name, f)
+
+
+@functools.lru_cache(maxsize=None)
+def want_nearest_self(name, f):
+    """(nearest_ref's NearestRows, played faces) of cd_nearest_self at rmax = nearest_self_r on frame f: the restatement of the proximity
+    witness rows at that distance (every pair on the tiny meshes, the grid's candidates elsewhere), reduced per face."""
+    s = seq(name)
+    w = wr.witness_pairs(s.frames[f], s.vidx, dist=nearest_self_r(name, f), brute=_brute(s))
+    return ns.reduce_pairs(s.nt, w.faces, w.pairs, w.dists, w.points, w.bary, w.feature)
+
+
+def has_nearest_self_inf(name, f):
+    """The frames whose rows at rmax = +inf are restated over all pairs: every frame of the tiny meshes; of the 1000-triangle soups
+    scale_walk's k = 60 and translated frames and collapse's collapsed frame and the one after it."""
+    return _brute(seq(name)) or f in NEAREST_SELF_INF.get(name, ())
+
+
+@functools.lru_cache(maxsize=None)
+def want_nearest_self_inf(name, f):
+    """The rows of cd_nearest_self at rmax = +inf on frame f: nearest_self_ref.nearest_rows, every admissible pair, no box, no bound."""
+    assert has_nearest_self_inf(name, f)
+    s = seq(name)
+    return ns.nearest_rows(s.frames[f], s.vidx, np.inf)
+
+
+def _under(name, f):
+    v = seq(name).frames[f]
+    return v[::max(1, len(v) // UNDER_VERTICES)]
+
+
+@functools.lru_cache(maxsize=None)
+def inside_points(name, f, axis):
+    """The points of cd_points_inside / cd_signed_distance on frame f: points(name, f), and behind them about UNDER_VERTICES of the
+    frame's vertices moved half an edge down the axis -- their other two coordinates are a vertex's exactly, so column_tri's tie rule
+    decides which face of that vertex owns the crossing."""
+    under = _under(name, f).copy()
+    under[:, axis] -= 0.5 * edge_at(name, f)
+    return np.ascontiguousarray(np.concatenate([points(name, f), under]))
+
+
+@functools.lru_cache(maxsize=None)
+def want_inside(name, f, axis, parity=False):
+    """column_ref.points_inside of inside_points(name, f, axis) on frame f: (inside, n_above, n_below, w_above, w_below), all faces."""
+    s = seq(name)
+    return cref.points_inside(inside_points(name, f, axis), s.frames[f], s.vidx, axis, parity)
+
+
+@functools.lru_cache(maxsize=None)
+def inside_tie_covers(name, f, axis):
+    """How many of the under-vertex points of inside_points(name, f, axis) are covered by a face with an exact zero among its three
+    E: the covers the tie rule decided."""
+    s = seq(name)
+    p = inside_points(name, f, axis)[NQ:]
+    r = cref.column_tri(p[:, None, :], s.frames[f][s.vidx.astype(np.int64)][None], axis)
+    return int(((r["cover"] != 0) & (r["E"] == 0).any(axis=-1)).any(axis=1).sum())
+
+
 def _pipeline(mode, v, vidx):
     if mode == "auto":
         off, span, lay = oracle.auto_frame(v, vidx)
@@ -721,6 +789,26 @@ def same_nearest(got, want: nr.NearestRows, what=""):
         _same_bytes(x, y, (what, k))
     found = int((want.faces[:, 0] != nr.NONE).sum())
     assert got.info.n_found == found, (what, got.info.n_found, found)
+
+
+def nearest_self_call(res):
+    """What cd_nearest_self with a witness returns for (rows, played faces)."""
+    rows, played = res
+    found = int((rows.faces[:, 0] != nr.NONE).sum())
+    return mi355cd.Nearest(rows.faces, rows.ids, rows.dist, mi355cd.Witness(played, rows.points, rows.bary, rows.feature), mi355cd.CdNearestInfo(found, 0, 0))
+
+
+def same_nearest_self(got, want, what=""):
+    """got: cd_nearest_self's Nearest with its witness; want: nearest_self_ref's (NearestRows, played faces).  test_nearest_self_gpu.py's
+    _same: faces, IDs, the bits of dist, played faces, points, barycentrics, features and n_found (that module imports this one, so
+    it is imported at the first call)."""
+    from test_nearest_self_gpu import _same
+    _same(got, want, what)
+
+
+def inside_call(want):
+    """What cd_points_inside returns for the restatement's five arrays."""
+    return tuple(want) + (mi355cd.CdInsideInfo(int(np.asarray(want[0]).sum()), 0, 0),)
 
 
 # ---------------------------------------------------------------- between two meshes

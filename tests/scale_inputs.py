@@ -1,4 +1,5 @@
-"""Meshes, motions and power-of-two scales for the range tests of the proximity and continuous collision queries.
+"""Meshes, motions and power-of-two scales for the range tests of the proximity and continuous collision queries, and the points of
+the inside query's (tests/test_inside_gpu.py; tests/test_column_ref.py pins column_ref.points_inside's equivariance over SCALES).
 
 Scaling every coordinate, dist and the motion by 2^k is exact in FP64 (no coordinate comes near the FP64 subnormal or overflow range
 for k in SCALES), and the restatements (tests/proximity_ref.py, tests/ccd_ref.py) are equivariant under it over that band: the same
@@ -14,6 +15,8 @@ on unscaled coordinates), and at |k| >~ 512 the rate bound L of the advancement 
 Results there follow those predicates, not the scaled k = 0 result.
 """
 from __future__ import annotations
+
+import functools
 
 import numpy as np
 
@@ -62,3 +65,32 @@ def motion(verts, edge, seed=7):
 def scaled(x, k):
     """x 2^k, exact for the arrays and scales used here."""
     return np.ldexp(np.asarray(x, dtype=np.float64), k)
+
+
+# ---------------------------------------------------------------- the inside query's points and restated answers (cached, never modified)
+INSIDE_RANDOM = 500
+
+
+@functools.lru_cache(maxsize=None)
+def _meshes():
+    return meshes()
+
+
+@functools.lru_cache(maxsize=None)
+def inside_points(name, axis):
+    """The points of the inside query on mesh `name` at k = 0: INSIDE_RANDOM uniform in its bounding box, then every tenth vertex moved
+    half an edge down the axis (its other two coordinates are the vertex's exactly: column_tri's tie rule decides).  Another scale
+    takes scaled() of these, never points of its own."""
+    v, _, edge = _meshes()[name]
+    g = np.random.default_rng(50 + axis)
+    under = v[::10].copy()
+    under[:, axis] -= edge / 2
+    return np.ascontiguousarray(np.concatenate([g.uniform(v.min(axis=0), v.max(axis=0), size=(INSIDE_RANDOM, 3)), under]))
+
+
+@functools.lru_cache(maxsize=None)
+def want_inside(name, axis, k=0, parity=False, shift=0.0):
+    """column_ref.points_inside of the points on the mesh, both translated by `shift` and then scaled by 2^k."""
+    import column_ref
+    v, vidx, _ = _meshes()[name]
+    return column_ref.points_inside(scaled(inside_points(name, axis) + shift, k), scaled(v + shift, k), vidx, axis, parity)

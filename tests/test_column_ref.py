@@ -1,11 +1,13 @@
 """The numpy restatement of column_tri and the per-point sums (tests/column_ref.py) against answers known in closed form, on the CPU:
 the unit box at lattice points that sit exactly under its vertices and edges, the torus against its analytic distance, nested and
-open boxes.  No exceptions are allowed: where the arithmetic is exact the counts are the moved point's."""
+open boxes.  No exceptions are allowed: where the arithmetic is exact the counts are the moved point's.  And its equivariance under
+powers of two over tests/scale_inputs.SCALES, which the device's range test (tests/test_inside_gpu.py) rests on."""
 import numpy as np
 import pytest
 
 import closed_meshes as cm
 import column_ref as ref
+import scale_inputs as si
 
 AXES = (0, 1, 2)
 
@@ -104,3 +106,27 @@ def test_ties_and_degenerate_faces():
     assert int(r["cover"]) == 1 and not bool(r["counted"]) and not bool(r["above"])
     on = ref.column_tri(np.array([0.25, 0.25, 1.0]), tri, 2)                          # the point ON the face is below
     assert int(on["cover"]) == 1 and bool(on["counted"]) and not bool(on["above"])
+
+
+@pytest.mark.parametrize("axis", AXES)
+@pytest.mark.parametrize("name", list(si.meshes()))
+def test_points_inside_is_equivariant_under_powers_of_two(name, axis):
+    """scale_inputs' meshes and inside points times 2^k for every k of SCALES: the same five integer arrays as at k = 0, also with
+    parity (no E, S or zc over- or underflows in FP64 over that band, so every sign and every exact zero is the unscaled one's).
+    A condition on the inputs: at least 200 of the points have a face over or under them, and some cover is the tie rule's."""
+    v, vidx, edge = si.meshes()[name]
+    pts = si.inside_points(name, axis)
+    want = si.want_inside(name, axis)
+    crossed = int(((want[1] + want[2]) > 0).sum())
+    under = pts[si.INSIDE_RANDOM:]
+    r = ref.column_tri(under[:, None, :], v[vidx.astype(np.int64)][None], axis)
+    ties = int(((r["cover"] != 0) & (r["E"] == 0).any(axis=-1)).any(axis=1).sum())
+    print(f"{name} axis {axis}: {pts.shape[0]} points, {crossed} with a face over or under them, {int(want[0].sum())} inside, {ties} covers by the tie rule")
+    assert pts.shape[0] == si.INSIDE_RANDOM + (v.shape[0] + 9) // 10 and crossed >= 200 and ties > 0
+    for k in si.SCALES:                                                          # every scale, on every mesh and axis: none is left out
+        got = si.want_inside(name, axis, k)
+        for j, (g, w) in enumerate(zip(got, want)):
+            assert g.dtype == w.dtype and np.array_equal(g, w), (name, axis, k, j, int((g != w).sum()))
+        if k in si.EDGES:
+            for g, w in zip(si.want_inside(name, axis, k, True), si.want_inside(name, axis, 0, True)):
+                assert np.array_equal(g, w), (name, axis, k, "parity")

@@ -11,6 +11,7 @@ import pytest
 import closed_meshes as cm
 import column_ref as ref
 import mi355cd
+import scale_inputs as si
 
 pytestmark = pytest.mark.gpu
 
@@ -264,6 +265,64 @@ def test_scaled_by_a_power_of_two(name, k):
             _same(cd.points_inside(np.ldexp(_points(name, axis), k), axis), _want(name, axis), f"{name} 2^{k} axis {axis}")
 
 
+# ---------------------------------------------------------------- the fp32 range
+SCALE_MESHES = si.meshes()
+FRAMES = ((mi355cd.CD_FRAME_REFERENCE, "reference"), (mi355cd.CD_FRAME_AUTO, "auto"))
+SHIFT = 2.0 ** 20 + 0.37
+
+
+def _run_all(cd, pts, want, want_parity, parity_axis, what):
+    """Both cell-table settings and the Morton frames, on the tree cd_self_collide builds for each (test_query_scales_gpu.py's _run_all).
+    pts: the points per axis; want: per axis the lists of restated answers the device must equal (the same integers in each);
+    want_parity: the restated answer with parity on parity_axis."""
+    for table in (1, 0):
+        cd.set_option(mi355cd.CD_OPT_CELL_TABLE, table)
+        for frame, fname in FRAMES:
+            w = f"{what} table={table} frame={fname}"
+            cd.set_morton_frame(frame)
+            assert cd.self_collide(cap=CAP)[2] == mi355cd.CD_OK, w
+            for axis in AXES:
+                got = cd.points_inside(pts[axis], axis)
+                for j, ww in enumerate(want[axis]):
+                    _same(got, ww, f"{w} axis {axis} restatement {j}")
+                sd = cd.signed_distance(pts[axis], axis)
+                assert np.array_equal(sd[6], want[axis][0][0]), f"{w} axis {axis} signed distance"
+                assert np.array_equal(_bits(np.abs(sd[0])), _bits(cd.closest_points(pts[axis])[2])), f"{w} axis {axis} |sdist|"
+                assert np.array_equal(np.signbit(sd[0]), sd[6] & (np.abs(sd[0]) > 0)), f"{w} axis {axis} sign"
+            _same(cd.points_inside(pts[parity_axis], parity_axis, parity=True), want_parity, f"{w} axis {parity_axis} parity")
+
+
+@pytest.mark.parametrize("k", si.SCALES)
+@pytest.mark.parametrize("name", list(SCALE_MESHES))
+def test_fp32_range(name, k):
+    """tests/scale_inputs.py's meshes and inside points scaled by 2^k, past FLT_MAX (stored bounds of +-inf) and below the smallest
+    fp32 subnormal (all +-0): the k = 0 restatement's integers on every axis (tests/test_column_ref.py: the restatement is
+    equivariant there), and at si.EDGES the restatement on the scaled inputs itself; parity on one axis; cd_signed_distance's inside
+    and the bits of its |sdist| against cd_closest_points."""
+    v, vidx, edge = SCALE_MESHES[name]
+    verts = si.scaled(v, k)
+    if k >= 128:                                                                 # the range end is really reached: the FLT_MAX cell is ambiguous
+        for a in AXES:
+            assert np.unique(verts[np.abs(verts[:, a]) > si.FLT_MAX, a]).size >= 2, (name, k, a)
+    pts = [si.scaled(si.inside_points(name, a), k) for a in AXES]
+    want = [[si.want_inside(name, a)] + ([si.want_inside(name, a, k)] if k in si.EDGES else []) for a in AXES]
+    pa = k % 3
+    with mi355cd.CollisionDetector(verts, vidx) as cd:
+        _run_all(cd, pts, want, si.want_inside(name, pa, 0, True), pa, f"{name} k={k}")
+
+
+@pytest.mark.parametrize("name", list(SCALE_MESHES))
+def test_translated_by_2_pow_20(name):
+    """World coordinates: mesh and points translated by 2^20 + 0.37 (the pad 2^-20 max(M, |p|) is then several edges wide, and the
+    points under a vertex still have its other two coordinates exactly), against the restatement on the translated inputs."""
+    v, vidx, edge = SCALE_MESHES[name]
+    pts = [si.inside_points(name, a) + SHIFT for a in AXES]
+    want = [[si.want_inside(name, a, 0, False, SHIFT)] for a in AXES]
+    assert all(int(((w[0][1] + w[0][2]) > 0).sum()) >= 200 for w in want), name
+    with mi355cd.CollisionDetector(v + SHIFT, vidx) as cd:
+        _run_all(cd, pts, want, si.want_inside(name, 1, 0, True, SHIFT), 1, f"{name} translated")
+
+
 # ---------------------------------------------------------------- the signed distance
 @pytest.mark.parametrize("axis", AXES)
 def test_signed_distance_is_closest_points_with_the_sign(axis):
@@ -320,7 +379,8 @@ def _raw(lib, ctx, pts, axis, flags):
     sd = np.full(n + 4, -7.0)
     pinfo = mi355cd.CdPointInfo(5, 5, 5)
     rc2 = lib.cd_signed_distance(ctx, pts.ctypes.data if n else None, n, axis, flags, sd.ctypes.data, None, None, None, None, None, out[0].ctypes.data, C.byref(pinfo))
-    untouched = all((a == 7).all() for a in out) and (sd == -7.0).all() and info.n_inside == 5 and pinfo.n_found == 5
+    untouched = all((a == 7).all() for a in out) and (sd == -7.0).all() and (info.n_inside, info.node_visits, info.tri_tests) == (5, 5, 5) \
+        and (pinfo.n_found, pinfo.node_visits, pinfo.tri_tests) == (5, 5, 5)
     return rc, rc2, untouched
 
 

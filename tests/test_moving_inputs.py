@@ -3,7 +3,9 @@ answers, each sequence does what it is named for, and every comparison helper of
 frame f - 1's expected result against frame f's (the planted error: a device that kept the previous frame's state), and the
 comparisons of the witness, contour, nearest-triangle, all-within, every-hit and swept-point rows also when one field of one row of the
 right frame's result is changed.  The conditions the all-results and swept-point queries need of their items -- items without a row,
-items with several, contacts strictly inside the step, a block that overflows its shard -- are asserted here too."""
+items with several, contacts strictly inside the step, a block that overflows its shard -- are asserted here too.  So are those of
+the self-nearest and inside references: rows with a partner, points with a face over them, points inside, covers the tie rule decided;
+and the two routes to the self-nearest rows (the reduced proximity restatement, all pairs cut to the radius) agree column by column."""
 from __future__ import annotations
 
 import numpy as np
@@ -11,6 +13,7 @@ import pytest
 
 import moving_inputs as mi
 import nearest_ref as nr
+import nearest_self_ref as ns
 import oracle
 import proximity_ref as pr
 import scale_inputs as si
@@ -319,6 +322,130 @@ def test_the_growth_block_has_more_rows_than_a_shard_of_the_first_candidate_buff
     print("jitter's growth block: rows (all within, swept points, swept points at rest)", figures, "of", mi.mi355cd.WITHIN_SHARD_FIRST, "slots")
     for g in range(len(mi.seq("jitter"))):                                      # no other frame has the block: its buffers stay as the dense frame left them
         assert (mi.within_items("jitter", g)[0].shape[0] == mi.NQ) == (mi.sweep_items("jitter", g).shape[0] == mi.NQ) == (g != f)
+
+
+# ---------------------------------------------------------------- the mesh against itself and points inside it
+def _found(res):
+    return res[0].faces[:, 0] != ns.NONE
+
+
+@pytest.mark.parametrize("name", mi.NAMES)
+def test_nearest_self_and_inside_comparisons_raise_on_the_previous_frames_result(name):
+    """cd_nearest_self (rows and CD_NEAREST_MIN, at an edge and at +inf) and cd_points_inside (three axes, and parity): same_nearest_self
+    and same_inside pass on the frame's own restatement and raise on the one of the frame before it.  cd_signed_distance is held to
+    want_inside's first array, so the same holds for it."""
+    s = mi.seq(name)
+    min_rows_that_change = 0
+    for f in range(1, len(s)):
+        what = f"{name} frame {f}"
+        sets = [(mi.want_nearest_self(name, f - 1), mi.want_nearest_self(name, f))]
+        before = [k for k in range(f) if mi.has_nearest_self_inf(name, k)]     # (the last frame before this one that has the rows at +inf)
+        if mi.has_nearest_self_inf(name, f) and before:
+            sets.append((mi.want_nearest_self_inf(name, before[-1]), mi.want_nearest_self_inf(name, f)))
+        for w0, w1 in sets:
+            mi.same_nearest_self(mi.nearest_self_call(w1), w1, what)
+            mi.same_nearest_self(mi.nearest_self_call(ns.nearest_min(w1)), ns.nearest_min(w1), what)
+            if _found(w0).any() or _found(w1).any():                            # (tiny1 has no pair at all)
+                with pytest.raises(AssertionError):
+                    mi.same_nearest_self(mi.nearest_self_call(w0), w1, what)
+            # the MIN row of a mesh in contact is the pair in contact with the smallest IDs, with no witness: the same row in both frames
+            # where that pair stays in contact
+            m0, m1 = ns.nearest_min(w0), ns.nearest_min(w1)
+            if any(x.tobytes() != y.tobytes() for x, y in zip(m0[0] + (m0[1],), m1[0] + (m1[1],))):
+                min_rows_that_change += 1
+                with pytest.raises(AssertionError):
+                    mi.same_nearest_self(mi.nearest_self_call(m0), m1, what)
+        for axis, parity in ((0, False), (1, False), (2, False), ((f + s.seed) % 3, True)):
+            w0, w1 = mi.want_inside(name, f - 1, axis, parity), mi.want_inside(name, f, axis, parity)
+            assert mi.inside_points(name, f, axis).shape == mi.inside_points(name, f - 1, axis).shape
+            mi.same_inside(mi.inside_call(w1), w1, what)
+            crossed = lambda w: int(((w[1] + w[2]) > 0).sum())
+            if name in mi.LARGE or crossed(w0) + crossed(w1) >= 8:              # (a handful of triangles: few of the points have one over them)
+                with pytest.raises(AssertionError):
+                    mi.same_inside(mi.inside_call(w0), w1, what)
+                with pytest.raises(AssertionError):                             # the first array alone: what the signed distance is held to
+                    assert np.array_equal(w0[0], w1[0])
+    assert min_rows_that_change > 0 or s.nt == 1, name
+
+
+def test_one_corrupted_field_of_a_nearest_self_row_or_an_inside_count_raises():
+    name, f = "collapse", 1
+    res = mi.want_nearest_self(name, f)
+    k = int(np.flatnonzero(_found(res) & (res[0].feature != wr.FEATURE_NONE).all(axis=1))[100])
+    for field, bad in _corrupted_nearest(res[0], k).items():
+        with pytest.raises(AssertionError):
+            mi.same_nearest_self(mi.nearest_self_call((bad, res[1])), res, field)
+    played = res[1].copy()
+    played[k] = played[k, ::-1]
+    with pytest.raises(AssertionError):
+        mi.same_nearest_self(mi.nearest_self_call((res[0], played)), res, "played faces exchanged")
+    with pytest.raises(AssertionError):                                         # n_found alone
+        mi.same_nearest_self(mi.nearest_self_call(res)._replace(info=mi.mi355cd.CdNearestInfo(0, 0, 0)), res, "n_found")
+    want = mi.want_inside(name, f, 1)
+    k = int(np.flatnonzero(want[1] > 0)[10])
+    for j in range(5):
+        bad = [a.copy() for a in want]
+        bad[j][k] = not bad[j][k] if j == 0 else bad[j][k] + 1
+        with pytest.raises(AssertionError):
+            mi.same_inside(mi.inside_call(bad), want, j)
+    with pytest.raises(AssertionError):                                         # n_inside alone
+        mi.same_inside(want + (mi.mi355cd.CdInsideInfo(int(want[0].sum()) + 1, 0, 0),), want, "n_inside")
+
+
+def test_reduced_proximity_rows_are_the_all_pairs_rows_within_the_radius():
+    """want_nearest_self -- the proximity witness restatement at one edge, reduced per face -- is nearest_self_ref.within of the brute
+    force over every admissible pair, column by column, on every frame that has the brute force; and its minimum is the clearance
+    wherever it finds a row (what the GPU test takes for CD_NEAREST_MIN at +inf on the other frames)."""
+    frames = [(name, f) for name in mi.NAMES for f in range(len(mi.seq(name))) if mi.has_nearest_self_inf(name, f)]
+    assert sum(name in mi.LARGE for name, f in frames) == 4 and len(frames) == 4 + 4 * len(mi.TINY)
+    assert all(mi.seq(name).nt <= 1000 for name, f in frames)
+    assert mi.SCALE_WALK_K[mi.NEAREST_SELF_INF["scale_walk"][0]] == 60 and mi.NEAREST_SELF_INF["scale_walk"][1] == mi.SCALE_WALK_OFFSET_FRAME
+    assert mi.NEAREST_SELF_INF["collapse"] == (mi.COLLAPSE_FRAMES[0], mi.COLLAPSE_FRAMES[0] + 1)
+    for name, f in frames:
+        every, got = mi.want_nearest_self_inf(name, f), mi.want_nearest_self(name, f)
+        want = ns.within(every, mi.nearest_self_r(name, f))
+        for k, x, y in zip(every[0]._fields + ("played",), got[0] + (got[1],), want[0] + (want[1],)):
+            mi._same_bytes(x, y, (name, f, k))
+        if _found(got).any():
+            mi.same_nearest_self(mi.nearest_self_call(ns.nearest_min(got)), ns.nearest_min(every), (name, f))
+
+
+def test_nearest_self_and_inside_references_cannot_pass_vacuously():
+    """Conditions, for every LARGE sequence, frame and axis: of the about 1300 inside points at least 200 have a face over or under
+    them and at least 100 are inside; at least 30 of the under-vertex points are covered by a face with an exact zero of E (the tie
+    rule decided); want_nearest_self finds a partner for at least half of the rows."""
+    low = dict(crossed=(1 << 30,), inside=(1 << 30,), ties=(1 << 30,), partner=(2.0,))
+    for name in mi.LARGE:
+        s = mi.seq(name)
+        for f in range(len(s)):
+            found = int(_found(mi.want_nearest_self(name, f)).sum())
+            assert 2 * found >= s.nt, (name, f, found)
+            low["partner"] = min(low["partner"], (found / s.nt, found, s.nt, name, f))
+            for axis in range(3):
+                p = mi.inside_points(name, f, axis)
+                inside, na, nb, wa, wb = mi.want_inside(name, f, axis)
+                crossed, ties = int(((na + nb) > 0).sum()), mi.inside_tie_covers(name, f, axis)
+                assert mi.NQ + 250 <= p.shape[0] <= mi.NQ + 350 and np.array_equal(p[:mi.NQ], mi.points(name, f)), (name, f, axis)
+                under = p[mi.NQ:]
+                v = s.frames[f][::max(1, s.frames[f].shape[0] // mi.UNDER_VERTICES)]
+                rest = [a for a in range(3) if a != axis]
+                assert np.array_equal(_bits(under[:, rest]), _bits(v[:, rest])) and (under[:, axis] < v[:, axis]).all(), (name, f, axis)
+                assert crossed >= 200 and int(inside.sum()) >= 100 and ties >= 30, (name, f, axis, crossed, int(inside.sum()), ties)
+                for k, x in (("crossed", crossed), ("inside", int(inside.sum())), ("ties", ties)):
+                    low[k] = min(low[k], (x, name, f, axis))
+    print("the smallest over every LARGE sequence, frame and axis:", low)
+    v, f0 = mi.want_inside("jitter", 1, 1, True), mi.want_inside("jitter", 1, 1)     # parity is another answer on these open meshes
+    assert not np.array_equal(v[0], f0[0]) and all(np.array_equal(a, b) for a, b in zip(v[1:], f0[1:]))
+
+
+def test_tiny_sequences_have_nearest_self_rows_and_crossings_in_some_frame():
+    for n in mi.TINY:
+        name = f"tiny{n}"
+        frames = range(len(mi.seq(name)))
+        rows = [int(_found(mi.want_nearest_self_inf(name, f)).sum()) for f in frames]
+        crossed = [sum(int(((w[1] + w[2]) > 0).sum()) for w in (mi.want_inside(name, f, axis) for axis in range(3))) for f in frames]
+        print(f"{name}: nearest-self rows with a partner a frame {rows}, inside points with a face over or under them (three axes) {crossed}")
+        assert rows == [0 if n == 1 else n] * len(frames) and max(crossed) > 0, (name, rows, crossed)
 
 
 def test_between_comparisons_raise_on_the_previous_frames_result():

@@ -21,12 +21,26 @@ bytes after the sweeps as before them.  On jitter's dense frame one whole 64-ite
 shard of the first candidate buffer holds (WITHIN_SHARD_FIRST): the pass grows the buffer and runs again, with CD_OK and the exact rows,
 and the sparse frames after it run on the grown buffers.
 
+And the mesh against itself and the points inside it: cd_nearest_self ("nearest self": per triangle and CD_NEAREST_MIN at a radius of one
+edge, against the proximity witness restatement of that frame reduced per face; at +inf byte for byte against the fresh context,
+against nearest_self_ref's all-pairs rows on the frames that have them, and elsewhere its MIN row against the radius' -- the clearance
+is within an edge), cd_points_inside ("inside": the frame's points and 300 of its vertices moved half an edge down the axis, where
+column_tri's tie rule decides, on all three axes and with parity on axis (f + seed) % 3, against column_ref's sums over all faces: the
+five arrays and n_inside) and cd_signed_distance ("signed distance": on that axis, inside from the restatement, everything else the
+device's own cd_closest_points answer byte for byte, the sign where inside and dist > 0) are in the permuted list too.  They read
+recs32, root, leaf, the vertices, the root box for the pad, the sort's flags, and cd_nearest_self perm[0] and the Morton neighbours:
+whatever an entry leaves stale of those shows here.  Between cd_update_vertices and the entry all three (and CD_NEAREST_MIN) return
+CD_ERR_ORDER and write nothing.  Their node_visits and tri_tests are compared with nothing (tiny1's node_visits of
+cd_points_inside is 0: there is no record to walk).
+
 Counters that are NOT compared with the fresh context's: node_visits and tri_tests of cd_cast_rays / cd_closest_points /
-cd_sweep_points / cd_nearest_between (the last also not with a restatement: nearest_ref has no walk), and the collision step's node_visits and
+cd_sweep_points / cd_nearest_between / cd_nearest_self / cd_points_inside / cd_signed_distance (cd_nearest_between and cd_nearest_self
+also not with a restatement: nearest_ref has no walk), and the collision step's node_visits and
 wave_steps -- they count the walk, which may legitimately differ with the options the entry left behind (traversal bookkeeping, the
 order hint; cd_nearest_between's shared bound makes them differ from run to run: test_nearest_gpu.py).  pairs_tested of a collision step is
 compared with the oracle's, proximity's and CCD's evaluation counts with the restatement's and the fresh context's, n_candidates with
 swept_ref's count and the fresh context's, the contour calls' n_tested with isect_ref's, cd_nearest_between's n_found with nearest_ref's;
+cd_nearest_self's n_found and cd_points_inside's n_inside with their restatements' and the fresh context's;
 within_tested and rays_all_tested with the fresh context's; cd_sweep_points_all's n_tested, n_evals and n_unresolved with sweep_ref's counts
 and the fresh context's, its n_candidates -- a function of the swept records and the items -- with the fresh context's."""
 from __future__ import annotations
@@ -39,13 +53,17 @@ import pytest
 import ccd_ref as cr
 import mi355cd
 import moving_inputs as mi
+import nearest_self_ref as ns
 import proximity_ref as pr
 import swept_ref as sr
 import within_ref as wn
+from test_inside_gpu import _raw as raw_inside
+from test_nearest_self_gpu import _raw as raw_nearest_self, _untouched as untouched_nearest_self
 
 pytestmark = pytest.mark.gpu
 
 CAP = 1 << 20
+INF = float("inf")
 ENTRIES = ("build_tree", "self_collide", "graph", "self_proximity", "self_ccd", "stagewise")
 FRAME = {"reference": mi355cd.CD_FRAME_REFERENCE, "auto": mi355cd.CD_FRAME_AUTO}
 
@@ -275,9 +293,53 @@ def _queries(cd, fresh, name, f, entry=None):
             _equal_bytes(before[:3], after[:3], what + " the CCD pass's swept tree after the sweeps")
             assert before[3] == after[3] and sr.bits1(before[4]) == sr.bits1(after[4]), what
 
+    def nearest_self():
+        r, want = mi.nearest_self_r(name, f), mi.want_nearest_self(name, f)
+        least = ns.nearest_min(want)
+        mi.same_nearest_self(cd.nearest_self(r, witness=True), want, what + " nearest self")
+        mi.same_nearest_self(cd.nearest_self(r, minimum=True, witness=True), least, what + " nearest self, MIN")
+        flat = lambda g: (g.faces, g.ids, g.dist, g.witness.faces, g.witness.points, g.witness.bary, g.witness.feature)
+        rows, one = cd.nearest_self(INF, witness=True), cd.nearest_self(INF, minimum=True, witness=True)
+        for got, minimum in ((rows, False), (one, True)):
+            gf = fresh.nearest_self(INF, minimum=minimum, witness=True)
+            _equal_bytes(flat(got), flat(gf), f"{what} nearest self at +inf{', MIN' if minimum else ''} against the fresh context")
+            assert got.info.n_found == gf.info.n_found, (what, got.info.n_found, gf.info.n_found)
+        if mi.has_nearest_self_inf(name, f):
+            every = mi.want_nearest_self_inf(name, f)
+            mi.same_nearest_self(rows, every, what + " nearest self at +inf")
+            mi.same_nearest_self(one, ns.nearest_min(every), what + " nearest self at +inf, MIN")
+        else:                                                                   # the clearance is within the radius, so it is the radius' MIN row
+            assert least[0].faces[0, 0] != ns.NONE, what
+            mi.same_nearest_self(one, least, what + " nearest self at +inf, MIN")
+
+    turn = (f + s.seed) % 3                                                     # the axis of the parity call and of the signed distance
+
+    def inside():
+        for axis, parity in ((0, False), (1, False), (2, False), (turn, True)):
+            w = f"{what} inside, axis {axis}{', parity' if parity else ''}"
+            p = mi.inside_points(name, f, axis)
+            got = cd.points_inside(p, axis, parity=parity)
+            mi.same_inside(got, mi.want_inside(name, f, axis, parity), w)
+            gf = fresh.points_inside(p, axis, parity=parity)
+            _equal_bytes(got[:5], gf[:5], w + " against the fresh context")
+            assert got[5].n_inside == gf[5].n_inside, (w, got[5].n_inside, gf[5].n_inside)
+            if s.nt == 1:                                                       # no record to walk
+                assert got[5].node_visits == 0, (w, got[5].node_visits)
+
+    def signed_distance():
+        p = mi.inside_points(name, f, turn)
+        sdist, face, ids, closest, uv, feature, ins, info = cd.signed_distance(p, turn)
+        near = cd.closest_points(p)                                             # (pinned by point_queries)
+        w = f"{what} signed distance, axis {turn}"
+        assert np.array_equal(ins, mi.want_inside(name, f, turn)[0]), w
+        _equal_bytes((face, ids, np.abs(sdist), closest, uv, feature), near[:6], w + " against closest_points")
+        assert np.array_equal(np.signbit(sdist), ins & (near[2] > 0)), w
+        assert info.n_found == p.shape[0], (w, info.n_found)
+
     return [("proximity", proximity), ("ccd", ccd), ("rays", ray_queries), ("points", point_queries), ("root box", box),
             ("proximity witness", proximity_witness), ("ccd witness", ccd_witness), ("contour", contour),
-            ("all within", all_within), ("every hit", every_hit), ("swept points", swept_points)]
+            ("all within", all_within), ("every hit", every_hit), ("swept points", swept_points),
+            ("nearest self", nearest_self), ("inside", inside), ("signed distance", signed_distance)]
 
 
 def _swept(cd):
@@ -287,6 +349,22 @@ def _swept(cd):
     except mi355cd.CdError as e:
         assert e.rc == mi355cd.CD_ERR_ORDER
         return None
+
+
+def _order_errors_self(cd, pts, rmax):
+    """The vertices moved and the tree was not rebuilt: cd_nearest_self (both flags), cd_points_inside and cd_signed_distance return
+    CD_ERR_ORDER and write nothing -- not a row of the canary-filled outputs, not a field of the info structs."""
+    lib, E = cd.lib, mi355cd.CD_ERR_ORDER
+    info = mi355cd.CdNearestInfo(5, 5, 5)
+    for r in (rmax, INF):
+        for flags in (0, mi355cd.CD_NEAREST_MIN):
+            rc, arr = raw_nearest_self(lib, cd._ctx, r, flags, cd.nt, info=info)
+            assert rc == E, (r, flags, rc)
+            untouched_nearest_self(arr)
+    assert (info.n_found, info.node_visits, info.tri_tests) == (5, 5, 5)
+    for axis in (0, 1, 2):
+        for flags in (0, mi355cd.CD_INSIDE_PARITY):
+            assert raw_inside(lib, cd._ctx, pts, axis, flags) == (E, E, True), (axis, flags)
 
 
 def _new(verts, vidx, mode):
@@ -307,6 +385,7 @@ def _run(name, schedule):
                 for _ in range(70):
                     cd.build_tree()
             cd.update_vertices(v)
+            _order_errors_self(cd, mi.inside_points(name, f, 2), mi.nearest_self_r(name, f))
             _rebuild(cd, entry, name, f)
             used.append(entry)
             if name == "frame_exit":
