@@ -422,9 +422,15 @@ __global__ __launch_bounds__(MORTON_THREADS) void k_morton(const double *__restr
                                                            const double *__restrict__ partial /* auto frame: k_centroid_bounds' per-block bounds, else NULL */, uint32_t nparts,
                                                            double *__restrict__ frame_out, double *__restrict__ box_out /* NULL, or the box of all vertices (partials of k_centroid_bounds<true>) */,
                                                            uint32_t *__restrict__ tile_hist /* [tiles][256]: per SORT_TILE keys, the counts of digit `first_digit` -- the first global pass of the sort
-                                                                                              takes its tile offsets from these (no look-back: k_os_pass) */)
+                                                                                              takes its tile offsets from these (no look-back: k_os_pass) */,
+                                                           int cell_shift /* the hybrid forms: the sort's 16 global bits are key bits [cell_shift, cell_shift + 16) -- a "cell"; < 0: no cells (the other forms) */,
+                                                           uint32_t *__restrict__ cell_hist /* NULL, or [CELLS]: the keys per cell, for the cell form of the global stage (cd_sort.h, k_cell_scatter) */,
+                                                           uint32_t *__restrict__ cell_stat /* the cell changes among every wave's 64 consecutive keys (cd_sort.h cell_count), summed over the waves: what the host chooses the form by */)
 {
     __shared__ uint32_t h[8][RADIX];
+    __shared__ uint32_t s_changes;
+    if (threadIdx.x == 0) s_changes = 0u;
+    uint32_t changes = 0;                                // (wave-uniform)
     __shared__ double smw[MORTON_THREADS / 64][BOUNDS_STRIDE];
     __shared__ double sframe[FRAME_WORDS], sbox[6];
     for (int i = threadIdx.x; i < 8 * RADIX; i += MORTON_THREADS) (&h[0][0])[i] = 0;
@@ -456,8 +462,8 @@ __global__ __launch_bounds__(MORTON_THREADS) void k_morton(const double *__restr
 #pragma unroll
         for (int it = 0; it < SORT_TILE / MORTON_THREADS; ++it) {
             const uint32_t t = tile * SORT_TILE + it * MORTON_THREADS + threadIdx.x;
+            uint64_t k = 0;
             if (t < n) {
-                uint64_t k;
                 if constexpr (LAYOUT) {                                   // (the host launches this instance only for a frame WITH a layout: an auto frame, or cd_set_morton_frame_layout's)
                     const uint32_t ia = vidx[3 * (size_t)t], ib = vidx[3 * (size_t)t + 1], ic = vidx[3 * (size_t)t + 2];
                     const d3 p1 = load_vertex(verts, ia), p2 = load_vertex(verts, ib), p3 = load_vertex(verts, ic);
@@ -467,6 +473,7 @@ __global__ __launch_bounds__(MORTON_THREADS) void k_morton(const double *__restr
                 hist_add(h, k, first_digit, down);
                 above |= k;
             }
+            if (cell_shift >= 0) changes += cell_count((uint32_t)(k >> cell_shift) & (uint32_t)(CELLS - 1), t < n, cell_hist);      // (uniform)
         }
         __syncthreads();
         if (threadIdx.x < RADIX) { const uint32_t now = h[first_digit][threadIdx.x]; tile_hist[(size_t)tile * RADIX + threadIdx.x] = now - seen; seen = now; }
@@ -475,7 +482,9 @@ __global__ __launch_bounds__(MORTON_THREADS) void k_morton(const double *__restr
     // a centroid outside the Morton frame sets key bits the shifted digits do not cover (bits 64 - down .. 63): the
     // shifted hybrid sort then does not apply -- same flag, same repair (the next form) as a run too long to window
     if (down && (above >> (64 - down))) atomicOr(overflow, SORTF_ABOVE);   // a key beyond the shifted digits -- the mesh has left the frame (cd_sort.h: the flag word's bits)
+    if (cell_shift >= 0 && (threadIdx.x & 63) == 0) atomicAdd(&s_changes, changes);
     __syncthreads();
+    if (cell_shift >= 0 && threadIdx.x == 0) atomicAdd(cell_stat, s_changes);
     for (int i = threadIdx.x + first_digit * RADIX; i < 8 * RADIX; i += MORTON_THREADS) {
         const uint32_t v = (&h[0][0])[i];
         if (v) atomicAdd(&ghist[(size_t)(blockIdx.x & (HIST_COPIES - 1)) * HIST_STRIDE + i], v);
@@ -543,7 +552,7 @@ __global__ __launch_bounds__(256) void k_sort_fixup_fill(const uint64_t *__restr
     uint32_t pos;
     // run too long: flag it (the host redoes the sort with 8 passes) but still emit a VALID permutation and valid
     // leaves -- the rest of the fused pipeline runs on this output before the host sees the flag
-    if (!fixup_position(keys_in, n, i, k0, pos)) { atomicOr(overflow, SORTF_FIXUP); pos = i; }
+    if (!fixup_position(keys_in, vals_in, n, i, k0, t, pos)) { atomicOr(overflow, SORTF_FIXUP); pos = i; }
     keys_out[pos] = k0;
     vals_out[pos] = t;
     fill_leaf(pos, t, vidx, ids, n, leaf, parent, bounded, nullptr);

@@ -3,7 +3,10 @@
 // offsets by decoupled look-back), 4 passes + a fix-up hop in half-key mode or 8 passes.  Stability inside a tile
 // comes from wave-level match masks (__ballot over the 8 digit bits, rank = popcount of lower matching lanes),
 // per-wave digit counters in LDS and a cross-wave prefix; no atomics on the data path, so the result is the
-// unique stable ascending order (ties keep original index order), run to run identical.
+// unique stable ascending order (ties keep original index order), run to run identical.  (The cell form of the hybrid
+// sort's global stage, k_cell_scatter below, does place keys by atomics: the order it leaves inside a run of equal global
+// bits is arbitrary, and k_local_sort, which orders every run completely and breaks full-key ties by value, makes the
+// same unique order of it.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -150,6 +153,7 @@ __global__ __launch_bounds__(RADIX) void k_tile_chunks(const uint32_t *__restric
 #ifndef OS_WAVES_PER_EU
 #define OS_WAVES_PER_EU 8
 #endif
+__device__ __forceinline__ void cell_stat_turn(uint32_t *__restrict__ stat);
 // (68 VGPRs left to itself: seven waves a SIMD, i.e. ONE 1024-thread workgroup a CU.  Held at 64 -- two workgroups a CU -- a sort of many tiles has somebody to run while a
 //  workgroup waits for its look-back: DESIGN.md 4a)
 __global__ __launch_bounds__(OS_THREADS) __attribute__((amdgpu_waves_per_eu(OS_WAVES_PER_EU, OS_WAVES_PER_EU))) void k_os_pass(const uint64_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in,
@@ -158,7 +162,8 @@ __global__ __launch_bounds__(OS_THREADS) __attribute__((amdgpu_waves_per_eu(OS_W
                                                           unsigned long long *lookback /* [ntiles][256] */, uint32_t *ticket /* [pass]; ticket[8 - pass] = timeout flag */, int first_pass, int hist_copies,
                                                           const uint32_t *__restrict__ tile_hist /* NULL, or [ntiles][256]: this digit's counts per INPUT tile, left by the kernel that wrote the keys
                                                                                                     (k_morton): the tile offsets are their sums, no look-back */,
-                                                          const uint32_t *__restrict__ chunk_tot /* NULL, or [ntiles / OS_CHUNK][256]: the same counts summed over chunks of OS_CHUNK tiles (k_tile_chunks) */)
+                                                          const uint32_t *__restrict__ chunk_tot /* NULL, or [ntiles / OS_CHUNK][256]: the same counts summed over chunks of OS_CHUNK tiles (k_tile_chunks) */,
+                                                          uint32_t *__restrict__ stat /* NULL, or (the first pass behind k_morton) the cell statistic's two words: cell_stat_turn */)
 {
     __shared__ uint32_t wcnt[OS_WAVES][RADIX];
     __shared__ uint32_t gbase[RADIX];
@@ -167,6 +172,7 @@ __global__ __launch_bounds__(OS_THREADS) __attribute__((amdgpu_waves_per_eu(OS_W
     __shared__ uint32_t s_wsum[RADIX / 64];
     const uint32_t tid = threadIdx.x;
     const int lane = tid & 63, w = tid >> 6;
+    cell_stat_turn(stat);
     if (tid == 0) s_tile = tile_hist ? blockIdx.x : atomicAdd(ticket, 1u);      // (no look-back, no need for arrival order: the ticket's round trip is saved)
     for (int i = tid; i < OS_WAVES * RADIX; i += OS_THREADS) (&wcnt[0][0])[i] = 0;
     // digit bases = exclusive scan of the 256 raw counts; every tile does it for itself (no scan kernel)
@@ -295,6 +301,179 @@ __global__ __launch_bounds__(OS_THREADS) __attribute__((amdgpu_waves_per_eu(OS_W
     }
 }
 
+// ====================================================================================================
+// The cell form of the global stage: ONE launch in place of the two onesweep passes of the hybrid sort, for input whose order is coherent (a mesh as a modelling
+// tool or a simulator writes it: 64 consecutive triangles fall into a few of the 2^16 cells of the sort's 16 global key bits).  Nothing here waits for another
+// workgroup -- no look-back, no ticket, no spin:
+//   (k_morton)     : beside the digit histograms, the keys per cell (cell_hist[CELLS]) -- per wave ONE atomic add per distinct cell of its 64 keys (cell_count, cell_groups)
+//   k_cell_scatter : the base of cell (h, l) is the exclusive scan of the high digit's 256 counts + the prefix of row h of cell_hist, which a tile works out for
+//                    the rows it holds; a key's place inside its cell comes from a cursor per cell, again one (returning) atomic add per wave and distinct cell.
+// The order INSIDE a cell is whatever order the waves arrive in and differs from run to run; k_local_sort orders every run of equal global bits completely
+// (its epilogue breaks full-key ties by value), so the final keys and permutation are those of the two stable passes.  Input without coherence (a triangle soup:
+// 64 cells a wave) would make this a million scattered atomics a step -- three times the cost of a pass (see above): the host chooses the form by the mean number
+// of cell changes among a wave's 64 consecutive triangles that k_morton reports (cell_count; mi355cd.hip, CELL_FORM_MAX_MEAN_16), and both forms are correct for any input.
+constexpr int CELLS = 1 << (2 * RADIX_BITS);
+constexpr int CELL_LOOP_CAP = 8;                       // distinct cells a wave handles with one atomic each; lanes left after that add for themselves
+constexpr int CELL_ROWS = 16;                          // rows of cell_hist (high digits) a tile scans at a time: a coherent tile holds fewer
+
+// One round of a wave: every lane holds a cell (`ok`: and a key).  The lanes are put into groups of one cell each: `lead` the group's first lane, `rank` the lane's
+// place among the group's lanes, `cnt` (in the leading lane) their number -- so that ONE lane a group goes to memory for all of them, and the leading lanes of a round
+// do so in ONE instruction (an atomic inside the loop, one lane at a time, made k_cell_scatter 22.3 us at 1 M keys where this is 11.8).  Up to CELL_LOOP_CAP distinct
+// cells are found one after the other; the lanes of further cells are each a group of their own: correct for any input.
+__device__ __forceinline__ void cell_groups(uint32_t cell, bool ok, int &lead, uint32_t &rank, uint32_t &cnt)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    lead = lane; rank = 0u; cnt = 1u;
+    unsigned long long rem = __ballot(ok);
+    for (int u = 0; u < CELL_LOOP_CAP && rem; ++u) {
+        const int leader = __builtin_amdgcn_readfirstlane(__ffsll(rem) - 1);
+        const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cell, leader);
+        const unsigned long long m = __ballot(ok && cell == c);
+        if ((m >> lane) & 1ull) { lead = leader; rank = (uint32_t)__popcll(m & lt_mask); cnt = (uint32_t)__popcll(m); }
+        rem &= ~m;
+    }
+}
+
+// k_morton's part: the statistic -- the places where the cell changes between consecutive triangles, counted per wave (its return value, the same in every lane: one
+// compare with the lane before: the classic form pays no loop for it; for coherent input close to the number of distinct cells, never below it) -- and, for the cell
+// form (hist != NULL), the keys per cell.
+__device__ __forceinline__ uint32_t cell_count(uint32_t cell, bool ok, uint32_t *__restrict__ hist)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp((int)~cell, (int)cell, 0x138, 0xf, 0xf, false);
+    const uint32_t changes = (uint32_t)__popcll(__ballot(ok && (lane == 0 || cell != prev)));
+    if (hist) {                                                            // (uniform)
+        int lead; uint32_t rank, cnt;
+        cell_groups(cell, ok, lead, rank, cnt);
+        if (ok && lead == lane) atomicAdd(&hist[cell], cnt);
+    }
+    return changes;
+}
+
+// The statistic's two words (stat[0]: the last complete count, what the report posts; stat[1]: k_morton's accumulator): the first kernel behind k_morton moves
+// the count over and clears the accumulator for the next step.
+__device__ __forceinline__ void cell_stat_turn(uint32_t *__restrict__ stat)
+{
+    if (stat && blockIdx.x == 0 && threadIdx.x == 0) { stat[0] = stat[1]; stat[1] = 0u; }
+}
+
+// (1024 threads and tiles of 4096 keys like k_os_pass: 512 / 256 threads -- two / four workgroups a CU -- took 13.6 / 16.5 us where this takes 11.8, 1 M keys)
+__global__ __launch_bounds__(OS_THREADS) void k_cell_scatter(const uint64_t *__restrict__ keys_in, uint64_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out /* value = position in keys_in */,
+                                                          uint32_t n, int shift /* cell = key bits [shift, shift + 16) */,
+                                                          const uint32_t *__restrict__ digit_hist /* [256] raw counts of the HIGH digit (key bits [shift + 8, shift + 16)), hist_copies partial tables */, int hist_copies,
+                                                          const uint32_t *__restrict__ cell_hist /* [CELLS] keys per cell (k_morton) */, uint32_t *__restrict__ cell_cursor /* [CELLS], zero */,
+                                                          uint32_t *__restrict__ stat)
+{
+    constexpr int THREADS = OS_THREADS;
+    static_assert(THREADS % RADIX == 0 && THREADS <= 1024, "a row of cell_hist is scanned by RADIX threads");
+    constexpr int ITEMS = OS_ITEMS, WAVES = THREADS / 64, TILE = THREADS * ITEMS, GROUPS = THREADS / RADIX /* rows scanned side by side */, ROUNDS = CELL_ROWS / GROUPS;
+    __shared__ uint32_t s_dbase[RADIX];                  // exclusive scan of the high digit's counts
+    __shared__ uint32_t s_cbase[CELL_ROWS][RADIX];       // base of the cells of the rows in hand
+    __shared__ uint32_t s_hmask[RADIX / 32];             // the high digits this tile holds
+    __shared__ uint32_t s_slot[RADIX], s_hof[RADIX];     // high digit -> its number among those, and back
+    __shared__ uint32_t s_wsum[RADIX / 64];
+    __shared__ uint32_t s_rsum[ROUNDS][WAVES];
+    const uint32_t tid = threadIdx.x;
+    const int lane = tid & 63, w = tid >> 6;
+    cell_stat_turn(stat);
+    if (tid < RADIX / 32) s_hmask[tid] = 0u;
+    uint32_t dbase = 0;
+    if (tid < RADIX) {
+        uint32_t c = 0;
+        for (int k = 0; k < hist_copies; ++k) c += digit_hist[(size_t)k * HIST_STRIDE + tid];
+        uint32_t v = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(v, o); if (lane >= o) v += t; }
+        if (lane == 63) s_wsum[w] = v;
+        dbase = v - c;
+    }
+    const uint32_t base_w = blockIdx.x * TILE + w * (ITEMS * 64);
+    uint64_t k[ITEMS];
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+        const uint32_t i = base_w + it * 64 + lane;
+        k[it] = i < n ? keys_in[i] : 0ull;
+    }
+    __syncthreads();
+    if (tid < RADIX) { for (int ww = 0; ww < w; ++ww) dbase += s_wsum[ww]; s_dbase[tid] = dbase; }
+    // a place inside its cell for every key: per group of lanes with one cell (cell_groups) one returning add to the cell's cursor -- the lanes of the group take
+    // consecutive places from it by their rank.  ALL the atomics of the wave go out before the first result is used: they fly while the tile scans its rows.
+    uint32_t old[ITEMS], rk[ITEMS]; int lead[ITEMS];
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+        const bool ok = base_w + it * 64 + lane < n;
+        const uint32_t cell = (uint32_t)(k[it] >> shift) & (uint32_t)(CELLS - 1);
+        uint32_t cnt;
+        cell_groups(cell, ok, lead[it], rk[it], cnt);
+        old[it] = 0u;
+        if (ok && lead[it] == lane) { old[it] = atomicAdd(&cell_cursor[cell], cnt); atomicOr(&s_hmask[cell >> 13], 1u << ((cell >> 8) & 31u)); }
+    }
+    __syncthreads();
+    // the high digits the tile holds, numbered in order
+    uint32_t nh = 0;
+    {
+        uint32_t mine = 0;
+#pragma unroll
+        for (int q = 0; q < RADIX / 32; ++q) {
+            const uint32_t mq = s_hmask[q];
+            nh += (uint32_t)__popc(mq);
+            if (tid < RADIX) mine += (uint32_t)q < (tid >> 5) ? (uint32_t)__popc(mq) : ((uint32_t)q == (tid >> 5) ? (uint32_t)__popc(mq & ((1u << (tid & 31u)) - 1u)) : 0u);
+        }
+        if (tid < RADIX) {
+            const bool present = (s_hmask[tid >> 5] >> (tid & 31u)) & 1u;
+            s_slot[tid] = present ? mine : 0xffffffffu;
+            if (present) s_hof[mine] = tid;
+        }
+    }
+    __syncthreads();
+    // CELL_ROWS rows at a time (a coherent tile: once): four waves scan a row of cell_hist, base = the high digit's base + the row's exclusive prefix
+    uint32_t base[ITEMS];
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) base[it] = 0u;
+    for (uint32_t r0 = 0; r0 < nh; r0 += CELL_ROWS) {                      // (workgroup-uniform)
+        uint32_t x[ROUNDS], v[ROUNDS];
+#pragma unroll
+        for (int u = 0; u < ROUNDS; ++u) {
+            const uint32_t slot = r0 + (uint32_t)(GROUPS * u) + (tid >> 8);     // (wave-uniform)
+            x[u] = slot < nh ? cell_hist[(size_t)s_hof[slot] * RADIX + (tid & 255u)] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < ROUNDS; ++u) {
+            v[u] = x[u];
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(v[u], o); if (lane >= o) v[u] += t; }
+            if (lane == 63) s_rsum[u][w] = v[u];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < ROUNDS; ++u) {
+            const uint32_t slot = r0 + (uint32_t)(GROUPS * u) + (tid >> 8);
+            if (slot < nh) {
+                uint32_t pre = s_dbase[s_hof[slot]] + v[u] - x[u];
+                for (int ww = w & ~3; ww < w; ++ww) pre += s_rsum[u][ww];
+                s_cbase[GROUPS * u + (tid >> 8)][tid & 255u] = pre;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < ITEMS; ++it) {
+            const uint32_t cell = (uint32_t)(k[it] >> shift) & (uint32_t)(CELLS - 1);
+            const uint32_t slot = s_slot[cell >> 8] - r0;                  // (a lane without a key: cell 0, which the tile may not hold -- its base is not used)
+            if (slot < (uint32_t)CELL_ROWS) base[it] = s_cbase[slot][cell & 255u];
+        }
+        if (r0 + CELL_ROWS < nh) __syncthreads();                         // (the next rows go where these were)
+    }
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+        const uint32_t i = base_w + it * 64 + lane;
+        const uint32_t pos = base[it] + (uint32_t)__shfl((int)old[it], lead[it]) + rk[it];
+        if (i < n && pos < n) {                                             // (pos < n whenever cell_hist counts these keys and the cursors began at zero: the host's part; never a store out of bounds)
+            keys_out[pos] = k[it];
+            vals_out[pos] = i;
+        }
+    }
+}
 
 // ====================================================================================================
 // Hybrid sort (default).  The onesweep passes cost ~20 us each at 1 M keys, nearly all of it the cross-XCD hand-off
@@ -329,7 +508,7 @@ using LocalLarge = LocalCfg<1024, 10, 6144, 1>;            // (a planar 1 M clot
 using LocalSmall = LocalCfg<512, 10, 3072, LOCAL_SMALL_BLOCKS>;             // (8 M triangles of cloth objects: runs up to 1878 on bits 44..59; a 4 M cloth pair: 2312)
 constexpr int LOCAL_W = LocalLarge::W;                  // nominal keys per workgroup of the large form (the host's window arithmetic)
 
-__device__ __forceinline__ bool fixup_position_lds(const uint2 *item, uint32_t cnt, uint32_t j, uint32_t low, uint32_t high, uint32_t &pos);
+__device__ __forceinline__ bool fixup_position_lds(const uint2 *item, const uint32_t *ival, uint32_t cnt, uint32_t j, uint32_t low, uint32_t high, uint32_t val, uint32_t &pos);
 template <class Emit, class CFG>
 __global__ __launch_bounds__(CFG::THREADS) __attribute__((amdgpu_waves_per_eu(CFG::BLOCKS * CFG::WAVES / 4, CFG::BLOCKS * CFG::WAVES / 4))) void k_local_sort(const uint64_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in,
                                                               uint64_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out, uint32_t n,
@@ -341,6 +520,7 @@ __global__ __launch_bounds__(CFG::THREADS) __attribute__((amdgpu_waves_per_eu(CF
     constexpr int LOCAL_THREADS = CFG::THREADS, LOCAL_WAVES = CFG::WAVES, LOCAL_ITEMS = CFG::ITEMS, LOCAL_LIMIT = CFG::LIMIT, LOCAL_CAP = CFG::CAP;
     if (blockIdx.x == 0) for (uint32_t i = threadIdx.x; i < n_zero; i += LOCAL_THREADS) zero_words[i] = 0u;
     __shared__ uint2 sitem[LOCAL_CAP];                   // 80 KB: {high 32 key bits, position inside the window}
+    __shared__ uint32_t sval[LOCAL_CAP];                 // 40 KB (the small form: 20 of 68 KB, two workgroups a CU as before; the large form: 136 KB, one): the epilogue's values, its tie-break
     __shared__ uint32_t wcnt[LOCAL_WAVES][RADIX];        // 16 KB
     __shared__ uint32_t s_wsum[RADIX / 64];
     __shared__ uint32_t s_enc[2];
@@ -575,7 +755,7 @@ __global__ __launch_bounds__(CFG::THREADS) __attribute__((amdgpu_waves_per_eu(CF
 #pragma unroll
     for (int it = 0; it < LOCAL_ITEMS; ++it) if (it < nit) {
         const uint32_t j = base_w + it * 64 + lane;
-        if (j < cnt) sitem[j] = make_uint2(lowk[it], high[it]);
+        if (j < cnt) { sitem[j] = make_uint2(lowk[it], high[it]); sval[j] = tv[it]; }
     }
     __syncthreads();
     // (in chunks of 5 items -- a window of the nominal size has 4 per lane: what emit gathers for an item is requested
@@ -594,7 +774,7 @@ __global__ __launch_bounds__(CFG::THREADS) __attribute__((amdgpu_waves_per_eu(CF
                 const uint32_t low = lowk[it];
                 uint32_t pos;
                 // run too long: flag it (the host redoes the sort with 8 passes) but still emit a valid permutation and valid leaves
-                if (!fixup_position_lds(sitem, cnt, j, low, high[it], pos)) { atomicOr(overflow, SORTF_FIXUP); pos = j; }
+                if (!fixup_position_lds(sitem, sval, cnt, j, low, high[it], tv[it], pos)) { atomicOr(overflow, SORTF_FIXUP); pos = j; }
                 keys_out[lo + pos] = ((uint64_t)high[it] << 32) | low; vals_out[lo + pos] = tv[it];
                 emit.store(lo + pos, tv[it], pl[u]);
             }
@@ -618,26 +798,30 @@ constexpr int FIX_MAX = 16;
 // which is its position inside the run.  Typical cost: two neighbour reads and one copy.
 // Final position of key i (value k0) inside its run of equal high halves; false if the run may exceed FIX_MAX.
 // The two neighbours are fetched up front (independent loads): for most keys they already end the run.
-__device__ __forceinline__ bool fixup_position(const uint64_t *__restrict__ keys_in, uint32_t n, uint32_t i, uint64_t k0, uint32_t &pos)
+// A FULL-key tie is broken by the value (the triangle number), on both sides alike: the order inside the run is then (low half, value) whatever order the run
+// arrived in -- the stable order where the passes in front are stable (equal keys arrive by triangle number), and the same order where they are not (the cell
+// form of the global stage, k_cell_scatter).  The value of a neighbour is fetched only where the whole key is equal.
+__device__ __forceinline__ bool fixup_position(const uint64_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, uint32_t n, uint32_t i, uint64_t k0, uint32_t v0, uint32_t &pos)
 {
     const uint32_t h = (uint32_t)(k0 >> 32);
     const uint64_t kp = i > 0 ? keys_in[i - 1] : ~k0, kn = i + 1 < n ? keys_in[i + 1] : ~k0;   // ~k0: a different high half
     uint32_t back = 0, before = 0, fwd = 0;
+    auto precedes = [&](uint64_t kb, uint32_t at) -> uint32_t { return kb != k0 ? (kb < k0) : (vals_in[at] < v0); };
     if ((uint32_t)(kp >> 32) == h) {
-        before += kp <= k0; back = 1;
+        before += precedes(kp, i - 1); back = 1;
         while (back < (uint32_t)FIX_MAX && back < i) {
             const uint64_t kb = keys_in[i - 1 - back];
             if ((uint32_t)(kb >> 32) != h) break;
-            before += kb <= k0;
+            before += precedes(kb, i - 1 - back);
             ++back;
         }
     }
     if ((uint32_t)(kn >> 32) == h) {
-        before += kn < k0; fwd = 1;
+        before += precedes(kn, i + 1); fwd = 1;
         while (fwd < (uint32_t)FIX_MAX && i + 1 + fwd < n) {
             const uint64_t kf = keys_in[i + 1 + fwd];
             if ((uint32_t)(kf >> 32) != h) break;
-            before += kf < k0;
+            before += precedes(kf, i + 1 + fwd);
             ++fwd;
         }
     }
@@ -645,20 +829,20 @@ __device__ __forceinline__ bool fixup_position(const uint64_t *__restrict__ keys
     return back < (uint32_t)FIX_MAX && fwd < (uint32_t)FIX_MAX;
 }
 
-// The same count over a window held in LDS as {low half, high half} (k_local_sort's epilogue).
-__device__ __forceinline__ bool fixup_position_lds(const uint2 *item, uint32_t cnt, uint32_t j, uint32_t low, uint32_t high, uint32_t &pos)
+// The same count over a window held in LDS as {low half, high half} and, beside it, the values (k_local_sort's epilogue).
+__device__ __forceinline__ bool fixup_position_lds(const uint2 *item, const uint32_t *ival, uint32_t cnt, uint32_t j, uint32_t low, uint32_t high, uint32_t val, uint32_t &pos)
 {
     uint32_t back = 0, before = 0, fwd = 0;
     while (back < (uint32_t)FIX_MAX && back < j) {
         const uint2 b = item[j - 1 - back];
         if (b.y != high) break;
-        before += b.x <= low;
+        before += b.x != low ? (b.x < low) : (ival[j - 1 - back] < val);
         ++back;
     }
     while (fwd < (uint32_t)FIX_MAX && j + 1 + fwd < cnt) {
         const uint2 f = item[j + 1 + fwd];
         if (f.y != high) break;
-        before += f.x < low;
+        before += f.x != low ? (f.x < low) : (ival[j + 1 + fwd] < val);
         ++fwd;
     }
     pos = j - back + before;

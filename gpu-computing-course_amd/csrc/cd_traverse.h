@@ -41,7 +41,7 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 struct alignas(256) Report {
     unsigned long long n_pairs, pairs_tested, node_visits, max_shard_candidates, wave_steps, candidates;
     uint32_t n_deferred, pad0;
-    uint32_t sort_flags[9]; uint32_t pad1;
+    uint32_t sort_flags[10];                     // [9] is no flag: the cell statistic of the step's sort (cd_sort.h cell_stat_turn), which sits behind the flag words
     double root_box[6];
     unsigned long long clk_start_inv, clk_end;   // descent kernel, device wall clock (s_memrealtime ticks): ~(earliest wave start), latest wave end; 0 = not taken
     unsigned long long seq;                      // polled completion: the step's sequence number, stored LAST (0: this report does not take part)
@@ -56,7 +56,7 @@ static_assert(sizeof(Report) == 256, "report layout");
 // stores the sequence number with a system-scope release (the memory-model argument: DESIGN.md section 6), after putting the counter back
 // to zero for the next report (of this step -- the deep pass, whose grid may differ -- or of the next one).
 constexpr int REPORT_THREADS = 256;
-__global__ __launch_bounds__(REPORT_THREADS) void k_report(const TravState *__restrict__ st, const uint32_t *__restrict__ sort_flags /* 9 words */,
+__global__ __launch_bounds__(REPORT_THREADS) void k_report(const TravState *__restrict__ st, const uint32_t *__restrict__ sort_flags /* 9 words + the cell statistic */,
                                                            const double *__restrict__ root_box, Report *__restrict__ out,
                                                            const uint32_t *__restrict__ pairs, uint32_t *__restrict__ pairs_out, unsigned long long spec_n,
                                                            unsigned long long seq)
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(REPORT_THREADS) void k_report(const TravState *__re
             out->wave_steps = steps; out->candidates = cands; out->n_deferred = st->n_deferred;
             out->clk_start_inv = c0; out->clk_end = c1;
         }
-        if (lane < 9) out->sort_flags[lane] = sort_flags[lane];
+        if (lane < 10) out->sort_flags[lane] = sort_flags[lane];
         if (lane < 6) out->root_box[lane] = root_box[lane];
     }
     const unsigned long long take = np < spec_n ? np : spec_n;          // pairs are 8 bytes; move them as 16-byte quads, an odd last pair on its own

@@ -300,6 +300,13 @@ struct cd_ctx {
     uint64_t *d_keys[2] = {nullptr, nullptr}; uint32_t *d_perm[2] = {nullptr, nullptr};
     uint32_t *d_counts = nullptr; uint32_t ntiles = 0;
     uint32_t *d_chunk_tot = nullptr;        // d_counts summed over chunks of OS_CHUNK tiles (sorts of more than OS_CHUNK_MIN_TILES tiles: k_tile_chunks)
+    // The cell form of the hybrid sort's global stage (cd_sort.h, k_cell_scatter): keys per cell | a cursor per cell, 2 x CELLS words.  Both are zero between steps: a step in
+    // the cell form clears them for the next (ZeroPlan), the classic form does not touch them, a step that did not clean up after itself leaves cell_clean false (one memset).
+    uint32_t *d_cell = nullptr; bool cell_clean = false;
+    bool cell_form = false;                 // the form the NEXT hybrid sort's global stage takes: chosen by choose_cell_form when a step's flags are judged, from the statistic that step's report carried
+    bool cell_form_used = false;            // ... and the one the last sort took (CD_DBG_GET_SORT_CELLS)
+    uint32_t dbg_sort_cells = 0;            // CD_DBG_SORT_CELLS: 0 the form the statistic asks for, 1 always the classic form (two onesweep passes), 2 always the cell form (A/B, tests)
+    uint32_t cell_stat = 0;                 // the last judged step's statistic: cell changes among every wave of k_morton's 64 consecutive triangles, summed (CD_DBG_GET_CELL_STAT)
     // onesweep state, part of one scratch block (layout: cd_create): [8][256] u32 histograms | 8 u32 tickets (padded) | [8][ntiles][256] u64 granules
     void *d_os = nullptr; size_t os_bytes = 0 /* whole block */, zero_bytes = 0 /* its front part: all a fused call with the hybrid sort needs zeroed */, sort_hi_bytes = 0 /* of that, the sort's own */;
     unsigned long long *d_os_look_lo = nullptr;   // granules of the digit passes 0..5 (behind the front part); d_os_look: passes 6 and 7
@@ -350,7 +357,7 @@ struct cd_ctx {
     } left;
     // host mirrors
     cd_stats stats = {};
-    uint32_t sort_flags[9] = {};            // [0..7] look-back time-out words of the last sort, [8] half-key fix-up overflow; refreshed by read_state()
+    uint32_t sort_flags[10] = {};           // [0..7] look-back time-out words of the last sort, [8] half-key fix-up overflow, [9] no flag: the cell statistic (k_morton), which travels with them; refreshed by read_state()
     bool stage_events = true;               // CD_OPT_STAGE_TIMING
     uint32_t dbg_report_copies = 0;        // CD_DBG_REPORT_COPIES: the report kernel copies the first pairs to the host (32 workgroups) instead of the exact kernel posting them (A/B)
     bool order_hint_large = false;          // CD_OPT_ORDER_HINT 2: also for trees of more than 1 M leaves (sorted chunk by chunk; measured slower there)
@@ -441,7 +448,7 @@ void free_all(cd_ctx *c)
 {
     hipFree(c->d_verts); hipFree(c->d_vidx); hipFree(c->d_ids);
     for (int i = 0; i < 2; ++i) { hipFree(c->d_keys[i]); hipFree(c->d_perm[i]); }
-    hipFree(c->d_counts); hipFree(c->d_chunk_tot); hipFree(c->d_os); hipFree(c->d_frame); hipFree(c->d_partial);
+    hipFree(c->d_counts); hipFree(c->d_chunk_tot); hipFree(c->d_cell); hipFree(c->d_os); hipFree(c->d_frame); hipFree(c->d_partial);
     hipFree(c->d_top_pub); hipFree(c->d_leaf); hipFree(c->d_meta); hipFree(c->d_parent); hipFree(c->d_seg); hipFree(c->d_seg32); hipFree(c->d_cross); hipFree(c->d_boxes);
     hipFree(c->d_bounded); hipFree(c->d_recs32); hipFree(c->d_qbox); hipFree(c->d_leaf_side); hipFree(c->d_split_of); hipFree(c->d_cost); hipFree(c->d_order); hipFree(c->d_tri_cost);
     hipFree(c->d_amb_keys); hipFree(c->d_amb_flag); hipFree(c->d_vamb);
@@ -654,8 +661,8 @@ int enqueue_morton_sort(cd_ctx *c, bool links_too = true, bool frame_ready = fal
     const bool skip_memset = self_cleaning && c->left.scratch_clean;
     c->left.scratch_clean = false;
     if (!skip_memset) HIPCHK(hipMemsetAsync(c->d_os, 0, c->sort_mode <= 1 ? (c->prezeroed ? c->zero_bytes : c->sort_hi_bytes) : c->os_bytes, s));
-    // Three forms of the same stable 64-bit sort (cd_sort.h): hybrid = 2 global passes on the top 16 bits + an in-LDS
-    // sort of run-aligned windows + the fix-up hop; half-key = 4 global passes on the high 32 bits + the fix-up hop;
+    // Three forms of the same stable 64-bit sort (cd_sort.h): hybrid = the top 16 bits ordered globally (2 passes, or one launch that places
+    // every key by its cell of those bits: `cells` below) + an in-LDS sort of run-aligned windows + the fix-up hop; half-key = 4 global passes on the high 32 bits + the fix-up hop;
     // full = 8 global passes.  The keys start in the buffer that leaves the sorted data in buffer 0.
     const int mode = c->sort_mode;
     const bool hybrid = mode <= 1;
@@ -663,27 +670,39 @@ int enqueue_morton_sort(cd_ctx *c, bool links_too = true, bool frame_ready = fal
                                                 // where bits 48..63 of a 60-bit Morton key hold 12: runs 16 x shorter, windows of even size
     const int first_digit = hybrid ? 6 : (mode == 2 ? 4 : 0);
     int cur = mode == 3 ? 0 : 1;
+    // The hybrid forms' global stage, classic (two onesweep passes) or by cells (one launch, no rendezvous: cd_sort.h); same result either way.  The cell arrays are
+    // zero unless a step in the cell form went without its clean-up (no fused build behind it, or a raised flag).
+    const bool cells = hybrid && c->cell_form;
+    c->cell_form_used = cells;
+    if (cells && !(skip_memset && c->cell_clean)) HIPCHK(hipMemsetAsync(c->d_cell, 0, sizeof(uint32_t) * 2 * CELLS, s));
+    if (cells) { c->cell_clean = false; cur = 0; }                           // (one hop instead of two: the keys start in buffer 0, the window sort finds them in buffer 1 as always)
+    const int cell_shift = hybrid ? 48 - down : -1;
+    uint32_t *cell_hist = cells ? c->d_cell : nullptr, *cell_stat = c->d_os_ticket + 17;
     const uint32_t mblocks = c->ntiles < 2048u ? c->ntiles : 2048u;         // a workgroup per sort tile (4096 keys)
     unsigned long long host_layout = 0ull; std::memcpy(&host_layout, &c->frame_host[6], sizeof host_layout);
     const double *mframe = auto_frame ? nullptr : c->d_frame;               // (auto: the kernel folds the partial bounds itself and WRITES d_frame)
     const double *mpart = auto_frame ? c->d_partial : nullptr;
     if (auto_frame || host_layout != 0ull)
         k_morton<true><<<mblocks, MORTON_THREADS, 0, s>>>(c->d_verts, c->d_vidx, n, mframe, c->d_keys[cur], c->d_os_hist, first_digit, down, c->d_os_ticket + 16,
-                                                          mpart, (uint32_t)BOUNDS_BLOCKS, c->d_frame, nullptr, c->d_counts);
+                                                          mpart, (uint32_t)BOUNDS_BLOCKS, c->d_frame, nullptr, c->d_counts, cell_shift, cell_hist, cell_stat + 1);
     else
         k_morton<false><<<mblocks, MORTON_THREADS, 0, s>>>(c->d_verts, c->d_vidx, n, mframe, c->d_keys[cur], c->d_os_hist, first_digit, down, c->d_os_ticket + 16,
-                                                           mpart, (uint32_t)BOUNDS_BLOCKS, c->d_frame, nullptr, c->d_counts);
+                                                           mpart, (uint32_t)BOUNDS_BLOCKS, c->d_frame, nullptr, c->d_counts, cell_shift, cell_hist, cell_stat + 1);
     HIPCHK(evrec(c, EV_MORTON1));
     // onesweep: one pass over the data per digit; the digit histograms came with the keys
     // (more than 512 tiles: the first pass adds up chunk totals of the per-tile counts instead of every earlier tile's row -- cd_sort.h)
-    const bool chunked = c->ntiles > (uint32_t)OS_CHUNK_MIN_TILES;
+    const bool chunked = !cells && c->ntiles > (uint32_t)OS_CHUNK_MIN_TILES;
+    if (cells) {
+        k_cell_scatter<<<c->ntiles, OS_THREADS, 0, s>>>(c->d_keys[cur], c->d_keys[cur ^ 1], c->d_perm[cur ^ 1], n, cell_shift, c->d_os_hist + 7 * RADIX, HIST_COPIES,
+                                                        c->d_cell, c->d_cell + CELLS, cell_stat);
+    }
     if (chunked) k_tile_chunks<<<cdiv(c->ntiles, (uint32_t)OS_CHUNK), RADIX, 0, s>>>(c->d_counts, c->ntiles, c->d_chunk_tot);
-    for (int pass = first_digit; pass < 8; ++pass) {
+    for (int pass = first_digit; pass < 8 && !cells; ++pass) {
         k_os_pass<<<c->ntiles, OS_THREADS, 0, s>>>(c->d_keys[cur], c->d_perm[cur], c->d_keys[cur ^ 1], c->d_perm[cur ^ 1], n, pass * RADIX_BITS - down,
                                                     c->d_os_hist + pass * RADIX,
                                                     (pass >= 6 ? c->d_os_look + (size_t)(pass - 6) * c->ntiles * RADIX : c->d_os_look_lo + (size_t)pass * c->ntiles * RADIX),
                                                     c->d_os_ticket + pass, pass == first_digit, HIST_COPIES, pass == first_digit ? c->d_counts : nullptr,
-                                                    pass == first_digit && chunked ? c->d_chunk_tot : nullptr);
+                                                    pass == first_digit && chunked ? c->d_chunk_tot : nullptr, pass == first_digit && hybrid ? cell_stat : nullptr);
         cur ^= 1;
     }
     c->left.leaves_filled = false; c->left.leaf_records_filled = false;
@@ -714,7 +733,7 @@ int enqueue_morton_sort(cd_ctx *c, bool links_too = true, bool frame_ready = fal
         c->left.leaves_filled = links_too;           // by the fix-up hop; enqueue_hierarchy runs k_fill_leaves otherwise
         c->left.leaf_records_filled = true;
     }
-    c->stats.sort_passes = hybrid ? 2 : (mode == 2 ? 4 : 8);
+    c->stats.sort_passes = hybrid ? 2 : (mode == 2 ? 4 : 8);       // (8-bit digits ordered globally: two in either form of the hybrid sort's global stage)
     HIPCHK(evrec(c, EV_SORT1));
     HIPCHK(hipGetLastError());
     return 0;
@@ -777,7 +796,8 @@ int enqueue_refit(cd_ctx *c, bool write_internal, bool fused = false)
         if (self_cleaning) {
             const size_t gran = sizeof(unsigned long long) * (size_t)c->ntiles * RADIX;
             zp = ZeroPlan{c->d_os_hist, (uint32_t)HIST_COPIES * 8u * RADIX + 8u /* histograms + tickets; the flags behind them stay */,
-                          reinterpret_cast<uint4 *>(c->d_os_look), (uint32_t)(2 * gran / sizeof(uint4)),
+                          c->cell_form_used ? reinterpret_cast<uint4 *>(c->d_cell) : reinterpret_cast<uint4 *>(c->d_os_look),      // (the cell form wrote no granule: its cell arrays instead)
+                          c->cell_form_used ? (uint32_t)(sizeof(uint32_t) * 2 * CELLS / sizeof(uint4)) : (uint32_t)(2 * gran / sizeof(uint4)),
                           reinterpret_cast<uint32_t *>(c->tb[0].d_state), (uint32_t)(sizeof(TravState) / sizeof(uint32_t)), top_flag_of(c)};
         }
         const int seg_min = (c->nbp2 > 1 && !c->dbg_split_cross) ? SEG32_MIN_LEVEL : SEG_MIN_LEVEL;
@@ -799,6 +819,7 @@ int enqueue_refit(cd_ctx *c, bool write_internal, bool fused = false)
                                                         hp, ht, hc, c->d_leaf_side, store_q);
         c->order_pending = hint;
         c->left.scratch_clean = self_cleaning;       // (judge_sort_flags takes it back when the sort has raised a flag)
+        if (self_cleaning && c->cell_form_used) c->cell_clean = true;
     } else {
         c->left.qbox_valid = true;
         k_refit_seg_local<<<nblocks, REFIT_BLK, 0, s>>>(c->d_verts, c->d_leaf, (int)n, c->d_meta, c->d_boxes, c->d_bounded,
@@ -1224,7 +1245,7 @@ int pp_sort(cd_ctx *c, uint32_t m)
     int cur = 0;
     for (int pass = 0; pass < 8; ++pass) {
         k_os_pass<<<ntiles, OS_THREADS, 0, s>>>(c->pp_keys[cur], c->pp_vals[cur], c->pp_keys[cur ^ 1], c->pp_vals[cur ^ 1], m, pass * RADIX_BITS,
-                                                hist + pass * RADIX, look + (size_t)pass * ntiles * RADIX, ticket + pass, pass == 0, 1, nullptr, nullptr);
+                                                hist + pass * RADIX, look + (size_t)pass * ntiles * RADIX, ticket + pass, pass == 0, 1, nullptr, nullptr, nullptr);
         cur ^= 1;
     }
     return 0;
@@ -1234,7 +1255,7 @@ int judge_sort_flags(cd_ctx *c);
 // ---- CD_OPT_GRAPH: the steady-state fused step as ONE hipGraph launch ------------------------------------------------
 // Eligible: no stage events, no time stamps, hybrid sort, fused build, half traversal, and a previous step has left the
 // scratch clean (so the captured sequence holds kernels only: no memset).  The capture records exactly what the stream path
-// enqueues -- k_morton, 2 x k_os_pass, k_local_sort, k_build_block, k_cross_fused, k_descend_half, k_exact, k_report -- with
+// enqueues -- k_morton, 2 x k_os_pass or k_cell_scatter, k_local_sort, k_build_block, k_cross_fused, k_descend_half, k_exact, k_report -- with
 // the arguments of this call baked in; any change of those (capacity, buffers grown, options) captures again.  Whatever the
 // report says that the stream path would answer with a retry -- a sort flag, a candidate shard that overflowed, a deferred
 // subtree -- is handed to the stream path (handled = false, or run_traversal on the tree that is there).
@@ -1285,7 +1306,7 @@ int amb_refresh(cd_ctx *c)
 bool graph_eligible(const cd_ctx *c)
 {
     return c->graph_opt && !c->stage_events && c->stamp_mask == 0 && c->sort_mode <= 1 && fused_build_next(c) && c->trav_variant == 3 &&
-           c->left.scratch_clean && !c->dbg_diag && !c->dbg_lds_pad && c->nt > 1 && c->tree_done_event == nullptr;
+           c->left.scratch_clean && (!c->cell_form || c->cell_clean) /* (no memset in a captured step) */ && !c->dbg_diag && !c->dbg_lds_pad && c->nt > 1 && c->tree_done_event == nullptr;
 }
 int graph_step(cd_ctx *c, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs, bool &handled)
 {
@@ -1297,7 +1318,7 @@ int graph_step(cd_ctx *c, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs
     if (rc) return rc;
     uint64_t spec_n = pairs ? (cap_pairs < SPEC_PAIRS ? cap_pairs : SPEC_PAIRS) : 0;
     const bool direct = pinned_pairs_id(pairs, cap_pairs) != 0;
-    const cd_ctx::GraphKey key{cap_pairs, spec_n, c->sort_mode, c->trav_variant, c->frame_mode, c->nt, (uint32_t)c->exact_blocks, c->dbg_no_shared_path | (c->dbg_split_cross << 1) | (c->order_hint ? 4u : 0u) | (c->order_ready ? 8u : 0u) | (c->local_small_ok ? 16u : 0u) | (c->dbg_sort_windows << 5) | (qbox_wanted(c) ? 128u : 0u) /* (whether the descent's launch reads the order hint is baked in) */,
+    const cd_ctx::GraphKey key{cap_pairs, spec_n, c->sort_mode, c->trav_variant, c->frame_mode, c->nt, (uint32_t)c->exact_blocks, c->dbg_no_shared_path | (c->dbg_split_cross << 1) | (c->order_hint ? 4u : 0u) | (c->order_ready ? 8u : 0u) | (c->local_small_ok ? 16u : 0u) | (c->dbg_sort_windows << 5) | (qbox_wanted(c) ? 128u : 0u) | (c->cell_form ? 256u : 0u) /* (whether the descent's launch reads the order hint is baked in) */,
                                tb.d_pairs, tb.d_cand, tb.d_defer, direct ? (const void *)pairs : (const void *)tb.h_report, tb.cand_cap, tb.defer_cap, 0u};
     static_assert(sizeof(cd_ctx::GraphKey) == 2 * 8 + 6 * 4 + 4 * 8 + 8 + 2 * 4, "GraphKey has no padding");
     if (!c->graph_exec || std::memcmp(&key, &c->graph_key, sizeof key) != 0) {
@@ -1324,6 +1345,7 @@ int graph_step(cd_ctx *c, uint32_t *pairs, uint64_t cap_pairs, uint64_t *n_pairs
     }
     // what the enqueue functions leave behind on the host side, as the capture left it
     c->left = c->graph_post.left; c->stats.sort_passes = c->graph_post.sort_passes;
+    c->cell_form_used = c->cell_form;                                       // (the form is part of the key: the captured step's)
     HIPCHK(hipGraphLaunch(c->graph_exec, s));
     HIPCHK(hipStreamSynchronize(s));
     ++c->graph_replays;
@@ -1388,11 +1410,14 @@ int cd_create(cd_ctx **out, const double *verts_xyz, uint32_t nv, const uint32_t
     for (int i = 0; i < 2; ++i) { ALLOC(c->d_keys[i], sizeof(uint64_t) * n); ALLOC(c->d_perm[i], sizeof(uint32_t) * n); }
     ALLOC(c->d_counts, sizeof(uint32_t) * RADIX * c->ntiles);
     ALLOC(c->d_chunk_tot, sizeof(uint32_t) * RADIX * cdiv(c->ntiles, (uint32_t)OS_CHUNK));
+    ALLOC(c->d_cell, sizeof(uint32_t) * 2 * CELLS);
+    { hipError_t e_ = hipMemset(c->d_cell, 0, sizeof(uint32_t) * 2 * CELLS); if (e_ != hipSuccess) { free_all(c); delete c; return -(int)e_; } }
+    c->cell_clean = true;
     // one scratch block so that the fused pipeline zeroes everything with ONE memset, and as little as the sort form needs:
     //   [onesweep: histograms | tickets, flags | look-back granules of passes 6, 7] [small counters: 128 words] [TravState]   <- hybrid sort: this much
     //   [look-back granules of passes 0..5]                                                                                  <- the other forms: all of it
     const size_t gran = sizeof(unsigned long long) * (size_t)c->ntiles * RADIX;           // one pass
-    const size_t look_off = sizeof(uint32_t) * HIST_COPIES * 8 * RADIX + 128;              // hist (HIST_COPIES partial tables) | 8 tickets, 8 time-out flags, fix-up flag, pad
+    const size_t look_off = sizeof(uint32_t) * HIST_COPIES * 8 * RADIX + 128;              // hist (HIST_COPIES partial tables) | 8 tickets, 8 time-out flags, fix-up flag, the cell statistic's two words (cd_sort.h cell_stat_turn), pad
     c->sort_hi_bytes = look_off + 2 * gran;
     const size_t small_off = (c->sort_hi_bytes + 127) & ~(size_t)127, state_off = small_off + 512;
     c->zero_bytes = state_off + sizeof(TravState);
@@ -1514,11 +1539,26 @@ int cd_get_morton_frame(cd_ctx *c, double offset[3], double span[3], uint64_t *l
 // the onesweep look-back spins are bounded; a timeout sets one of the words d_os_ticket[8..15]
 constexpr int SORT_REDO = 77;                   // internal: this form of the sort could not finish, redo with the one the flags ask for
 constexpr int SORT_REDO_MAX = 4;                // redos one call can need: small windows -> large windows -> half-key -> full is three (judge_sort_flags); one to spare
+// The mean number of cell changes among 64 consecutive triangles (k_morton's statistic, cd_sort.h cell_count) up to which the global stage goes by cells, in sixteenths.
+// Measured (profiles/r20_experiments/cell_sort.log): the 1 M / 4 M cloth lie at 5.7 / 3.4 and gain, a cloth of 250 k at 10.3 and one of 40 k at 22.9 lose (few keys a cell),
+// a triangle soup lies at 64 and takes twice as long; at CELL_LOOP_CAP = 8 distinct cells a wave the kernels' loop no longer covers the wave.
+constexpr uint32_t CELL_FORM_MAX_MEAN_16 = 8u * 16u;
+static void choose_cell_form(cd_ctx *c, bool stat_known)
+{
+    const uint64_t waves = ((uint64_t)c->nt + 63u) / 64u;
+    const bool coherent = stat_known && c->cell_stat != 0u && (uint64_t)c->cell_stat * 16u <= (uint64_t)CELL_FORM_MAX_MEAN_16 * waves;
+    const bool next = c->dbg_sort_cells == 2 || (c->dbg_sort_cells == 0 && coherent);
+    c->cell_form = next;
+}
 namespace { int judge_sort_flags(cd_ctx *c)
 {
-    for (int i = 0; i < 9; ++i) if (c->sort_flags[i]) c->left.scratch_clean = false;     // the flag words are cleared by the memset only
+    for (int i = 0; i < 9; ++i) if (c->sort_flags[i]) { c->left.scratch_clean = false; c->cell_clean = false; }     // the flag words are cleared by the memset only
     for (int i = 0; i < 8; ++i) if (c->sort_flags[i]) return CD_ERR_SORT;
     const uint32_t f = c->sort_flags[8];
+    // The form of the NEXT sort's global stage (cd_sort.h): by cells where this step's keys came in coherent order -- k_morton's statistic, which travels with the flags --,
+    // classic after a raised flag (the redo, and a context's first step: nothing is known yet).  Either form gives the same keys and permutation.
+    c->cell_stat = c->sort_flags[9];
+    choose_cell_form(c, !f);
     if (!f) return CD_OK;
     // The flags say WHY (cd_sort.h): the next form is the one that can finish, not the next in line (round 5 walked 0 -> 1 -> 2 -> 3: a mesh with 17 coincident centroids
     // took four redos, one more than the multi-GPU step allowed itself).
@@ -2049,6 +2089,9 @@ int cd_debug_option(cd_ctx *c, int key, int64_t value, int64_t *out)
     case CD_DBG_GET_GRAPH_REPLAYS:  if (!out) return CD_ERR_ARG; *out = (int64_t)c->graph_replays; return CD_OK;
     case CD_DBG_GET_TREE_WAS_FUSED: if (!out) return CD_ERR_ARG; *out = c->left.last_tree_fused ? 1 : 0; return CD_OK;
     case CD_DBG_GET_SORT_FORM:   if (out) *out = c->sort_mode; return CD_OK;
+    case CD_DBG_SORT_CELLS:      if (value < 0 || value > 2) return CD_ERR_ARG; if ((uint32_t)value != c->dbg_sort_cells) { c->dbg_sort_cells = (uint32_t)value; c->cell_form = value == 2; } return CD_OK;   // (a change to 0: classic until a judged step says otherwise; the form is in the graph's key)
+    case CD_DBG_GET_SORT_CELLS:  if (!out) return CD_ERR_ARG; *out = c->cell_form_used ? 1 : 0; return CD_OK;
+    case CD_DBG_GET_CELL_STAT:   if (!out) return CD_ERR_ARG; *out = c->cell_stat; return CD_OK;
     case CD_DBG_GET_ORDER_STATE: {          // the order hint as it stands: 0 none built, 1 a permutation of the groups that differs from the plain order, 2 the plain order itself, -1 NOT a permutation (a bug)
         if (!out) return CD_ERR_ARG;
         *out = 0;

@@ -31,6 +31,7 @@ CD_DBG_REPORT_COPIES = 6
 CD_DBG_STORE_QBOX = 9
 CD_DBG_BIG_OFFSETS = 18
 CD_DBG_GET_GRAPH_CAPTURES, CD_DBG_GET_GRAPH_REPLAYS = 19, 20
+CD_DBG_SORT_CELLS, CD_DBG_GET_SORT_CELLS, CD_DBG_GET_CELL_STAT = 21, 22, 23
 
 QUERY_DTYPE = np.dtype([("v", "<f8", (9,)), ("id", "<u4"), ("vidx", "<u4", (3,))])
 assert QUERY_DTYPE.itemsize == 88

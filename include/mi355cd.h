@@ -69,7 +69,8 @@ typedef struct cd_stats {
     uint64_t candidates;       /* (query, leaf) candidates the fp32 descent handed to the exact kernel */
     float ms_descend;          /* shallow pass: memset + descent kernel (part of ms_traverse)          */
     float ms_exact;            /* shallow pass: exact-test kernel        (part of ms_traverse)          */
-    uint32_t sort_passes;      /* global digit passes of the last sort: 2 (hybrid), 4 (half-key) or 8     */
+    uint32_t sort_passes;      /* 8-bit key digits the last sort ordered globally: 2 (hybrid: by two passes or, for meshes */
+                               /* in coherent order, by one launch that places keys by cell), 4 (half-key) or 8            */
     float ms_pipeline;         /* fused calls: pipeline start -> end of the traversal kernels, one event pair */
     float ms_build_block;      /* fused calls: the kernel that builds hierarchy + boxes + records of the 512-leaf     */
                                /* blocks (k_refit_seg_local<fused>), from its own dispatch packet; part of ms_refit  */
@@ -279,8 +280,13 @@ enum {
     CD_DBG_GET_GRAPH_CAPTURES = 19,  /* ... CD_OPT_GRAPH: steps captured as a graph on this context so far (a captured step kept across other calls: no new capture)    */
     CD_DBG_GET_GRAPH_REPLAYS  = 20,  /* ... CD_OPT_GRAPH: graph launches of captured steps so far                                              */
     CD_DBG_GET_TREE_WAS_FUSED = 14,  /* 1: the tree that is there was made by the one-pass build                                              */
-    CD_DBG_GET_ORDER_STATE    = 15   /* the order hint (CD_OPT_ORDER_HINT) as it stands: 0 none built yet; 1 a permutation of the groups of 64 leaves that differs from the plain order;    */
+    CD_DBG_GET_ORDER_STATE    = 15,  /* the order hint (CD_OPT_ORDER_HINT) as it stands: 0 none built yet; 1 a permutation of the groups of 64 leaves that differs from the plain order;    */
                                      /* 2 the plain order itself; -1 not a permutation (must never be)                                                                                        */
+    CD_DBG_SORT_CELLS         = 21,  /* how sort forms 0 and 1 order their 16 global key bits: 0 (default) by the previous step's statistic -- one launch that places every key by its cell  */
+                                     /* (k_cell_scatter) where the cell changes 8 times or fewer, on average, along 64 consecutive triangles, else the two onesweep passes; a context's first */
+                                     /* step and the step after a redo take the passes; 1 always the passes; 2 always the cells.  Same keys and permutation either way (A/B, tests)           */
+    CD_DBG_GET_SORT_CELLS     = 22,  /* ... 1: the last sort ordered its global bits by cells, 0: by the two passes                                                                            */
+    CD_DBG_GET_CELL_STAT      = 23   /* ... the statistic of the last step: the cell changes along each 64 consecutive triangles (a group's first counts), summed over the ceil(n / 64) groups */
 };
 int cd_debug_option(cd_ctx *ctx, int key, int64_t value, int64_t *out);
 
