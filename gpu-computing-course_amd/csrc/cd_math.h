@@ -588,6 +588,70 @@ __device__ __forceinline__ ColumnTri column_tri(const d3 p, const int c, const d
     return r;
 }
 
+// ---------------------------------------------------------------- box against triangle (not reference behaviour)
+// box_tri(box; p0, p1, p2): does the triangle meet the CLOSED axis-aligned box {x1, x2, y1, y2, z1, z2} (touching counts; lo == hi on
+// an axis is allowed: a slab, a line, a point), and do all three vertices lie in it?  FP64 with this operation order, no contraction;
+// every difference, product and sum is rounded on its own.  The separating-axis test of a box and a triangle in a fixed order:
+//   1 gate  : per axis a = x, y, z, exact comparisons of the inputs: all three p_a < lo_a, or all three > hi_a: miss, code 1 + a.
+//   2 inside: all nine coordinates in the closed box (exact comparisons): hit, inside = 1, code 0.  Nothing further is evaluated --
+//             "a triangle wholly in the box is a hit" is a statement about comparisons, not about rounded arithmetic, and
+//             cd_boxes_count's contained subtrees rest on it (cd_boxes.h).
+//   2b vertex: any vertex in the closed box (exact comparisons): hit, inside = 0, code 0.  Nothing further is evaluated.  In exact
+//             arithmetic steps 3 and 4 separate no such triangle, so this changes no true answer; in FP64 it keeps a box that TOUCHES
+//             a vertex from losing the face to rounding.  A point box on vertex p1 has the true plane value d = n . (p0 - p1) = 0 and
+//             r = 0, and the rounded d is nonzero for about a third of a mesh's faces (3250 of 10 000 in the 10 k soup), which step 4
+//             would report as separated.
+//   3 edges : c_a = 0.5 lo_a + 0.5 hi_a, h_a = 0.5 hi_a - 0.5 lo_a, v_i = p_i - c, f0 = p1 - p0, f1 = p2 - p1, f2 = p0 - p2 (the input
+//             vertices).  Edge k = 0, 1, 2 and box axis j = 0, 1, 2 in lexicographic (k, j) order, a = (j + 1) % 3, b = (j + 2) % 3:
+//             q_i = v_i[b] f_k[a] - v_i[a] f_k[b],  r = h[a] |f_k[b]| + h[b] |f_k[a]|;  all three q_i > r, or all three < -r: miss,
+//             code 4 + 3 k + j.
+//   4 plane : n = f0 x f1, d = (n_x v0_x + n_y v0_y) + n_z v0_z, r = (h_x |n_x| + h_y |n_y|) + h_z |n_z|;  d > r or d < -r: miss,
+//             code 13.  Otherwise hit, inside = 0, code 0.
+// A miss reports the FIRST separating test in this order: the code is part of the contract.  Every comparison is written so that a NaN
+// separates nothing.  A degenerate triangle needs no special case: its zero edges and zero normal give 0 > 0, which is false, the
+// remaining axes are the complete set for the segment it is, and the gate alone is exact for the point it is.
+// Band: scaling box and triangle by 2^k changes nothing while no nonzero intermediate -- products of up to three coordinate
+// differences, so magnitudes around m^3 -- leaves the normal FP64 range: as ray_tri's, for inputs whose largest |coordinate| m is of
+// order 1 .. 16 with features down to about 2^-20 m, |k| <= 300.  Outside it the result follows this arithmetic, overflow included.
+struct BoxTri { bool hit, inside; uint32_t code; };
+// one edge axis: the three q and r of step 3 from the (a, b) coordinates; true: separated
+__device__ __forceinline__ bool box_tri_axis(const double v0a, const double v0b, const double v1a, const double v1b, const double v2a, const double v2b,
+                                             const double fa, const double fb, const double ha, const double hb)
+{
+    const double q0 = v0b * fa - v0a * fb, q1 = v1b * fa - v1a * fb, q2 = v2b * fa - v2a * fb;
+    const double r = ha * dabs(fb) + hb * dabs(fa);
+    const double nr = -r;
+    return (q0 > r && q1 > r && q2 > r) || (q0 < nr && q1 < nr && q2 < nr);
+}
+__device__ __forceinline__ BoxTri box_tri(const Box &bx, const d3 p0, const d3 p1, const d3 p2)
+{
+    BoxTri t{false, false, 0u};
+    if ((p0.x < bx.x1 && p1.x < bx.x1 && p2.x < bx.x1) || (p0.x > bx.x2 && p1.x > bx.x2 && p2.x > bx.x2)) { t.code = 1u; return t; }
+    if ((p0.y < bx.y1 && p1.y < bx.y1 && p2.y < bx.y1) || (p0.y > bx.y2 && p1.y > bx.y2 && p2.y > bx.y2)) { t.code = 2u; return t; }
+    if ((p0.z < bx.z1 && p1.z < bx.z1 && p2.z < bx.z1) || (p0.z > bx.z2 && p1.z > bx.z2 && p2.z > bx.z2)) { t.code = 3u; return t; }
+    auto in = [&](const d3 p) { return bx.x1 <= p.x && p.x <= bx.x2 && bx.y1 <= p.y && p.y <= bx.y2 && bx.z1 <= p.z && p.z <= bx.z2; };
+    const bool in0 = in(p0), in1 = in(p1), in2 = in(p2);
+    if (in0 || in1 || in2) { t.hit = true; t.inside = in0 && in1 && in2; return t; }
+    const d3 c{0.5 * bx.x1 + 0.5 * bx.x2, 0.5 * bx.y1 + 0.5 * bx.y2, 0.5 * bx.z1 + 0.5 * bx.z2};
+    const d3 h{0.5 * bx.x2 - 0.5 * bx.x1, 0.5 * bx.y2 - 0.5 * bx.y1, 0.5 * bx.z2 - 0.5 * bx.z1};
+    const d3 v0 = sub(p0, c), v1 = sub(p1, c), v2 = sub(p2, c);
+    const d3 f0 = sub(p1, p0), f1 = sub(p2, p1), f2 = sub(p0, p2);
+#define CD_BOX_TRI_EDGE(K, F)                                                                                                         \
+    if (box_tri_axis(v0.y, v0.z, v1.y, v1.z, v2.y, v2.z, F.y, F.z, h.y, h.z)) { t.code = 4u + 3u * K; return t; }                     \
+    if (box_tri_axis(v0.z, v0.x, v1.z, v1.x, v2.z, v2.x, F.z, F.x, h.z, h.x)) { t.code = 5u + 3u * K; return t; }                     \
+    if (box_tri_axis(v0.x, v0.y, v1.x, v1.y, v2.x, v2.y, F.x, F.y, h.x, h.y)) { t.code = 6u + 3u * K; return t; }
+    CD_BOX_TRI_EDGE(0u, f0)
+    CD_BOX_TRI_EDGE(1u, f1)
+    CD_BOX_TRI_EDGE(2u, f2)
+#undef CD_BOX_TRI_EDGE
+    const d3 n = cross(f0, f1);
+    const double d = (n.x * v0.x + n.y * v0.y) + n.z * v0.z;
+    const double r = (h.x * dabs(n.x) + h.y * dabs(n.y)) + h.z * dabs(n.z);
+    if (d > r || d < -r) { t.code = 13u; return t; }
+    t.hit = true;
+    return t;
+}
+
 // morton.h:7-29
 __device__ __forceinline__ uint64_t expand64(uint64_t v)
 {

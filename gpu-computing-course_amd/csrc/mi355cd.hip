@@ -18,6 +18,7 @@
 #include "cd_within.h"
 #include "cd_sweep.h"
 #include "cd_inside.h"
+#include "cd_boxes.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -434,6 +435,11 @@ struct cd_ctx {
     // sdist.state: the closest-point kernel's counters, sdist_in: k_points_inside's
     ItemBuf<PointState> inside, sdist;
     StateWords<PointState> sdist_in;
+    // box queries (cd_boxes_overlap_all, cd_boxes_count, cd_boxes.h): buffers of their own, allocated on first use.
+    // boxes_all.items: boxes [6 n];   boxes_all.vals: ids [cap] (u32) | inside [cap] (u8)
+    // boxes_count.block: boxes [6 n] (doubles) | count [n] | n_inside [n] (u32)
+    ItemRowsBuf boxes_all;
+    ItemBuf<PointState> boxes_count;
 };
 
 namespace {
@@ -463,7 +469,7 @@ void free_all(cd_ctx *c)
     c->prox.release(); c->cont.release(); c->ccd.release(); c->bw.release(); c->ccd_x1.release(); c->bw_x1a.release(); c->bw_x1b.release();
     for (SweptBuf &sw : c->swept) sw.release();
     c->rays.release(); c->points.release(); c->nearest.release(); c->nearest_self.release(); c->within.release(); c->rays_all.release(); c->sweep.release();
-    c->inside.release(); c->sdist.release(); c->sdist_in.release();
+    c->inside.release(); c->sdist.release(); c->sdist_in.release(); c->boxes_all.release(); c->boxes_count.release();
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -3206,6 +3212,92 @@ int cd_column_tri_points(const double *points, const double *tri, uint64_t n, in
     dev.back(E, d_e, 3 * n);
     dev.back(zc, d_z, n);
     dev.back(S, d_s, n);
+    return dev.rc();
+}
+// ---- box queries (cd_boxes.h) -----------------------------------------------------------------------------------------------------
+// Own buffers (items, candidates, rows, counters): nothing any other call keeps is touched.  The rows call is the all-results item
+// queries' pass; the count call is one kernel.
+constexpr uint64_t BOXES_ROW_BYTES = 4 + 1;                                 // device bytes a row besides (item, face): ID, inside
+constexpr uint64_t BOXES_COUNT_BYTES = 6 * 8 + 4 + 4;                       // device bytes an item: the box, count, n_inside
+// every bound is finite and lo <= hi on every axis (a NaN fails)
+static bool boxes_ok(const double *boxes, uint64_t n)
+{
+    for (uint64_t i = 0; i < 3 * n; ++i) {
+        const double lo = boxes[2 * i], hi = boxes[2 * i + 1];
+        if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo <= hi)) return false;
+    }
+    return true;
+}
+int cd_boxes_overlap_all(cd_ctx *c, const double *boxes, uint64_t n, uint32_t *rows, uint64_t cap_rows, uint64_t *n_rows, uint64_t *n_tested, const cd_box_rows *out)
+{
+    int rc = item_rows_args(c, boxes, n, rows, cap_rows, n_rows);
+    if (rc) return rc;
+    if (!boxes_ok(boxes, n)) return CD_ERR_ARG;                             // before anything is launched: nothing is written for a bad box
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { *n_rows = 0; if (n_tested) *n_tested = 0; return CD_OK; }
+    ItemRowsBuf &b = c->boxes_all;
+    if ((rc = b.ensure(n, 6 * 8, cap_rows, BOXES_ROW_BYTES))) return rc;
+    const cd_box_rows want = out ? *out : cd_box_rows{};
+    const uint64_t cap = b.vals.cap;
+    const double *d_boxes = reinterpret_cast<const double *>(b.items.d);
+    uint32_t *d_ids = reinterpret_cast<uint32_t *>(b.vals.d);
+    uint8_t *d_in = reinterpret_cast<uint8_t *>(d_ids + cap);
+    rc = item_rows_pass(c, b, boxes, 6, n, [&] {
+        k_boxes_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, c->stream>>>(c->d_recs32, c->d_root, (int)c->nt, c->d_os_ticket + 8, d_boxes, n, b.q.state.d,
+                                                                                        b.q.d_cand, b.q.shard_cap);
+        k_boxes_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, c->stream>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, d_boxes, b.q.state.d,
+                                                                                                  cap_rows, b.q.d_pairs, want.ids ? d_ids : nullptr, want.inside ? d_in : nullptr);
+    });
+    if (rc) return rc;
+    const uint64_t take = std::min<uint64_t>(b.q.state.h->n_pairs, cap_rows);
+    if ((rc = row_values(want.ids, d_ids, 1, take)) || (rc = row_values(want.inside, d_in, 1, take))) return rc;
+    if (n_tested) *n_tested = b.q.state.h->n_tested;
+    return b.q.results(rows, nullptr, nullptr, cap_rows, n_rows);
+}
+int cd_boxes_count(cd_ctx *c, const double *boxes, uint64_t n, int flags, uint32_t *count, uint32_t *n_inside, cd_box_info *info)
+{
+    if (!c || (flags & ~CD_BOX_ANY) || ((flags & CD_BOX_ANY) && n_inside) || n > 0xffffffffull || (n && (!boxes || !count))) return CD_ERR_ARG;
+    if (!boxes_ok(boxes, n)) return CD_ERR_ARG;                             // before anything is launched: nothing is written for a bad box
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { if (info) *info = cd_box_info{0, 0, 0}; return CD_OK; }
+    int rc = c->boxes_count.ensure(n, BOXES_COUNT_BYTES);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const uint64_t cap = c->boxes_count.block.cap;
+    double *d_boxes = reinterpret_cast<double *>(c->boxes_count.block.d);
+    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(d_boxes + 6 * cap), *d_nin = d_cnt + cap;
+    PointState *st = c->boxes_count.state.d, *h = c->boxes_count.state.h;
+    HIPCHK(hipMemcpyAsync(d_boxes, boxes, sizeof(double) * 6 * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(st, 0, sizeof(PointState), s));
+    const uint32_t grid = cdiv(n, BOXES_THREADS);
+    if (flags & CD_BOX_ANY)
+        k_boxes_count<true><<<grid, BOXES_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_verts, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, d_boxes, n, st, d_cnt, nullptr);
+    else
+        k_boxes_count<false><<<grid, BOXES_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_verts, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, d_boxes, n, st, d_cnt,
+                                                            n_inside ? d_nin : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h, st, sizeof(PointState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(count, d_cnt, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    if (n_inside) HIPCHK(hipMemcpyAsync(n_inside, d_nin, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (info) { info->n_found = h->n_found; info->node_visits = h->node_visits; info->tri_tests = h->tri_tests; }
+    return CD_OK;
+}
+int cd_box_tri_points(const double *boxes, const double *tri, uint64_t n, uint8_t *hit, uint8_t *inside, uint8_t *code)
+{
+    if (n == 0) return CD_OK;
+    if (!boxes || !tri || !hit) return CD_ERR_ARG;
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_b = dev.in(boxes, 6 * n), *d_t = dev.in(tri, 9 * n);
+    uint8_t *d_h = dev.out<uint8_t>(n), *d_i = dev.out<uint8_t>(n), *d_c = dev.out<uint8_t>(n);
+    if (dev.e == hipSuccess) {
+        k_box_tri_points<<<strided_grid(n, 256), 256>>>(d_b, d_t, n, d_h, d_i, d_c);
+        dev.e = hipGetLastError();
+    }
+    dev.back(hit, d_h, n);
+    dev.back(inside, d_i, n);
+    dev.back(code, d_c, n);
     return dev.rc();
 }
 }  // extern "C"

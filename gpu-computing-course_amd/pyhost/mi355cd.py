@@ -160,6 +160,30 @@ class CdInsideInfo(C.Structure):
 CD_INSIDE_PARITY = 1
 
 
+class CdBoxInfo(C.Structure):
+    _fields_ = [("n_found", C.c_uint64), ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64)]
+
+
+class CdBoxRows(C.Structure):
+    _fields_ = [("ids", C.c_void_p), ("inside", C.c_void_p)]
+
+
+CD_BOX_ANY = 1
+
+
+class _BoxRowArrays:
+    """The arrays of a boxes_overlap_all call with room for cap rows, and the cd_box_rows that points at them."""
+
+    def __init__(self, cap):
+        n = max(cap, 1)
+        self.ids = np.empty(n, dtype=np.uint32)
+        self.inside = np.empty(n, dtype=np.uint8)
+        self.out = CdBoxRows(self.ids.ctypes.data, self.inside.ctypes.data)
+
+    def take(self, got):
+        return tuple(a[:got].copy() for a in (self.ids, self.inside))
+
+
 class Nearest(collections.namedtuple("Nearest", "faces ids dist witness info")):
     """cd_nearest_between's rows: faces u32[n, 2] (face of self, face of other; NEAREST_NONE twice when nothing is within rmax),
     ids u32[n, 2], dist f64[n] (+inf then), witness (a Witness over the same rows, or None), info (CdNearestInfo)."""
@@ -266,6 +290,7 @@ EXPORTS = [
     "cd_points_within", "cd_cast_rays_all",
     "cd_sweep_points_all", "cd_sweep_points", "cd_pt_advance_points",
     "cd_points_inside", "cd_signed_distance", "cd_column_tri_points",
+    "cd_boxes_overlap_all", "cd_boxes_count", "cd_box_tri_points",
 ]
 
 _lib = None
@@ -368,6 +393,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_points_inside.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.POINTER(CdInsideInfo)]
     lib.cd_signed_distance.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CdPointInfo)]
     lib.cd_column_tri_points.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, vp, vp, vp]
+    lib.cd_boxes_overlap_all.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(CdBoxRows)]
+    lib.cd_boxes_count.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, C.POINTER(CdBoxInfo)]
+    lib.cd_box_tri_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -828,6 +856,31 @@ class CollisionDetector:
         self._chk("cd_signed_distance", rc)
         return sdist, face, ids, closest, uv, feature, inside.astype(bool), info
 
+    # ---- box queries against this mesh (cd_boxes_overlap_all, cd_boxes_count)
+    def boxes_overlap_all(self, lo, hi, cap: int = 1 << 20):
+        """cd_boxes_overlap_all on the tree that is there.  lo, hi: [n, 3], the closed boxes [lo, hi].  -> (rows[n, 2] (box index, face
+        index), ids[n], inside[n] (bool), n, rc): one row for EVERY (box, triangle) that box_tri hits -- the triangle meets the closed
+        box; inside: all three of its vertices lie in it.  n may exceed cap (rc = CD_OVERFLOW, cap rows are returned).  The rows come
+        in no order.  self.boxes_tested: box_tri evaluations made.  Boxes are walked in the order given: keep spatially coherent boxes
+        next to each other; a box around the whole mesh walks the whole tree in one lane (boxes_count does not)."""
+        boxes = pack_boxes(lo, hi)
+        self.boxes_tested, (rows, n, rc, vals) = self._pair_query("cd_boxes_overlap_all", (self._ctx, _ptr(boxes), boxes.shape[0]), cap, extra=_BoxRowArrays(cap))
+        return (rows, vals[0], vals[1].astype(bool), n, rc)
+
+    def boxes_count(self, lo, hi, any: bool = False):
+        """cd_boxes_count on the tree that is there.  lo, hi: [n, 3].  -> (count[n], n_inside[n], info): the number of rows each box has
+        in boxes_overlap_all and the number of those with inside; with any, count is 0 / 1 (the box meets a triangle: an occupancy
+        grid is one box a voxel) and n_inside is None.  info: CdBoxInfo (boxes with count > 0, boxes tested, box_tri evaluations).
+        A subtree that lies inside the box is counted without being walked."""
+        boxes = pack_boxes(lo, hi)
+        n = boxes.shape[0]
+        count = np.empty(n, dtype=np.uint32)
+        n_inside = None if any else np.empty(n, dtype=np.uint32)
+        info = CdBoxInfo()
+        rc = self.lib.cd_boxes_count(self._ctx, _ptr(boxes), n, CD_BOX_ANY if any else 0, _ptr(count), _ptr(n_inside), C.byref(info))
+        self._chk("cd_boxes_count", rc)
+        return count, n_inside, info
+
     def find_collisions(self, cap: int = 1 << 20):
         return self._pairs_call(self.lib.cd_find_collisions, "cd_find_collisions", cap)
 
@@ -1170,6 +1223,32 @@ def column_tri_points(points, tris, axis: int = 2):
     if rc != CD_OK:
         raise CdError("cd_column_tri_points", rc)
     return cover, above.astype(bool), E, zc, S
+
+
+def pack_boxes(lo, hi) -> np.ndarray:
+    """[n, 6] doubles {x1, x2, y1, y2, z1, z2}, the layout cd_boxes_overlap_all, cd_boxes_count and cd_root_box use."""
+    a = np.asarray(lo, dtype=np.float64).reshape(-1, 3)
+    b = np.asarray(hi, dtype=np.float64).reshape(-1, 3)
+    if a.shape != b.shape:
+        raise ValueError(f"{a.shape[0]} lower corners against {b.shape[0]} upper corners")
+    return np.ascontiguousarray(np.stack([a, b], axis=2).reshape(-1, 6))
+
+
+def box_tri_points(boxes, tris):
+    """box_tri (the per-pair predicate of the box queries) on explicit operands, on the device (cd_box_tri_points): boxes [n, 6]
+    {x1, x2, y1, y2, z1, z2}, tris [n, 3, 3] -> (hit[n] (bool), inside[n] (bool), code[n] (uint8: 0, or the first separating test))."""
+    b = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, 6))
+    p = np.ascontiguousarray(np.asarray(tris, dtype=np.float64).reshape(-1, 9))
+    if b.shape[0] != p.shape[0]:
+        raise ValueError(f"{b.shape[0]} boxes against {p.shape[0]} triangles")
+    n = b.shape[0]
+    hit = np.zeros(n, dtype=np.uint8)
+    inside = np.zeros(n, dtype=np.uint8)
+    code = np.zeros(n, dtype=np.uint8)
+    rc = load_library().cd_box_tri_points(_ptr(b), _ptr(p), n, _ptr(hit), _ptr(inside), _ptr(code))
+    if rc != CD_OK:
+        raise CdError("cd_box_tri_points", rc)
+    return hit.astype(bool), inside.astype(bool), code
 
 
 def pack_sweeps(p0, p1, dist) -> np.ndarray:

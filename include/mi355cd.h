@@ -922,6 +922,66 @@ int cd_signed_distance(cd_ctx *ctx, const double *points /* n x 3 */, uint64_t n
 int cd_column_tri_points(const double *points, const double *tri, uint64_t n, int axis, int8_t *cover, uint8_t *above, double *E,
                          double *zc, double *S);
 
+/* ---- box queries: every triangle that meets an axis-aligned box (not reference behaviour) ----
+ * Which triangles lie in this region?  One box a voxel of an occupancy grid, a brush or a trigger volume, the part of a garment in a
+ * region, triangles per cell, the surface voxels of a distance field's narrow band.  A box is six doubles {x1, x2, y1, y2, z1, z2},
+ * the layout of cd_root_box, and it is CLOSED: touching counts, and lo == hi on any axis is allowed (a slab, a line, a point).  This
+ * is deliberately not the strict overlap of box.cuh: a triangle lying in a voxel's face belongs to both voxels.
+ * box_tri(box; triangle p0 p1 p2) -> (hit, inside, code), FP64 with a fixed operation order and no contraction, every difference,
+ * product and sum rounded on its own (csrc/cd_math.h):
+ *   1 gate:   per axis a = x, y, z in that order, exact comparisons of the inputs: max(p0_a, p1_a, p2_a) < lo_a or min(...) > hi_a:
+ *             miss, code 1 + a;
+ *   2 inside: all three vertices in the closed box on all axes (exact comparisons): hit, inside = 1, code 0; nothing further is
+ *             evaluated;
+ *   2b vertex: any vertex in the closed box (exact comparisons): hit, inside = 0, code 0; nothing further is evaluated -- a box that
+ *             touches a vertex, a point box on it included, cannot lose the face to the rounding of steps 3 and 4;
+ *   3 edges:  c_a = 0.5 lo_a + 0.5 hi_a, h_a = 0.5 hi_a - 0.5 lo_a, v_i = p_i - c, f0 = p1 - p0, f1 = p2 - p1, f2 = p0 - p2; for edge
+ *             k = 0, 1, 2 and box axis j = 0, 1, 2 in lexicographic (k, j) order, a = (j + 1) % 3, b = (j + 2) % 3:
+ *             q_i = v_i[b] f_k[a] - v_i[a] f_k[b], r = h[a] |f_k[b]| + h[b] |f_k[a]|; min(q0, q1, q2) > r or max(q0, q1, q2) < -r:
+ *             miss, code 4 + 3 k + j;
+ *   4 plane:  n = f0 x f1 (each component x y - z w), d = (n_x v0_x + n_y v0_y) + n_z v0_z, r = (h_x |n_x| + h_y |n_y|) + h_z |n_z|;
+ *             d > r or d < -r: miss, code 13; otherwise hit, inside = 0, code 0.
+ * A miss reports the first separating test in this order.  A NaN separates nothing.  A degenerate triangle (a segment, a point) needs
+ * no special case.  Scaling box and triangle by 2^k changes nothing while no nonzero product of three coordinate differences leaves
+ * the normal FP64 range (ray_tri's band: |k| <= 300 for coordinates of order 1 .. 16); outside it the result follows the arithmetic.
+ *
+ * cd_boxes_overlap_all: one row for every (box k, face f) of this context that box_tri hits.  rows[2 r] = k, rows[2 r + 1] = f, the
+ * index in cd_create's face list; out->ids[r]: the face's ID; out->inside[r]: box_tri's inside.  out and each array in it may be
+ * NULL.  Everything else is cd_points_within's contract: the order of the rows is free and each (k, f) appears once; *n_rows is the
+ * true number of rows, CD_OVERFLOW when it exceeds cap_rows, and nothing is written at or past cap_rows in any array; cap_rows = 0
+ * counts only; n_tested (may be NULL): box_tri evaluations, a number of this tree.
+ *
+ * cd_boxes_count, by definition: count[k] is the number of rows item k has in cd_boxes_overlap_all, n_inside[k] (may be NULL) the
+ * number of those with inside = 1.  With CD_BOX_ANY count[k] is 0 or 1, equal to (count > 0), the walk of a box stops at its first
+ * hit, and n_inside must be NULL.  info (may be NULL): boxes with count > 0, boxes tested, box_tri evaluations -- numbers of this
+ * tree.  One kernel with integer sums in registers: no candidate buffer, nothing that can overflow.  A subtree whose stored box lies
+ * inside the query box is counted without being walked (every triangle in it takes rule 2), the whole tree included: a box around
+ * the mesh costs one test.
+ *
+ * Limits.  The rows call walks a box that meets the whole mesh in one lane.  Neighbours in the array share a wave: boxes that are
+ * neighbours in space should be neighbours in the array; the library does not sort them.  Oriented boxes and forms between two
+ * meshes are not built.
+ * Guarantee: the result depends on the mesh and the boxes only -- not on the Morton frame, CD_OPT_TRAVERSAL, CD_OPT_CELL_TABLE, the
+ * build variant or the order of the boxes.
+ * Needs a tree built from the current vertices (CD_ERR_ORDER otherwise, including after cd_update_vertices without a rebuild).
+ * CD_ERR_ARG: a NULL context; NULL boxes with n > 0; n > 2^32 - 1; NULL n_rows, or NULL rows with cap_rows > 0 (cd_boxes_overlap_all);
+ * NULL count with n > 0, flags other than 0 / CD_BOX_ANY, n_inside given with CD_BOX_ANY (cd_boxes_count); a bound that is not finite
+ * or lo > hi on an axis -- checked on the host before anything is launched, and nothing is written then.  n = 0 returns CD_OK.  The
+ * calls leave cd_stats, the last pair list, the order hint, a captured CD_OPT_GRAPH step and every other query's buffers as they
+ * were; they keep device buffers of their own (grown on demand; cd_destroy frees them) and run on the context's stream. */
+enum { CD_BOX_ANY = 1 };
+typedef struct cd_box_rows { uint32_t *ids; uint8_t *inside; } cd_box_rows;
+typedef struct cd_box_info { uint64_t n_found, node_visits, tri_tests; } cd_box_info;
+int cd_boxes_overlap_all(cd_ctx *ctx, const double *boxes /* n x 6 */, uint64_t n, uint32_t *rows, uint64_t cap_rows,
+                         uint64_t *n_rows, uint64_t *n_tested, const cd_box_rows *out);
+int cd_boxes_count(cd_ctx *ctx, const double *boxes /* n x 6 */, uint64_t n, int flags, uint32_t *count, uint32_t *n_inside,
+                   cd_box_info *info);
+/* box_tri on explicit operands (host pointers; no context): boxes is n x 6 doubles, tri n x 9 (p0, p1, p2).  hit[k], inside[k]: 0 / 1;
+ * code[k]: 0 for a hit, else the first separating test (1 .. 13).  hit is required, the others may be NULL.  CD_ERR_ARG: NULL boxes,
+ * tri or hit with n > 0; n = 0 returns CD_OK and writes nothing.  No argument is checked for finiteness: the arithmetic decides.  The
+ * pin of the device function. */
+int cd_box_tri_points(const double *boxes, const double *tri, uint64_t n, uint8_t *hit, uint8_t *inside, uint8_t *code);
+
 /* Library / build identification: "mi355cd <version> gfx950". */
 const char *cd_version(void);
 
