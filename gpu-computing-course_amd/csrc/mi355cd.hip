@@ -19,6 +19,7 @@
 #include "cd_sweep.h"
 #include "cd_inside.h"
 #include "cd_boxes.h"
+#include "cd_columns.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -242,29 +243,45 @@ struct DevArray {
     }
 };
 
-// What a per-item query (rays, closest points) owns: counters and ONE block of the items' inputs and results, which the entry point carves
+// What a per-item query (rays, closest points) owns: counters and ONE block of the items' inputs and results, whose columns are the
+// query's list in cd_columns.h (Cols: it gives ensure() the bytes an item and cols() the pointers)
 template <typename State>
 struct ItemBuf {
     StateWords<State> state;
     DevArray<char> block;
     void release() { state.release(); block.release(); }
-    int ensure(uint64_t n, uint64_t bytes_per_item) { const int rc = state.ensure(); return rc ? rc : block.ensure(n, bytes_per_item); }
+    template <class Cols, class... A> int ensure(uint64_t n, A... a) { const int rc = state.ensure(); return rc ? rc : block.ensure(n, column_bytes<Cols>(a...)); }
+    template <class Cols, class... A> Cols cols(A... a) const { return carve<Cols>(block.d, block.cap, a...); }
+    // what every call enqueues in front of its kernels (the items up, the counters zeroed) and behind them (the counters back)
+    int upload(hipStream_t s, double *d_items, const double *items, uint64_t doubles, uint64_t n)
+    {
+        HIPCHK(hipMemcpyAsync(d_items, items, sizeof(double) * doubles * n, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(state.d, 0, sizeof(State), s));
+        return CD_OK;
+    }
+    int launched(hipStream_t s)
+    {
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(state.h, state.d, sizeof(State), hipMemcpyDeviceToHost, s));
+        return CD_OK;
+    }
 };
 
 // What an all-results item query (cd_points_within, cd_cast_rays_all, cd_within.h) owns: a pair query's record -- counters, candidate
-// shards, the rows (d_pairs: item, face) and their dist / t (d_dists) -- the items, and ONE block of the rows' other values, which the
-// entry point carves
+// shards, the rows (d_pairs: item, face) and their dist / t (d_dists) -- the items, and ONE block of the rows' other values, whose
+// columns are the query's row list in cd_columns.h
 struct ItemRowsBuf {
     PairBuf<ProxState> q;
-    DevArray<char> items, vals;
+    DevArray<double> items; DevArray<char> vals;
     void release() { q.release(); items.release(); vals.release(); }
-    int ensure(uint64_t n, uint64_t bytes_per_item, uint64_t cap_rows, uint64_t bytes_per_row)
+    template <class Cols> int ensure(uint64_t n, uint64_t doubles_per_item, uint64_t cap_rows)
     {
         int rc = q.shard_cap ? CD_OK : q.alloc_cand(WITHIN_SHARD_FIRST);     // (before q.ensure, which would size the shards by a triangle count)
         if (!rc) rc = q.ensure(0, cap_rows);
-        if (!rc) rc = items.ensure(n, bytes_per_item);
-        return rc ? rc : vals.ensure(std::max<uint64_t>(cap_rows, 1), bytes_per_row);
+        if (!rc) rc = items.ensure(n, doubles_per_item);
+        return rc ? rc : vals.ensure(std::max<uint64_t>(cap_rows, 1), column_bytes<Cols>());
     }
+    template <class Cols> Cols cols() const { return carve<Cols>(vals.d, vals.cap); }
 };
 
 // What the swept-point queries (cd_sweep_points_all, cd_sweep_points, cd_sweep.h) own: an all-results item query's record for the rows,
@@ -408,36 +425,29 @@ struct cd_ctx {
     // the swept trees of the CCD passes: [0] this mesh's own (cd_find_ccd / cd_self_ccd), [1] b's, of cd_find_ccd_between with this context as a
     SweptBuf swept[2];
     int device = 0;                         // the HIP device ordinal current at cd_create (the between queries need both contexts on one device)
-    // ray queries (cd_cast_rays, cd_rays.h): buffers of their own, allocated on first use and grown to the largest ray count seen.
-    // rays.block: rays [7 n] | t [n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | side [n] (u8)
+    // The per-item queries' buffers, each query's own, allocated on first use and grown to the largest count seen.  What a block or a
+    // rows' vals holds, column by column, is the list in cd_columns.h named here.
+    // ray queries (cd_cast_rays, cd_rays.h).  rays.block: RayCols
     ItemBuf<RayState> rays;
-    // closest-point queries (cd_closest_points, cd_points.h): buffers of their own, as the rays'.
-    // points.block: points [4 n] | dist [n] | closest [3 n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | feature [n] | side [n] (u8)
+    // closest-point queries (cd_closest_points, cd_points.h).  points.block: PointCols
     ItemBuf<PointState> points;
-    // nearest triangle / separation distance against another mesh (cd_nearest_between, cd_nearest.h) with this context as a: buffers of
-    // their own, na + 1 rows (the last one: CD_NEAREST_MIN's).
-    // nearest.block: dist [n] | points [6 n] | bary [4 n] (doubles) | leaf pair [n] (uint2) | faces [2 n] | ids [2 n] (u32) | feature [2 n] (u8)
+    // nearest triangle / separation distance against another mesh (cd_nearest_between, cd_nearest.h) with this context as a: na + 1
+    // rows (the last one: CD_NEAREST_MIN's).  nearest.block: NearestCols(self = false)
     ItemBuf<NearestState> nearest;
-    // the same against the mesh itself (cd_nearest_self): nt + 1 rows of its own, with the faces that played A and B behind the IDs
-    // nearest_self.block: dist [n] | points [6 n] | bary [4 n] | leaf pair [n] | faces [2 n] | ids [2 n] | played faces [2 n] | feature [2 n]
+    // the same against the mesh itself (cd_nearest_self): nt + 1 rows of its own.  nearest_self.block: NearestCols(self = true)
     ItemBuf<NearestState> nearest_self;
-    // all-results item queries (cd_points_within, cd_cast_rays_all, cd_within.h): buffers of their own, allocated on first use.
-    // within.items: points [4 n];   within.vals: closest [3 cap] | uv [2 cap] (doubles) | ids [cap] (u32) | feature [cap] | side [cap] (u8)
-    // rays_all.items: rays [7 n];   rays_all.vals: uv [2 cap] (doubles) | ids [cap] (u32) | side [cap] (u8)
+    // all-results item queries (cd_points_within, cd_cast_rays_all, cd_within.h).
+    // within.items: points [4 n], within.vals: WithinRowCols;   rays_all.items: rays [7 n], rays_all.vals: RayRowCols
     ItemRowsBuf within, rays_all;
-    // swept-point queries (cd_sweep_points_all, cd_sweep_points, cd_sweep.h): buffers of their own, allocated on first use.
-    // sweep.rows.items: items [7 n];   sweep.rows.vals: toi [cap] | closest [3 cap] | uv [2 cap] (doubles) | ids [cap] (u32) | feature [cap] | side [cap] (u8)
-    // sweep.first.block: items [7 n] | toi [n] | dist [n] | closest [3 n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | feature [n] | side [n] (u8)
+    // swept-point queries (cd_sweep_points_all, cd_sweep_points, cd_sweep.h).
+    // sweep.rows.items: items [7 n], sweep.rows.vals: SweepRowCols;   sweep.first.block: SweepFirstCols
     SweepBuf sweep;
-    // inside / outside and signed distance (cd_points_inside, cd_signed_distance, cd_inside.h): buffers of their own, allocated on first use.
-    // inside.block: points [3 n] (doubles) | n_above [n] | n_below [n] (u32) | w_above [n] | w_below [n] (i32) | inside [n] (u8)
-    // sdist.block: points [4 n] | dist [n] | closest [3 n] | uv [2 n] (doubles) | face [n] | ids [n] (u32) | feature [n] | inside [n] (u8);
-    // sdist.state: the closest-point kernel's counters, sdist_in: k_points_inside's
+    // inside / outside and signed distance (cd_points_inside, cd_signed_distance, cd_inside.h).  inside.block: InsideCols;
+    // sdist.block: PointCols with inside for side; sdist.state: the closest-point kernel's counters, sdist_in: k_points_inside's
     ItemBuf<PointState> inside, sdist;
     StateWords<PointState> sdist_in;
-    // box queries (cd_boxes_overlap_all, cd_boxes_count, cd_boxes.h): buffers of their own, allocated on first use.
-    // boxes_all.items: boxes [6 n];   boxes_all.vals: ids [cap] (u32) | inside [cap] (u8)
-    // boxes_count.block: boxes [6 n] (doubles) | count [n] | n_inside [n] (u32)
+    // box queries (cd_boxes_overlap_all, cd_boxes_count, cd_boxes.h).
+    // boxes_all.items: boxes [6 n], boxes_all.vals: BoxRowCols;   boxes_count.block: BoxCountCols
     ItemRowsBuf boxes_all;
     ItemBuf<PointState> boxes_count;
 };
@@ -507,6 +517,20 @@ struct OneShot {
     }
     int rc() const { return e == hipSuccess ? CD_OK : -(int)e; }
 };
+
+// An optional output of a per-item query on the context's stream.  wanted: the launch argument of its column -- the kernel writes it
+// only if the caller asked; fetch: `elems` elements for each of n items copied back into the caller's array, if the caller asked
+template <typename H, typename T> T *wanted(const H *host, T *dev) { return host ? dev : nullptr; }
+template <typename T> int fetch(hipStream_t s, T *host, const T *dev, uint64_t elems, uint64_t n)
+{
+    if (host) HIPCHK(hipMemcpyAsync(host, dev, sizeof(T) * elems * n, hipMemcpyDeviceToHost, s));
+    return CD_OK;
+}
+// after the synchronisation: the counters every per-item query reports (what it found, boxes visited, triangles tested), if asked for
+template <class Info, class State> void item_info(Info *info, uint64_t found, const State *h)
+{
+    if (info) *info = Info{found, h->node_visits, h->tri_tests};
+}
 
 // pair buffers handed out by cd_alloc_host_pairs: pinned host memory the report kernel writes STRAIGHT into (no staging copy on the host)
 // (id: a buffer's serial number -- an address the allocator hands out again is a NEW buffer, with pages the device has never written)
@@ -2623,7 +2647,6 @@ int cd_tri_isect_points(const double *tri, uint64_t n, uint8_t *code, double *pa
 
 // ---- ray queries (cd_rays.h) ------------------------------------------------------------------------------------------------------
 // Own buffers (rays, results, counters): nothing any other call keeps is touched.
-constexpr uint64_t RAY_BYTES = 7 * 8 + 8 + 16 + 4 + 4 + 1;                  // device bytes a ray: the ray, t, uv, face, ID, side
 // every ray has a finite origin and direction, a direction that is not all zero and a tmax >= 0 (a NaN tmax fails the comparison)
 static bool rays_ok(const double *rays, uint64_t n)
 {
@@ -2643,29 +2666,20 @@ int cd_cast_rays(cd_ctx *c, const double *rays, uint64_t n, int flags, uint32_t 
     if (!rays_ok(rays, n)) return CD_ERR_ARG;                               // before anything is launched: nothing is written for a bad ray
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if (n == 0) { if (info) *info = cd_ray_info{0, 0, 0}; return CD_OK; }
-    int rc = c->rays.ensure(n, RAY_BYTES);
+    int rc = c->rays.ensure<RayCols>(n);
     if (rc) return rc;
     hipStream_t s = c->stream;
-    const uint64_t cap = c->rays.block.cap;
-    double *d_rays = reinterpret_cast<double *>(c->rays.block.d), *d_t = d_rays + 7 * cap, *d_uv = d_t + cap;
-    uint32_t *d_face = reinterpret_cast<uint32_t *>(d_uv + 2 * cap), *d_ids = d_face + cap;
-    uint8_t *d_side = reinterpret_cast<uint8_t *>(d_ids + cap);
-    HIPCHK(hipMemcpyAsync(d_rays, rays, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(c->rays.state.d, 0, sizeof(RayState), s));
+    const RayCols k = c->rays.cols<RayCols>();
+    if ((rc = c->rays.upload(s, k.rays, rays, 7, n))) return rc;
     const uint32_t grid = cdiv(n, RAY_THREADS);
-    if (any) k_cast_rays<true><<<grid, RAY_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_rays, n, c->rays.state.d,
-                                                            d_face, nullptr, nullptr, nullptr, nullptr);
-    else k_cast_rays<false><<<grid, RAY_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_rays, n, c->rays.state.d,
-                                                         d_face, ids ? d_ids : nullptr, t ? d_t : nullptr, uv ? d_uv : nullptr, side ? d_side : nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->rays.state.h, c->rays.state.d, sizeof(RayState), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(face, d_face, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (t) HIPCHK(hipMemcpyAsync(t, d_t, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    if (uv) HIPCHK(hipMemcpyAsync(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, s));
-    if (side) HIPCHK(hipMemcpyAsync(side, d_side, n, hipMemcpyDeviceToHost, s));
+    if (any) k_cast_rays<true><<<grid, RAY_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, k.rays, n, c->rays.state.d,
+                                                            k.face, nullptr, nullptr, nullptr, nullptr);
+    else k_cast_rays<false><<<grid, RAY_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, k.rays, n, c->rays.state.d,
+                                                         k.face, wanted(ids, k.ids), wanted(t, k.t), wanted(uv, k.uv), wanted(side, k.side));
+    if ((rc = c->rays.launched(s)) || (rc = fetch(s, face, k.face, 1, n)) || (rc = fetch(s, ids, k.ids, 1, n)) || (rc = fetch(s, t, k.t, 1, n)) ||
+        (rc = fetch(s, uv, k.uv, 2, n)) || (rc = fetch(s, side, k.side, 1, n))) return rc;
     HIPCHK(hipStreamSynchronize(s));
-    if (info) { info->n_hits = c->rays.state.h->n_hits; info->node_visits = c->rays.state.h->node_visits; info->tri_tests = c->rays.state.h->tri_tests; }
+    item_info(info, c->rays.state.h->n_hits, c->rays.state.h);
     return CD_OK;
 }
 int cd_ray_tri_points(const double *ray, const double *tri, uint64_t n, uint8_t *hit, double *t, double *uv, uint8_t *side)
@@ -2689,7 +2703,6 @@ int cd_ray_tri_points(const double *ray, const double *tri, uint64_t n, uint8_t 
 }
 // ---- closest-point queries (cd_points.h) ------------------------------------------------------------------------------------------
 // Own buffers (points, results, counters): nothing any other call keeps is touched.
-constexpr uint64_t POINT_BYTES = 4 * 8 + 8 + 24 + 16 + 4 + 4 + 1 + 1;       // device bytes a point: the point, dist, closest, uv, face, ID, feature, side
 // every point has finite coordinates and an rmax >= 0 (a NaN rmax fails the comparison)
 static bool points_ok(const double *points, uint64_t n)
 {
@@ -2707,32 +2720,22 @@ int cd_closest_points(cd_ctx *c, const double *points, uint64_t n, int flags, ui
     if (!points_ok(points, n)) return CD_ERR_ARG;                           // before anything is launched: nothing is written for a bad point
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if (n == 0) { if (info) *info = cd_point_info{0, 0, 0}; return CD_OK; }
-    int rc = c->points.ensure(n, POINT_BYTES);
+    int rc = c->points.ensure<PointCols>(n);
     if (rc) return rc;
     hipStream_t s = c->stream;
-    const uint64_t cap = c->points.block.cap;
-    double *d_pts = reinterpret_cast<double *>(c->points.block.d), *d_dist = d_pts + 4 * cap, *d_q = d_dist + cap, *d_uv = d_q + 3 * cap;
-    uint32_t *d_face = reinterpret_cast<uint32_t *>(d_uv + 2 * cap), *d_ids = d_face + cap;
-    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + cap), *d_side = d_feat + cap;
-    HIPCHK(hipMemcpyAsync(d_pts, points, sizeof(double) * 4 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(c->points.state.d, 0, sizeof(PointState), s));
+    const PointCols k = c->points.cols<PointCols>();
+    if ((rc = c->points.upload(s, k.pts, points, 4, n))) return rc;
     const uint32_t grid = cdiv(n, POINT_THREADS);
-    if (any) k_closest_points<true><<<grid, POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_pts, n, c->points.state.d,
-                                                                  d_face, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    else k_closest_points<false><<<grid, POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_pts, n, c->points.state.d,
-                                                               d_face, ids ? d_ids : nullptr, dist ? d_dist : nullptr, closest ? d_q : nullptr, uv ? d_uv : nullptr,
-                                                               feature ? d_feat : nullptr, side ? d_side : nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->points.state.h, c->points.state.d, sizeof(PointState), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(face, d_face, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    if (closest) HIPCHK(hipMemcpyAsync(closest, d_q, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
-    if (uv) HIPCHK(hipMemcpyAsync(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, s));
-    if (feature) HIPCHK(hipMemcpyAsync(feature, d_feat, n, hipMemcpyDeviceToHost, s));
-    if (side) HIPCHK(hipMemcpyAsync(side, d_side, n, hipMemcpyDeviceToHost, s));
+    if (any) k_closest_points<true><<<grid, POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, k.pts, n, c->points.state.d,
+                                                                  k.face, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    else k_closest_points<false><<<grid, POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, k.pts, n, c->points.state.d,
+                                                               k.face, wanted(ids, k.ids), wanted(dist, k.dist), wanted(closest, k.closest), wanted(uv, k.uv),
+                                                               wanted(feature, k.feature), wanted(side, k.side));
+    if ((rc = c->points.launched(s)) || (rc = fetch(s, face, k.face, 1, n)) || (rc = fetch(s, ids, k.ids, 1, n)) || (rc = fetch(s, dist, k.dist, 1, n)) ||
+        (rc = fetch(s, closest, k.closest, 3, n)) || (rc = fetch(s, uv, k.uv, 2, n)) || (rc = fetch(s, feature, k.feature, 1, n)) ||
+        (rc = fetch(s, side, k.side, 1, n))) return rc;
     HIPCHK(hipStreamSynchronize(s));
-    if (info) { info->n_found = c->points.state.h->n_found; info->node_visits = c->points.state.h->node_visits; info->tri_tests = c->points.state.h->tri_tests; }
+    item_info(info, c->points.state.h->n_found, c->points.state.h);
     return CD_OK;
 }
 int cd_pt_tri_points(const double *points, const double *tri, uint64_t n, double *dist, double *closest, double *uv, uint8_t *feature, uint8_t *side)
@@ -2758,8 +2761,6 @@ int cd_pt_tri_points(const double *points, const double *tri, uint64_t n, double
 // ---- all-results item queries (cd_within.h) -----------------------------------------------------------------------------------------
 // Own buffers (items, candidates, rows, counters): nothing any other call keeps is touched.  The pass is the pair queries': descent, exact
 // stage, the counters' read-back, one synchronisation; a shard that overflowed grows the candidate buffer and the pass runs again.
-constexpr uint64_t WITHIN_ROW_BYTES = 24 + 16 + 4 + 1 + 1;                  // device bytes a row besides (item, face) and dist: closest, uv, ID, feature, side
-constexpr uint64_t RAYS_ALL_ROW_BYTES = 16 + 4 + 1;                         // besides (item, face) and t: uv, ID, side
 // the argument rules both calls share, before the items are read
 static int item_rows_args(const cd_ctx *c, const double *items, uint64_t n, const uint32_t *rows, uint64_t cap_rows, const uint64_t *n_rows)
 {
@@ -2798,24 +2799,21 @@ int cd_points_within(cd_ctx *c, const double *points, uint64_t n, uint32_t *rows
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if (n == 0) { *n_rows = 0; if (n_tested) *n_tested = 0; return CD_OK; }
     ItemRowsBuf &b = c->within;
-    if ((rc = b.ensure(n, 4 * 8, cap_rows, WITHIN_ROW_BYTES))) return rc;
+    if ((rc = b.ensure<WithinRowCols>(n, 4, cap_rows))) return rc;
     const cd_point_rows want = out ? *out : cd_point_rows{};
-    const uint64_t cap = b.vals.cap;
-    double *d_pts = reinterpret_cast<double *>(b.items.d), *d_q = reinterpret_cast<double *>(b.vals.d), *d_uv = d_q + 3 * cap;
-    uint32_t *d_ids = reinterpret_cast<uint32_t *>(d_uv + 2 * cap);
-    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + cap), *d_side = d_feat + cap;
+    const WithinRowCols k = b.cols<WithinRowCols>();
     rc = item_rows_pass(c, b, points, 4, n, [&] {
-        k_within_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, c->stream>>>(c->d_recs32, c->d_root, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, d_pts, n,
+        k_within_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, c->stream>>>(c->d_recs32, c->d_root, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, b.items.d, n,
                                                                                          b.q.state.d, b.q.d_cand, b.q.shard_cap);
-        k_within_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, c->stream>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, d_pts, b.q.state.d,
-                                                                                                   cap_rows, b.q.d_pairs, want.ids ? d_ids : nullptr, want.dist ? b.q.d_dists : nullptr,
-                                                                                                   want.closest ? d_q : nullptr, want.uv ? d_uv : nullptr,
-                                                                                                   want.feature ? d_feat : nullptr, want.side ? d_side : nullptr);
+        k_within_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, c->stream>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, b.items.d, b.q.state.d,
+                                                                                                   cap_rows, b.q.d_pairs, wanted(want.ids, k.ids), wanted(want.dist, b.q.d_dists),
+                                                                                                   wanted(want.closest, k.closest), wanted(want.uv, k.uv),
+                                                                                                   wanted(want.feature, k.feature), wanted(want.side, k.side));
     });
     if (rc) return rc;
     const uint64_t take = std::min<uint64_t>(b.q.state.h->n_pairs, cap_rows);
-    if ((rc = row_values(want.ids, d_ids, 1, take)) || (rc = row_values(want.closest, d_q, 3, take)) || (rc = row_values(want.uv, d_uv, 2, take)) ||
-        (rc = row_values(want.feature, d_feat, 1, take)) || (rc = row_values(want.side, d_side, 1, take))) return rc;
+    if ((rc = row_values(want.ids, k.ids, 1, take)) || (rc = row_values(want.closest, k.closest, 3, take)) || (rc = row_values(want.uv, k.uv, 2, take)) ||
+        (rc = row_values(want.feature, k.feature, 1, take)) || (rc = row_values(want.side, k.side, 1, take))) return rc;
     if (n_tested) *n_tested = b.q.state.h->n_tested;
     return b.q.results(rows, nullptr, want.dist, cap_rows, n_rows);
 }
@@ -2827,22 +2825,19 @@ int cd_cast_rays_all(cd_ctx *c, const double *rays, uint64_t n, uint32_t *rows, 
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if (n == 0) { *n_rows = 0; if (n_tested) *n_tested = 0; return CD_OK; }
     ItemRowsBuf &b = c->rays_all;
-    if ((rc = b.ensure(n, 7 * 8, cap_rows, RAYS_ALL_ROW_BYTES))) return rc;
+    if ((rc = b.ensure<RayRowCols>(n, 7, cap_rows))) return rc;
     const cd_ray_rows want = out ? *out : cd_ray_rows{};
-    const uint64_t cap = b.vals.cap;
-    double *d_rays = reinterpret_cast<double *>(b.items.d), *d_uv = reinterpret_cast<double *>(b.vals.d);
-    uint32_t *d_ids = reinterpret_cast<uint32_t *>(d_uv + 2 * cap);
-    uint8_t *d_side = reinterpret_cast<uint8_t *>(d_ids + cap);
+    const RayRowCols k = b.cols<RayRowCols>();
     rc = item_rows_pass(c, b, rays, 7, n, [&] {
-        k_rays_all_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, c->stream>>>(c->d_recs32, c->d_root, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, d_rays, n,
+        k_rays_all_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, c->stream>>>(c->d_recs32, c->d_root, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, b.items.d, n,
                                                                                            b.q.state.d, b.q.d_cand, b.q.shard_cap);
-        k_rays_all_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, c->stream>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, d_rays,
-                                                                                                     b.q.state.d, cap_rows, b.q.d_pairs, want.ids ? d_ids : nullptr,
-                                                                                                     want.t ? b.q.d_dists : nullptr, want.uv ? d_uv : nullptr, want.side ? d_side : nullptr);
+        k_rays_all_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, c->stream>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, b.items.d,
+                                                                                                     b.q.state.d, cap_rows, b.q.d_pairs, wanted(want.ids, k.ids),
+                                                                                                     wanted(want.t, b.q.d_dists), wanted(want.uv, k.uv), wanted(want.side, k.side));
     });
     if (rc) return rc;
     const uint64_t take = std::min<uint64_t>(b.q.state.h->n_pairs, cap_rows);
-    if ((rc = row_values(want.ids, d_ids, 1, take)) || (rc = row_values(want.uv, d_uv, 2, take)) || (rc = row_values(want.side, d_side, 1, take))) return rc;
+    if ((rc = row_values(want.ids, k.ids, 1, take)) || (rc = row_values(want.uv, k.uv, 2, take)) || (rc = row_values(want.side, k.side, 1, take))) return rc;
     if (n_tested) *n_tested = b.q.state.h->n_tested;
     return b.q.results(rows, nullptr, want.t, cap_rows, n_rows);
 }
@@ -2850,8 +2845,6 @@ int cd_cast_rays_all(cd_ctx *c, const double *rays, uint64_t n, uint32_t *rows, 
 // Own buffers (items, skip_vertex, x1, swept records and their counters, candidates, rows): nothing any other call keeps is touched --
 // swept[0] / swept[1] and what cd_debug_swept reports of them included.  The all-rows call is the all-results item queries' pass with
 // the swept refit in front of the descent; the first-contact call is one kernel behind the refit.
-constexpr uint64_t SWEEP_ROW_BYTES = 8 + 24 + 16 + 4 + 1 + 1;               // device bytes a row besides (item, face) and dist: toi, closest, uv, ID, feature, side
-constexpr uint64_t SWEEP_FIRST_BYTES = 7 * 8 + 8 + 8 + 24 + 16 + 4 + 4 + 1 + 1;   // device bytes an item: the item, toi, dist, closest, uv, face, ID, feature, side
 // every item has six finite coordinates and a dist that is finite and > 0 (ccd_dist_ok: a NaN fails)
 static bool sweeps_ok(const double *items, uint64_t n)
 {
@@ -2893,32 +2886,29 @@ int cd_sweep_points_all(cd_ctx *c, const double *verts_end, const double *items,
     if (n == 0) { *n_rows = 0; if (info) *info = cd_ccd_info{0, 0, 0, 0}; return CD_OK; }
     SweepBuf &sb = c->sweep;
     ItemRowsBuf &b = sb.rows;
-    if ((rc = b.ensure(n, 7 * 8, cap_rows, SWEEP_ROW_BYTES))) return rc;
+    if ((rc = b.ensure<SweepRowCols>(n, 7, cap_rows))) return rc;
     const double *x1 = nullptr; const uint32_t *d_skip = nullptr;
     if ((rc = sweep_inputs(c, verts_end, skip_vertex, n, x1, d_skip))) return rc;
     const cd_sweep_rows want = out ? *out : cd_sweep_rows{};
-    const uint64_t cap = b.vals.cap;
-    double *d_items = reinterpret_cast<double *>(b.items.d), *d_toi = reinterpret_cast<double *>(b.vals.d), *d_q = d_toi + cap, *d_uv = d_q + 3 * cap;
-    uint32_t *d_ids = reinterpret_cast<uint32_t *>(d_uv + 2 * cap);
-    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + cap), *d_side = d_feat + cap;
+    const SweepRowCols k = b.cols<SweepRowCols>();
     int erc = CD_OK;                                                        // the first error of a pass's own enqueues
     rc = item_rows_pass(c, b, items, 7, n, [&] {
         hipStream_t s = c->stream;
         if ((erc = sweep_refit(c, x1))) return;
-        k_sweep_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(sb.swept.d_recs, c->d_root, (int)c->nt, c->d_os_ticket + 8, d_items, n, sb.cst.d,
+        k_sweep_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(sb.swept.d_recs, c->d_root, (int)c->nt, c->d_os_ticket + 8, b.items.d, n, sb.cst.d,
                                                                                  b.q.state.d, b.q.d_cand, b.q.shard_cap);
-        k_sweep_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, x1, d_items, d_skip,
-                                                                                          b.q.state.d, sb.cst.d, cap_rows, b.q.d_pairs, want.ids ? d_ids : nullptr,
-                                                                                          want.toi ? d_toi : nullptr, want.dist ? b.q.d_dists : nullptr,
-                                                                                          want.closest ? d_q : nullptr, want.uv ? d_uv : nullptr,
-                                                                                          want.feature ? d_feat : nullptr, want.side ? d_side : nullptr);
+        k_sweep_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, x1, b.items.d, d_skip,
+                                                                                          b.q.state.d, sb.cst.d, cap_rows, b.q.d_pairs, wanted(want.ids, k.ids),
+                                                                                          wanted(want.toi, k.toi), wanted(want.dist, b.q.d_dists),
+                                                                                          wanted(want.closest, k.closest), wanted(want.uv, k.uv),
+                                                                                          wanted(want.feature, k.feature), wanted(want.side, k.side));
         const hipError_t e = hipMemcpyAsync(sb.cst.h, sb.cst.d, sizeof(CcdState), hipMemcpyDeviceToHost, s);
         if (e != hipSuccess) erc = -(int)e;
     });
     if (rc || (rc = erc)) return rc;
     const uint64_t take = std::min<uint64_t>(b.q.state.h->n_pairs, cap_rows);
-    if ((rc = row_values(want.ids, d_ids, 1, take)) || (rc = row_values(want.toi, d_toi, 1, take)) || (rc = row_values(want.closest, d_q, 3, take)) ||
-        (rc = row_values(want.uv, d_uv, 2, take)) || (rc = row_values(want.feature, d_feat, 1, take)) || (rc = row_values(want.side, d_side, 1, take))) return rc;
+    if ((rc = row_values(want.ids, k.ids, 1, take)) || (rc = row_values(want.toi, k.toi, 1, take)) || (rc = row_values(want.closest, k.closest, 3, take)) ||
+        (rc = row_values(want.uv, k.uv, 2, take)) || (rc = row_values(want.feature, k.feature, 1, take)) || (rc = row_values(want.side, k.side, 1, take))) return rc;
     if (info) {
         uint64_t cand = 0;
         for (int i = 0; i < NSHARD; ++i) cand += b.q.state.h->shard[i * PROX_SHARD_STRIDE];
@@ -2934,34 +2924,22 @@ int cd_sweep_points(cd_ctx *c, const double *verts_end, const double *items, uin
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if (n == 0) { if (info) *info = cd_point_info{0, 0, 0}; return CD_OK; }
     SweepBuf &sb = c->sweep;
-    int rc = sb.first.ensure(n, SWEEP_FIRST_BYTES);
+    int rc = sb.first.ensure<SweepFirstCols>(n);
     if (rc) return rc;
     const double *x1 = nullptr; const uint32_t *d_skip = nullptr;
     if ((rc = sweep_inputs(c, verts_end, skip_vertex, n, x1, d_skip))) return rc;
     hipStream_t s = c->stream;
-    const uint64_t cap = sb.first.block.cap;
-    double *d_items = reinterpret_cast<double *>(sb.first.block.d), *d_toi = d_items + 7 * cap, *d_dist = d_toi + cap, *d_q = d_dist + cap, *d_uv = d_q + 3 * cap;
-    uint32_t *d_face = reinterpret_cast<uint32_t *>(d_uv + 2 * cap), *d_ids = d_face + cap;
-    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + cap), *d_side = d_feat + cap;
-    HIPCHK(hipMemcpyAsync(d_items, items, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(sb.first.state.d, 0, sizeof(PointState), s));
-    if ((rc = sweep_refit(c, x1))) return rc;
+    const SweepFirstCols k = sb.first.cols<SweepFirstCols>();
+    if ((rc = sb.first.upload(s, k.items, items, 7, n)) || (rc = sweep_refit(c, x1))) return rc;
     k_sweep_first<<<cdiv(n, SWEEP_THREADS), SWEEP_THREADS, 0, s>>>(sb.swept.d_recs, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, x1, (int)c->nt, c->d_os_ticket + 8,
-                                                                   d_items, d_skip, n, sb.cst.d, sb.first.state.d, d_face, ids ? d_ids : nullptr, toi ? d_toi : nullptr,
-                                                                   dist ? d_dist : nullptr, closest ? d_q : nullptr, uv ? d_uv : nullptr,
-                                                                   feature ? d_feat : nullptr, side ? d_side : nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(sb.first.state.h, sb.first.state.d, sizeof(PointState), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(face, d_face, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (toi) HIPCHK(hipMemcpyAsync(toi, d_toi, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    if (closest) HIPCHK(hipMemcpyAsync(closest, d_q, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
-    if (uv) HIPCHK(hipMemcpyAsync(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, s));
-    if (feature) HIPCHK(hipMemcpyAsync(feature, d_feat, n, hipMemcpyDeviceToHost, s));
-    if (side) HIPCHK(hipMemcpyAsync(side, d_side, n, hipMemcpyDeviceToHost, s));
+                                                                   k.items, d_skip, n, sb.cst.d, sb.first.state.d, k.face, wanted(ids, k.ids), wanted(toi, k.toi),
+                                                                   wanted(dist, k.dist), wanted(closest, k.closest), wanted(uv, k.uv),
+                                                                   wanted(feature, k.feature), wanted(side, k.side));
+    if ((rc = sb.first.launched(s)) || (rc = fetch(s, face, k.face, 1, n)) || (rc = fetch(s, ids, k.ids, 1, n)) || (rc = fetch(s, toi, k.toi, 1, n)) ||
+        (rc = fetch(s, dist, k.dist, 1, n)) || (rc = fetch(s, closest, k.closest, 3, n)) || (rc = fetch(s, uv, k.uv, 2, n)) ||
+        (rc = fetch(s, feature, k.feature, 1, n)) || (rc = fetch(s, side, k.side, 1, n))) return rc;
     HIPCHK(hipStreamSynchronize(s));
-    if (info) { info->n_found = sb.first.state.h->n_found; info->node_visits = sb.first.state.h->node_visits; info->tri_tests = sb.first.state.h->tri_tests; }
+    item_info(info, sb.first.state.h->n_found, sb.first.state.h);
     return CD_OK;
 }
 int cd_pt_advance_points(const double *items, const double *tri, uint64_t n, double *toi, double *dist, double *closest, double *uv, uint8_t *feature, uint8_t *side,
@@ -2990,10 +2968,56 @@ int cd_pt_advance_points(const double *items, const double *tri, uint64_t n, dou
     dev.back(evals, d_e, n);
     return dev.rc();
 }
-// ---- nearest triangle and separation distance between two meshes (cd_nearest.h) ---------------------------------------------------
-// Everything runs on a's stream, in buffers a owns (rows, leaf pairs, witness, counters): nothing any other call keeps is touched.  Both
-// trees are finished (every call of the library blocks); b's stream is drained all the same before its records are read on a's.
-constexpr uint64_t NEAREST_BYTES = 8 + 48 + 32 + 8 + 8 + 8 + 2;             // device bytes a row: dist, points, bary, leaf pair, faces, IDs, feature
+// ---- nearest triangle and separation distance: between two meshes, and of a mesh against itself (cd_nearest.h) ---------------------
+// Everything runs on a's stream, in buffers a owns (rows, leaf pairs, witness, counters), with ONE synchronisation: nothing any other
+// call keeps is touched.  b == a is the mesh against itself (cd_nearest_self: the nearest NON-NEIGHBOURING triangle), which differs in
+// its kernel and in w->faces: those are the faces that PLAYED A and B (not own, partner), a column of their own that k_pair_witness
+// writes from the leaf pairs -- so there it runs whenever w asks for anything, and for faces alone it evaluates nothing.
+#ifndef CD_NEAREST_SELF_SHARED_BOUND
+#define CD_NEAREST_SELF_SHARED_BOUND 1                                      // (0: CD_NEAREST_MIN from the plain kernel's rows -- the build the shared bound was measured against)
+#endif
+using NearestRows = NearestCols<uint2>;
+static int nearest_rows(cd_ctx *a, cd_ctx *b, ItemBuf<NearestState> &nb, double rmax, bool mn, uint32_t *faces, uint32_t *ids, double *dist, const cd_witness_out *w,
+                        cd_nearest_info *info)
+{
+    const bool self = a == b;
+    const uint64_t na = a->nt;
+    const cd_witness_out want = w ? *w : cd_witness_out{};
+    hipStream_t s = a->stream;
+    const NearestRows k = nb.cols<NearestRows>(self);
+    NearestState *st = nb.state.d, *h = nb.state.h;
+    *h = NearestState{};
+    std::memcpy(&h->min_bits, &rmax, sizeof rmax);                          // the shared bound starts at rmax
+    HIPCHK(hipMemcpyAsync(st, h, sizeof(NearestState), hipMemcpyHostToDevice, s));
+    const uint32_t grid = cdiv(na, NEAREST_THREADS);
+#define CD_NEAREST_SELF(SHARED) k_nearest_self<SHARED><<<grid, NEAREST_THREADS, 0, s>>>(a->d_recs32, a->d_root, a->d_leaf, a->d_perm[0], a->d_verts, a->d_boxes, (int)na, rmax, st, \
+                                                                                      k.faces, k.ids, k.dist, k.leaf)
+#define CD_NEAREST_BETWEEN(MIN) k_nearest_between<MIN><<<grid, NEAREST_THREADS, 0, s>>>(b->d_recs32, b->d_root, b->d_leaf, b->d_perm[0], b->d_verts, b->d_boxes, (int)b->nt, \
+                                                                                      a->d_leaf, a->d_perm[0], a->d_verts, a->d_boxes, (int)na, rmax, st, k.faces, k.ids, k.dist, k.leaf)
+    if (self && mn) CD_NEAREST_SELF(CD_NEAREST_SELF_SHARED_BOUND != 0);
+    else if (self) CD_NEAREST_SELF(false);
+    else if (mn) CD_NEAREST_BETWEEN(true);
+    else CD_NEAREST_BETWEEN(false);
+#undef CD_NEAREST_SELF
+#undef CD_NEAREST_BETWEEN
+    if (mn) k_nearest_min<<<1, NEAREST_MIN_THREADS, 0, s>>>(na, na, st, k.faces, k.ids, k.dist, k.leaf);
+    const uint64_t first = mn ? na : 0, rows = mn ? 1 : na;                 // the rows the caller gets
+    const uint32_t *w_faces = self ? k.played : k.faces;                    // (between two meshes the faces that played A and B are the row's own)
+    if (want.points || want.bary || want.feature || (self && want.faces))
+        k_pair_witness<false><<<cdiv(rows, WITNESS_THREADS), WITNESS_THREADS, 0, s>>>(k.leaf + first, rows, a->d_leaf, a->d_perm[0], a->d_verts, nullptr,
+                                                                                      b->d_leaf, b->d_perm[0], b->d_verts, nullptr, nullptr,
+                                                                                      self ? wanted(want.faces, k.played + 2 * first) : nullptr,
+                                                                                      wanted(want.points, k.points + 6 * first), wanted(want.bary, k.bary + 4 * first),
+                                                                                      wanted(want.feature, k.feature + 2 * first));
+    int rc;
+    if ((rc = nb.launched(s)) || (rc = fetch(s, faces, k.faces + 2 * first, 2, rows)) || (rc = fetch(s, want.faces, w_faces + 2 * first, 2, rows)) ||
+        (rc = fetch(s, ids, k.ids + 2 * first, 2, rows)) || (rc = fetch(s, dist, k.dist + first, 1, rows)) || (rc = fetch(s, want.points, k.points + 6 * first, 6, rows)) ||
+        (rc = fetch(s, want.bary, k.bary + 4 * first, 4, rows)) || (rc = fetch(s, want.feature, k.feature + 2 * first, 2, rows))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    item_info(info, h->n_found, h);
+    return CD_OK;
+}
+// Both trees are finished (every call of the library blocks); b's stream is drained all the same before its records are read on a's.
 int cd_nearest_between(cd_ctx *a, cd_ctx *b, double rmax, int flags, uint32_t *faces, uint32_t *ids, double *dist, const cd_witness_out *w, cd_nearest_info *info)
 {
     const bool mn = flags == CD_NEAREST_MIN;
@@ -3001,107 +3025,20 @@ int cd_nearest_between(cd_ctx *a, cd_ctx *b, double rmax, int flags, uint32_t *f
     if (rc) return rc;
     if (!(rmax >= 0.0) || (flags != 0 && !mn)) return CD_ERR_ARG;          // (a NaN rmax fails the comparison)
     if (a->stage < ST_REFIT || b->stage < ST_REFIT) return CD_ERR_ORDER;
-    const uint64_t na = a->nt;
-    if ((rc = a->nearest.ensure(na + 1, NEAREST_BYTES))) return rc;
+    if ((rc = a->nearest.ensure<NearestRows>(a->nt + 1ull, false))) return rc;
     HIPCHK(hipStreamSynchronize(b->stream));
-    hipStream_t s = a->stream;
-    const uint64_t cap = a->nearest.block.cap;
-    double *d_dist = reinterpret_cast<double *>(a->nearest.block.d), *d_points = d_dist + cap, *d_bary = d_points + 6 * cap;
-    uint2 *d_leaf = reinterpret_cast<uint2 *>(d_bary + 4 * cap);
-    uint32_t *d_faces = reinterpret_cast<uint32_t *>(d_leaf + cap), *d_ids = d_faces + 2 * cap;
-    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + 2 * cap);
-    NearestState *st = a->nearest.state.d, *h = a->nearest.state.h;
-    *h = NearestState{};
-    std::memcpy(&h->min_bits, &rmax, sizeof rmax);                          // the shared bound starts at rmax
-    HIPCHK(hipMemcpyAsync(st, h, sizeof(NearestState), hipMemcpyHostToDevice, s));
-    const uint32_t grid = cdiv(na, NEAREST_THREADS);
-    if (mn) {
-        k_nearest_between<true><<<grid, NEAREST_THREADS, 0, s>>>(b->d_recs32, b->d_root, b->d_leaf, b->d_perm[0], b->d_verts, b->d_boxes, (int)b->nt,
-                                                                 a->d_leaf, a->d_perm[0], a->d_verts, a->d_boxes, (int)na, rmax, st, d_faces, d_ids, d_dist, d_leaf);
-        k_nearest_min<<<1, NEAREST_MIN_THREADS, 0, s>>>(na, na, st, d_faces, d_ids, d_dist, d_leaf);
-    } else {
-        k_nearest_between<false><<<grid, NEAREST_THREADS, 0, s>>>(b->d_recs32, b->d_root, b->d_leaf, b->d_perm[0], b->d_verts, b->d_boxes, (int)b->nt,
-                                                                  a->d_leaf, a->d_perm[0], a->d_verts, a->d_boxes, (int)na, rmax, st, d_faces, d_ids, d_dist, d_leaf);
-    }
-    const uint64_t first = mn ? na : 0, rows = mn ? 1 : na;                 // the rows the caller gets
-    const bool wit = w && (w->points || w->bary || w->feature);
-    if (wit)
-        k_pair_witness<false><<<cdiv(rows, WITNESS_THREADS), WITNESS_THREADS, 0, s>>>(d_leaf + first, rows, a->d_leaf, a->d_perm[0], a->d_verts, nullptr,
-                                                                                      b->d_leaf, b->d_perm[0], b->d_verts, nullptr, nullptr, nullptr,
-                                                                                      w->points ? d_points + 6 * first : nullptr, w->bary ? d_bary + 4 * first : nullptr,
-                                                                                      w->feature ? d_feat + 2 * first : nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h, st, sizeof(NearestState), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(faces, d_faces + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
-    if (w && w->faces) HIPCHK(hipMemcpyAsync(w->faces, d_faces + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
-    if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
-    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist + first, sizeof(double) * rows, hipMemcpyDeviceToHost, s));
-    if (w && w->points) HIPCHK(hipMemcpyAsync(w->points, d_points + 6 * first, sizeof(double) * 6 * rows, hipMemcpyDeviceToHost, s));
-    if (w && w->bary) HIPCHK(hipMemcpyAsync(w->bary, d_bary + 4 * first, sizeof(double) * 4 * rows, hipMemcpyDeviceToHost, s));
-    if (w && w->feature) HIPCHK(hipMemcpyAsync(w->feature, d_feat + 2 * first, sizeof(uint8_t) * 2 * rows, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (info) { info->n_found = h->n_found; info->node_visits = h->node_visits; info->tri_tests = h->tri_tests; }
-    return CD_OK;
+    return nearest_rows(a, b, a->nearest, rmax, mn, faces, ids, dist, w, info);
 }
-// ---- nearest non-neighbouring triangle of the same mesh, and the mesh's clearance (cd_nearest.h) ----------------------------------------
-// cd_nearest_between's host side with one context: buffers of its own, the context's stream, ONE synchronisation.  w->faces are the faces
-// that PLAYED A and B (not own, partner): k_pair_witness writes them from the leaf pairs, so it runs whenever w asks for anything -- for
-// faces alone it evaluates nothing.
-constexpr uint64_t NEAREST_SELF_BYTES = NEAREST_BYTES + 8;                  // ... and the played faces
-#ifndef CD_NEAREST_SELF_SHARED_BOUND
-#define CD_NEAREST_SELF_SHARED_BOUND 1                                      // (0: CD_NEAREST_MIN from the plain kernel's rows -- the build the shared bound was measured against)
-#endif
 int cd_nearest_self(cd_ctx *c, double rmax, int flags, uint32_t *faces, uint32_t *ids, double *dist, const cd_witness_out *w, cd_nearest_info *info)
 {
     const bool mn = flags == CD_NEAREST_MIN;
     if (!c || !faces || !(rmax >= 0.0) || (flags != 0 && !mn)) return CD_ERR_ARG;   // (a NaN rmax fails the comparison)
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
-    const uint64_t nt = c->nt;
-    int rc = c->nearest_self.ensure(nt + 1, NEAREST_SELF_BYTES);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    const uint64_t cap = c->nearest_self.block.cap;
-    double *d_dist = reinterpret_cast<double *>(c->nearest_self.block.d), *d_points = d_dist + cap, *d_bary = d_points + 6 * cap;
-    uint2 *d_leaf = reinterpret_cast<uint2 *>(d_bary + 4 * cap);
-    uint32_t *d_faces = reinterpret_cast<uint32_t *>(d_leaf + cap), *d_ids = d_faces + 2 * cap, *d_played = d_ids + 2 * cap;
-    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_played + 2 * cap);
-    NearestState *st = c->nearest_self.state.d, *h = c->nearest_self.state.h;
-    *h = NearestState{};
-    std::memcpy(&h->min_bits, &rmax, sizeof rmax);                          // the shared bound starts at rmax
-    HIPCHK(hipMemcpyAsync(st, h, sizeof(NearestState), hipMemcpyHostToDevice, s));
-    const uint32_t grid = cdiv(nt, NEAREST_THREADS);
-    if (mn) {
-        k_nearest_self<CD_NEAREST_SELF_SHARED_BOUND != 0><<<grid, NEAREST_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)nt,
-                                                                                           rmax, st, d_faces, d_ids, d_dist, d_leaf);
-        k_nearest_min<<<1, NEAREST_MIN_THREADS, 0, s>>>(nt, nt, st, d_faces, d_ids, d_dist, d_leaf);
-    } else {
-        k_nearest_self<false><<<grid, NEAREST_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)nt, rmax, st,
-                                                               d_faces, d_ids, d_dist, d_leaf);
-    }
-    const uint64_t first = mn ? nt : 0, rows = mn ? 1 : nt;                 // the rows the caller gets
-    if (w && (w->faces || w->points || w->bary || w->feature))
-        k_pair_witness<false><<<cdiv(rows, WITNESS_THREADS), WITNESS_THREADS, 0, s>>>(d_leaf + first, rows, c->d_leaf, c->d_perm[0], c->d_verts, nullptr,
-                                                                                      c->d_leaf, c->d_perm[0], c->d_verts, nullptr, nullptr,
-                                                                                      w->faces ? d_played + 2 * first : nullptr,
-                                                                                      w->points ? d_points + 6 * first : nullptr, w->bary ? d_bary + 4 * first : nullptr,
-                                                                                      w->feature ? d_feat + 2 * first : nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h, st, sizeof(NearestState), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(faces, d_faces + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
-    if (w && w->faces) HIPCHK(hipMemcpyAsync(w->faces, d_played + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
-    if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids + 2 * first, sizeof(uint32_t) * 2 * rows, hipMemcpyDeviceToHost, s));
-    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist + first, sizeof(double) * rows, hipMemcpyDeviceToHost, s));
-    if (w && w->points) HIPCHK(hipMemcpyAsync(w->points, d_points + 6 * first, sizeof(double) * 6 * rows, hipMemcpyDeviceToHost, s));
-    if (w && w->bary) HIPCHK(hipMemcpyAsync(w->bary, d_bary + 4 * first, sizeof(double) * 4 * rows, hipMemcpyDeviceToHost, s));
-    if (w && w->feature) HIPCHK(hipMemcpyAsync(w->feature, d_feat + 2 * first, sizeof(uint8_t) * 2 * rows, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (info) { info->n_found = h->n_found; info->node_visits = h->node_visits; info->tri_tests = h->tri_tests; }
-    return CD_OK;
+    const int rc = c->nearest_self.ensure<NearestRows>(c->nt + 1ull, true);
+    return rc ? rc : nearest_rows(c, c, c->nearest_self, rmax, mn, faces, ids, dist, w, info);
 }
 // ---- inside / outside and signed distance (cd_inside.h) ---------------------------------------------------------------------------
 // Own buffers (points, results, counters): nothing any other call keeps is touched.
-constexpr uint64_t INSIDE_BYTES = 3 * 8 + 4 * 4 + 1;                        // device bytes a point: the point, the four counts, inside
-constexpr uint64_t SDIST_BYTES = 4 * 8 + 8 + 24 + 16 + 4 + 4 + 1 + 1;       // the point with its rmax, dist, closest, uv, face, ID, feature, inside
 // what both calls reject before anything else is looked at: 0 when the arguments are in order
 static int inside_args(const cd_ctx *c, const double *points, uint64_t n, int axis, int flags, const void *required)
 {
@@ -3126,28 +3063,17 @@ int cd_points_inside(cd_ctx *c, const double *points, uint64_t n, int axis, int 
     int rc = inside_args(c, points, n, axis, flags, inside);
     if (rc) return rc;
     if (n == 0) { if (info) *info = cd_inside_info{0, 0, 0}; return CD_OK; }
-    rc = c->inside.ensure(n, INSIDE_BYTES);
+    rc = c->inside.ensure<InsideCols>(n);
     if (rc) return rc;
     hipStream_t s = c->stream;
-    const uint64_t cap = c->inside.block.cap;
-    double *d_pts = reinterpret_cast<double *>(c->inside.block.d);
-    uint32_t *d_na = reinterpret_cast<uint32_t *>(d_pts + 3 * cap), *d_nb = d_na + cap;
-    int32_t *d_wa = reinterpret_cast<int32_t *>(d_nb + cap), *d_wb = d_wa + cap;
-    uint8_t *d_in = reinterpret_cast<uint8_t *>(d_wb + cap);
-    PointState *st = c->inside.state.d, *h = c->inside.state.h;
-    HIPCHK(hipMemcpyAsync(d_pts, points, sizeof(double) * 3 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(st, 0, sizeof(PointState), s));
-    launch_points_inside(c, axis, d_pts, 3, n, flags & CD_INSIDE_PARITY, st, d_in, n_above ? d_na : nullptr, n_below ? d_nb : nullptr, w_above ? d_wa : nullptr,
-                         w_below ? d_wb : nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h, st, sizeof(PointState), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(inside, d_in, n, hipMemcpyDeviceToHost, s));
-    if (n_above) HIPCHK(hipMemcpyAsync(n_above, d_na, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (n_below) HIPCHK(hipMemcpyAsync(n_below, d_nb, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (w_above) HIPCHK(hipMemcpyAsync(w_above, d_wa, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    if (w_below) HIPCHK(hipMemcpyAsync(w_below, d_wb, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    const InsideCols k = c->inside.cols<InsideCols>();
+    if ((rc = c->inside.upload(s, k.pts, points, 3, n))) return rc;
+    launch_points_inside(c, axis, k.pts, 3, n, flags & CD_INSIDE_PARITY, c->inside.state.d, k.inside, wanted(n_above, k.n_above), wanted(n_below, k.n_below),
+                         wanted(w_above, k.w_above), wanted(w_below, k.w_below));
+    if ((rc = c->inside.launched(s)) || (rc = fetch(s, inside, k.inside, 1, n)) || (rc = fetch(s, n_above, k.n_above, 1, n)) ||
+        (rc = fetch(s, n_below, k.n_below, 1, n)) || (rc = fetch(s, w_above, k.w_above, 1, n)) || (rc = fetch(s, w_below, k.w_below, 1, n))) return rc;
     HIPCHK(hipStreamSynchronize(s));
-    if (info) { info->n_inside = h->n_found; info->node_visits = h->node_visits; info->tri_tests = h->tri_tests; }
+    item_info(info, c->inside.state.h->n_found, c->inside.state.h);
     return CD_OK;
 }
 // k_closest_points<false> with rmax = +inf and k_points_inside on the same uploaded rows, one synchronisation; the sign is set on the host
@@ -3157,7 +3083,7 @@ int cd_signed_distance(cd_ctx *c, const double *points, uint64_t n, int axis, in
     int rc = inside_args(c, points, n, axis, flags, sdist);
     if (rc) return rc;
     if (n == 0) { if (info) *info = cd_point_info{0, 0, 0}; return CD_OK; }
-    rc = c->sdist.ensure(n, SDIST_BYTES);
+    rc = c->sdist.ensure<PointCols>(n);
     if (!rc) rc = c->sdist_in.ensure();
     if (rc) return rc;
     std::vector<double> rows;                                               // cd_closest_points' rows: the point and rmax = +inf
@@ -3166,28 +3092,19 @@ int cd_signed_distance(cd_ctx *c, const double *points, uint64_t n, int axis, in
     uint8_t *in = inside ? inside : in_host.data();
     for (uint64_t i = 0; i < n; ++i) { rows[4 * i] = points[3 * i]; rows[4 * i + 1] = points[3 * i + 1]; rows[4 * i + 2] = points[3 * i + 2]; rows[4 * i + 3] = HUGE_VAL; }
     hipStream_t s = c->stream;
-    const uint64_t cap = c->sdist.block.cap;
-    double *d_pts = reinterpret_cast<double *>(c->sdist.block.d), *d_dist = d_pts + 4 * cap, *d_q = d_dist + cap, *d_uv = d_q + 3 * cap;
-    uint32_t *d_face = reinterpret_cast<uint32_t *>(d_uv + 2 * cap), *d_ids = d_face + cap;
-    uint8_t *d_feat = reinterpret_cast<uint8_t *>(d_ids + cap), *d_in = d_feat + cap;
+    const PointCols k = c->sdist.cols<PointCols>();
+    uint8_t *d_in = k.side;                                                 // (this call keeps inside where the closest-point layout keeps side)
     PointState *st = c->sdist.state.d, *h = c->sdist.state.h, *st_in = c->sdist_in.d, *h_in = c->sdist_in.h;
-    HIPCHK(hipMemcpyAsync(d_pts, rows.data(), sizeof(double) * 4 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(st, 0, sizeof(PointState), s));
+    if ((rc = c->sdist.upload(s, k.pts, rows.data(), 4, n))) return rc;
     HIPCHK(hipMemsetAsync(st_in, 0, sizeof(PointState), s));
-    k_closest_points<false><<<cdiv(n, POINT_THREADS), POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, d_pts, n, st,
-                                                                            d_face, ids ? d_ids : nullptr, d_dist, closest ? d_q : nullptr, uv ? d_uv : nullptr,
-                                                                            feature ? d_feat : nullptr, nullptr);
-    launch_points_inside(c, axis, d_pts, 4, n, flags & CD_INSIDE_PARITY, st_in, d_in, nullptr, nullptr, nullptr, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h, st, sizeof(PointState), hipMemcpyDeviceToHost, s));
+    k_closest_points<false><<<cdiv(n, POINT_THREADS), POINT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, k.pts, n, st,
+                                                                            k.face, wanted(ids, k.ids), k.dist, wanted(closest, k.closest), wanted(uv, k.uv),
+                                                                            wanted(feature, k.feature), nullptr);
+    launch_points_inside(c, axis, k.pts, 4, n, flags & CD_INSIDE_PARITY, st_in, d_in, nullptr, nullptr, nullptr, nullptr);
+    if ((rc = c->sdist.launched(s))) return rc;
     HIPCHK(hipMemcpyAsync(h_in, st_in, sizeof(PointState), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(sdist, d_dist, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(in, d_in, n, hipMemcpyDeviceToHost, s));
-    if (face) HIPCHK(hipMemcpyAsync(face, d_face, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (ids) HIPCHK(hipMemcpyAsync(ids, d_ids, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (closest) HIPCHK(hipMemcpyAsync(closest, d_q, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
-    if (uv) HIPCHK(hipMemcpyAsync(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, s));
-    if (feature) HIPCHK(hipMemcpyAsync(feature, d_feat, n, hipMemcpyDeviceToHost, s));
+    if ((rc = fetch(s, sdist, k.dist, 1, n)) || (rc = fetch(s, in, d_in, 1, n)) || (rc = fetch(s, face, k.face, 1, n)) || (rc = fetch(s, ids, k.ids, 1, n)) ||
+        (rc = fetch(s, closest, k.closest, 3, n)) || (rc = fetch(s, uv, k.uv, 2, n)) || (rc = fetch(s, feature, k.feature, 1, n))) return rc;
     HIPCHK(hipStreamSynchronize(s));
     for (uint64_t i = 0; i < n; ++i) if (in[i] && sdist[i] > 0.0) sdist[i] = -sdist[i];   // (a dist of 0 stays +0)
     if (info) { info->n_found = h->n_found; info->node_visits = h->node_visits + h_in->node_visits; info->tri_tests = h->tri_tests + h_in->tri_tests; }
@@ -3217,8 +3134,6 @@ int cd_column_tri_points(const double *points, const double *tri, uint64_t n, in
 // ---- box queries (cd_boxes.h) -----------------------------------------------------------------------------------------------------
 // Own buffers (items, candidates, rows, counters): nothing any other call keeps is touched.  The rows call is the all-results item
 // queries' pass; the count call is one kernel.
-constexpr uint64_t BOXES_ROW_BYTES = 4 + 1;                                 // device bytes a row besides (item, face): ID, inside
-constexpr uint64_t BOXES_COUNT_BYTES = 6 * 8 + 4 + 4;                       // device bytes an item: the box, count, n_inside
 // every bound is finite and lo <= hi on every axis (a NaN fails)
 static bool boxes_ok(const double *boxes, uint64_t n)
 {
@@ -3236,21 +3151,18 @@ int cd_boxes_overlap_all(cd_ctx *c, const double *boxes, uint64_t n, uint32_t *r
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if (n == 0) { *n_rows = 0; if (n_tested) *n_tested = 0; return CD_OK; }
     ItemRowsBuf &b = c->boxes_all;
-    if ((rc = b.ensure(n, 6 * 8, cap_rows, BOXES_ROW_BYTES))) return rc;
+    if ((rc = b.ensure<BoxRowCols>(n, 6, cap_rows))) return rc;
     const cd_box_rows want = out ? *out : cd_box_rows{};
-    const uint64_t cap = b.vals.cap;
-    const double *d_boxes = reinterpret_cast<const double *>(b.items.d);
-    uint32_t *d_ids = reinterpret_cast<uint32_t *>(b.vals.d);
-    uint8_t *d_in = reinterpret_cast<uint8_t *>(d_ids + cap);
+    const BoxRowCols k = b.cols<BoxRowCols>();
     rc = item_rows_pass(c, b, boxes, 6, n, [&] {
-        k_boxes_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, c->stream>>>(c->d_recs32, c->d_root, (int)c->nt, c->d_os_ticket + 8, d_boxes, n, b.q.state.d,
+        k_boxes_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, c->stream>>>(c->d_recs32, c->d_root, (int)c->nt, c->d_os_ticket + 8, b.items.d, n, b.q.state.d,
                                                                                         b.q.d_cand, b.q.shard_cap);
-        k_boxes_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, c->stream>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, d_boxes, b.q.state.d,
-                                                                                                  cap_rows, b.q.d_pairs, want.ids ? d_ids : nullptr, want.inside ? d_in : nullptr);
+        k_boxes_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, c->stream>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, b.items.d, b.q.state.d,
+                                                                                                  cap_rows, b.q.d_pairs, wanted(want.ids, k.ids), wanted(want.inside, k.inside));
     });
     if (rc) return rc;
     const uint64_t take = std::min<uint64_t>(b.q.state.h->n_pairs, cap_rows);
-    if ((rc = row_values(want.ids, d_ids, 1, take)) || (rc = row_values(want.inside, d_in, 1, take))) return rc;
+    if ((rc = row_values(want.ids, k.ids, 1, take)) || (rc = row_values(want.inside, k.inside, 1, take))) return rc;
     if (n_tested) *n_tested = b.q.state.h->n_tested;
     return b.q.results(rows, nullptr, nullptr, cap_rows, n_rows);
 }
@@ -3260,27 +3172,21 @@ int cd_boxes_count(cd_ctx *c, const double *boxes, uint64_t n, int flags, uint32
     if (!boxes_ok(boxes, n)) return CD_ERR_ARG;                             // before anything is launched: nothing is written for a bad box
     if (c->stage < ST_REFIT) return CD_ERR_ORDER;
     if (n == 0) { if (info) *info = cd_box_info{0, 0, 0}; return CD_OK; }
-    int rc = c->boxes_count.ensure(n, BOXES_COUNT_BYTES);
+    int rc = c->boxes_count.ensure<BoxCountCols>(n);
     if (rc) return rc;
     hipStream_t s = c->stream;
-    const uint64_t cap = c->boxes_count.block.cap;
-    double *d_boxes = reinterpret_cast<double *>(c->boxes_count.block.d);
-    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(d_boxes + 6 * cap), *d_nin = d_cnt + cap;
-    PointState *st = c->boxes_count.state.d, *h = c->boxes_count.state.h;
-    HIPCHK(hipMemcpyAsync(d_boxes, boxes, sizeof(double) * 6 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(st, 0, sizeof(PointState), s));
+    const BoxCountCols k = c->boxes_count.cols<BoxCountCols>();
+    PointState *st = c->boxes_count.state.d;
+    if ((rc = c->boxes_count.upload(s, k.boxes, boxes, 6, n))) return rc;
     const uint32_t grid = cdiv(n, BOXES_THREADS);
     if (flags & CD_BOX_ANY)
-        k_boxes_count<true><<<grid, BOXES_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_verts, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, d_boxes, n, st, d_cnt, nullptr);
+        k_boxes_count<true><<<grid, BOXES_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_verts, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, k.boxes, n, st, k.count, nullptr);
     else
-        k_boxes_count<false><<<grid, BOXES_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_verts, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, d_boxes, n, st, d_cnt,
-                                                            n_inside ? d_nin : nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h, st, sizeof(PointState), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(count, d_cnt, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (n_inside) HIPCHK(hipMemcpyAsync(n_inside, d_nin, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+        k_boxes_count<false><<<grid, BOXES_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_verts, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, k.boxes, n, st, k.count,
+                                                            wanted(n_inside, k.n_inside));
+    if ((rc = c->boxes_count.launched(s)) || (rc = fetch(s, count, k.count, 1, n)) || (rc = fetch(s, n_inside, k.n_inside, 1, n))) return rc;
     HIPCHK(hipStreamSynchronize(s));
-    if (info) { info->n_found = h->n_found; info->node_visits = h->node_visits; info->tri_tests = h->tri_tests; }
+    item_info(info, c->boxes_count.state.h->n_found, c->boxes_count.state.h);
     return CD_OK;
 }
 int cd_box_tri_points(const double *boxes, const double *tri, uint64_t n, uint8_t *hit, uint8_t *inside, uint8_t *code)
