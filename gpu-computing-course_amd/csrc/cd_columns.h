@@ -62,6 +62,9 @@ struct InsideCols : Columns {                   // cd_points_inside: the point, 
 struct BoxCountCols : Columns {                 // cd_boxes_count: the box, count, n_inside
     double *boxes = col<double>(6); uint32_t *count = col<uint32_t>(1), *n_inside = col<uint32_t>(1);
 };
+struct PlaneCountCols : Columns {               // cd_planes_count: the plane, n_cut, n_below, n_above
+    double *planes = col<double>(4); uint32_t *n_cut = col<uint32_t>(1), *n_below = col<uint32_t>(1), *n_above = col<uint32_t>(1);
+};
 
 // ---- blocks of cap_rows rows (ItemRowsBuf::vals): what a row has besides (item, face) and its dist / t, which are the pair record's ----
 struct WithinRowCols : Columns {                // cd_points_within: closest, uv, ID, feature, side
@@ -76,10 +79,13 @@ struct SweepRowCols : Columns {                 // cd_sweep_points_all: toi, clo
 struct BoxRowCols : Columns {                   // cd_boxes_overlap_all (no dist): ID, inside
     uint32_t *ids = col<uint32_t>(1); uint8_t *inside = col<uint8_t>(1);
 };
+struct PlaneRowCols : Columns {                 // cd_planes_cut_all (no dist): the segment a b, t of each, ID, edge of each, on
+    double *seg = col<double>(6), *t = col<double>(2); uint32_t *ids = col<uint32_t>(1); uint8_t *edge = col<uint8_t>(2), *on = col<uint8_t>(1);
+};
 
 // every list is walked at compile time: one whose columns widen calls the function above, which is no constant expression
 static_assert(column_bytes<RayCols>() + column_bytes<PointCols>() + column_bytes<SweepFirstCols>() + column_bytes<NearestCols<>>(false) + column_bytes<NearestCols<>>(true) +
-              column_bytes<InsideCols>() + column_bytes<BoxCountCols>() + column_bytes<WithinRowCols>() + column_bytes<RayRowCols>() + column_bytes<SweepRowCols>() +
-              column_bytes<BoxRowCols>() > 0, "a column's elements are larger than those of the column before it");
+              column_bytes<InsideCols>() + column_bytes<BoxCountCols>() + column_bytes<PlaneCountCols>() + column_bytes<WithinRowCols>() + column_bytes<RayRowCols>() + column_bytes<SweepRowCols>() +
+              column_bytes<BoxRowCols>() + column_bytes<PlaneRowCols>() > 0, "a column's elements are larger than those of the column before it");
 
 }  // namespace cd

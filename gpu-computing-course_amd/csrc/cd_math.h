@@ -652,6 +652,64 @@ __device__ __forceinline__ BoxTri box_tri(const Box &bx, const d3 p0, const d3 p
     return t;
 }
 
+// ---------------------------------------------------------------- plane against triangle (not reference behaviour)
+// plane_tri(plane; p0, p1, p2): on which side of the plane {nx, ny, nz, d} -- the points with n . x = d; n need not be a unit vector --
+// does the triangle lie, and if the plane cuts it, along which segment?  FP64 with this operation order, no contraction; every
+// product, sum, difference and quotient is rounded on its own.
+//   vertex : s_i = ((nx p_i.x + ny p_i.y) + nz p_i.z) - d  (plane_side).  Vertex i is BELOW iff s_i < 0; everything else -- s_i > 0, +-0,
+//            a NaN -- is "not below".  The decision depends on the vertex and the plane alone.
+//   class  : BELOW: all three vertices below.  ABOVE: none below (a face lying in the plane, or touching it from above, is ABOVE).
+//            CUT: otherwise.
+//   points : a CUT face has exactly two of its boundary edges e = 0 (p0 -> p1), 1 (p1 -> p2), 2 (p2 -> p0) whose ends differ in
+//            "below".  For such an edge L is its below vertex and U the other one, whichever way the face runs through the edge.
+//            s_U == 0: the point is U itself and t = 1.  Otherwise t = s_L / (s_L - s_U) and the point is L + t (U - L) per component
+//            (difference, product, sum).  a is the point on the edge through which the boundary LEAVES "not below" (its first end is
+//            not below, its second below), b the point on the edge through which it comes back; edge_a, edge_b, t_a, t_b go with them.
+//   on     : bit i set iff s_i == 0.
+// A face that is not CUT has a = b = (0, 0, 0), edges 0 and t = 0.
+// What follows (DESIGN.md section 24 has the proofs):
+//   - a point depends on (L, U, plane) alone, so the point of a shared edge is the same bits in both faces;
+//   - on a closed, consistently oriented mesh every edge whose ends differ in "below" is an a-edge of one face and a b-edge of the
+//     other: the multiset of a equals the multiset of b, the segments a -> b are closed loops, counter-clockwise seen from the tip of
+//     n for an outward mesh, and  sum n . (a x b) / (2 |n|)  is the enclosed area;
+//   - an edge lying in the plane is reported once, by the face below it (the face above it has no vertex below: ABOVE);
+//   - a face below that touches the plane with one vertex is a row with a == b (both edges have that vertex as U, s_U == 0);
+//   - every face has exactly one class: n_above + n_below + n_cut == n.
+// Band: scaling plane (n kept, d scaled) and triangle by 2^k changes nothing -- classes, edges, t, on; a and b scale -- while no nonzero
+// intermediate leaves the normal FP64 range.  The intermediates are products n_a p_a and their sums, so magnitudes around |n| m: as
+// ray_tri's band, for |n| of order 1 and coordinates of order 1 .. 16, |k| <= 300.  Outside it the result follows this arithmetic.
+constexpr uint32_t PLANE_ABOVE = 0u, PLANE_BELOW = 1u, PLANE_CUT = 2u;
+struct Plane { double nx, ny, nz, d; };
+struct PlaneTri { uint32_t cls, edge_a, edge_b, on; d3 a, b; double ta, tb; };
+__device__ __forceinline__ double plane_side(const Plane &pl, const double x, const double y, const double z)
+{
+    return ((pl.nx * x + pl.ny * y) + pl.nz * z) - pl.d;
+}
+// the point of an edge whose ends differ in "below": L the below end (sl < 0), U the other one
+__device__ __forceinline__ d3 plane_edge_point(const d3 L, const double sl, const d3 U, const double su, double &t)
+{
+    if (su == 0.0) { t = 1.0; return U; }
+    t = sl / (sl - su);
+    return d3{L.x + t * (U.x - L.x), L.y + t * (U.y - L.y), L.z + t * (U.z - L.z)};
+}
+__device__ __forceinline__ PlaneTri plane_tri(const Plane &pl, const d3 p0, const d3 p1, const d3 p2)
+{
+    PlaneTri r{PLANE_ABOVE, 0u, 0u, 0u, d3{0.0, 0.0, 0.0}, d3{0.0, 0.0, 0.0}, 0.0, 0.0};
+    const double s0 = plane_side(pl, p0.x, p0.y, p0.z), s1 = plane_side(pl, p1.x, p1.y, p1.z), s2 = plane_side(pl, p2.x, p2.y, p2.z);
+    const bool b0 = s0 < 0.0, b1 = s1 < 0.0, b2 = s2 < 0.0;
+    r.on = (s0 == 0.0 ? 1u : 0u) | (s1 == 0.0 ? 2u : 0u) | (s2 == 0.0 ? 4u : 0u);
+    if (b0 == b1 && b1 == b2) { r.cls = b0 ? PLANE_BELOW : PLANE_ABOVE; return r; }
+    r.cls = PLANE_CUT;
+    // the edge that leaves "not below" (first end not below, second below) and the edge that comes back
+    if (!b0 && b1) { r.edge_a = 0u; r.a = plane_edge_point(p1, s1, p0, s0, r.ta); }
+    else if (!b1 && b2) { r.edge_a = 1u; r.a = plane_edge_point(p2, s2, p1, s1, r.ta); }
+    else { r.edge_a = 2u; r.a = plane_edge_point(p0, s0, p2, s2, r.ta); }
+    if (b0 && !b1) { r.edge_b = 0u; r.b = plane_edge_point(p0, s0, p1, s1, r.tb); }
+    else if (b1 && !b2) { r.edge_b = 1u; r.b = plane_edge_point(p1, s1, p2, s2, r.tb); }
+    else { r.edge_b = 2u; r.b = plane_edge_point(p2, s2, p0, s0, r.tb); }
+    return r;
+}
+
 // morton.h:7-29
 __device__ __forceinline__ uint64_t expand64(uint64_t v)
 {

@@ -19,6 +19,7 @@
 #include "cd_sweep.h"
 #include "cd_inside.h"
 #include "cd_boxes.h"
+#include "cd_planes.h"
 #include "cd_columns.h"
 
 #include <hip/hip_runtime.h>
@@ -450,6 +451,10 @@ struct cd_ctx {
     // boxes_all.items: boxes [6 n], boxes_all.vals: BoxRowCols;   boxes_count.block: BoxCountCols
     ItemRowsBuf boxes_all;
     ItemBuf<PointState> boxes_count;
+    // plane queries (cd_planes_cut_all, cd_planes_count, cd_planes.h).
+    // planes_all.items: planes [4 n], planes_all.vals: PlaneRowCols;   planes_count.block: PlaneCountCols
+    ItemRowsBuf planes_all;
+    ItemBuf<PointState> planes_count;
 };
 
 namespace {
@@ -479,7 +484,7 @@ void free_all(cd_ctx *c)
     c->prox.release(); c->cont.release(); c->ccd.release(); c->bw.release(); c->ccd_x1.release(); c->bw_x1a.release(); c->bw_x1b.release();
     for (SweptBuf &sw : c->swept) sw.release();
     c->rays.release(); c->points.release(); c->nearest.release(); c->nearest_self.release(); c->within.release(); c->rays_all.release(); c->sweep.release();
-    c->inside.release(); c->sdist.release(); c->sdist_in.release(); c->boxes_all.release(); c->boxes_count.release();
+    c->inside.release(); c->sdist.release(); c->sdist_in.release(); c->boxes_all.release(); c->boxes_count.release(); c->planes_all.release(); c->planes_count.release();
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -3204,6 +3209,94 @@ int cd_box_tri_points(const double *boxes, const double *tri, uint64_t n, uint8_
     dev.back(hit, d_h, n);
     dev.back(inside, d_i, n);
     dev.back(code, d_c, n);
+    return dev.rc();
+}
+// ---- plane queries (cd_planes.h) ----------------------------------------------------------------------------------------------------
+// Own buffers (items, candidates, rows, counters): nothing any other call keeps is touched.  The rows call is the all-results item
+// queries' pass with the slab walk as its descent; the count call is one kernel.  Both launch one lane per (plane, slab).
+// every member is finite and the normal is not (0, 0, 0)
+static bool planes_ok(const double *planes, uint64_t n)
+{
+    for (uint64_t i = 0; i < n; ++i) {
+        const double *p = planes + 4 * i;
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]) || !std::isfinite(p[3]) || (p[0] == 0.0 && p[1] == 0.0 && p[2] == 0.0)) return false;
+    }
+    return true;
+}
+// lanes of a launch over n planes: one per (plane, slab); 0: more than a grid of one-wave workgroups holds
+static uint64_t plane_lanes(const cd_ctx *c, uint64_t n)
+{
+    const uint64_t lanes = n * ((c->nt + (uint64_t)PLANE_SLAB - 1) / PLANE_SLAB);
+    return lanes <= (1ull << 36) ? lanes : 0;
+}
+int cd_planes_cut_all(cd_ctx *c, const double *planes, uint64_t n, uint32_t *rows, uint64_t cap_rows, uint64_t *n_rows, uint64_t *n_tested, const cd_plane_rows *out)
+{
+    int rc = item_rows_args(c, planes, n, rows, cap_rows, n_rows);
+    if (rc) return rc;
+    if (!planes_ok(planes, n)) return CD_ERR_ARG;                           // before anything is launched: nothing is written for a bad plane
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { *n_rows = 0; if (n_tested) *n_tested = 0; return CD_OK; }
+    const uint64_t lanes = plane_lanes(c, n);
+    if (!lanes) return CD_ERR_ARG;
+    ItemRowsBuf &b = c->planes_all;
+    if ((rc = b.ensure<PlaneRowCols>(n, 4, cap_rows))) return rc;
+    const cd_plane_rows want = out ? *out : cd_plane_rows{};
+    const PlaneRowCols k = b.cols<PlaneRowCols>();
+    rc = item_rows_pass(c, b, planes, 4, n, [&] {
+        k_planes_descend<<<cdiv(lanes, PLANES_THREADS), PLANES_THREADS, 0, c->stream>>>(c->d_recs32, c->d_root, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, b.items.d, n,
+                                                                                       b.q.state.d, b.q.d_cand, b.q.shard_cap);
+        k_planes_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, c->stream>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, b.items.d, b.q.state.d,
+                                                                                                   cap_rows, b.q.d_pairs, wanted(want.ids, k.ids), wanted(want.seg, k.seg),
+                                                                                                   wanted(want.edge, k.edge), wanted(want.t, k.t), wanted(want.on, k.on));
+    });
+    if (rc) return rc;
+    const uint64_t take = std::min<uint64_t>(b.q.state.h->n_pairs, cap_rows);
+    if ((rc = row_values(want.ids, k.ids, 1, take)) || (rc = row_values(want.seg, k.seg, 6, take)) || (rc = row_values(want.edge, k.edge, 2, take)) ||
+        (rc = row_values(want.t, k.t, 2, take)) || (rc = row_values(want.on, k.on, 1, take))) return rc;
+    if (n_tested) *n_tested = b.q.state.h->n_tested;
+    return b.q.results(rows, nullptr, nullptr, cap_rows, n_rows);
+}
+int cd_planes_count(cd_ctx *c, const double *planes, uint64_t n, uint32_t *n_cut, uint32_t *n_below, uint32_t *n_above, cd_plane_info *info)
+{
+    if (!c || n > 0xffffffffull || (n && (!planes || !n_cut))) return CD_ERR_ARG;
+    if (!planes_ok(planes, n)) return CD_ERR_ARG;                           // before anything is launched: nothing is written for a bad plane
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { if (info) *info = cd_plane_info{0, 0, 0}; return CD_OK; }
+    const uint64_t lanes = plane_lanes(c, n);
+    if (!lanes) return CD_ERR_ARG;
+    int rc = c->planes_count.ensure<PlaneCountCols>(n);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const PlaneCountCols k = c->planes_count.cols<PlaneCountCols>();
+    if ((rc = c->planes_count.upload(s, k.planes, planes, 4, n))) return rc;
+    HIPCHK(hipMemsetAsync(k.n_cut, 0, sizeof(uint32_t) * 3 * c->planes_count.block.cap, s));   // the three count columns lie one behind the other
+    k_planes_count<<<cdiv(lanes, PLANES_THREADS), PLANES_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_verts, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, k.planes, n,
+                                                                         c->planes_count.state.d, k.n_cut, wanted(n_below, k.n_below), wanted(n_above, k.n_above));
+    if ((rc = c->planes_count.launched(s)) || (rc = fetch(s, n_cut, k.n_cut, 1, n)) || (rc = fetch(s, n_below, k.n_below, 1, n)) || (rc = fetch(s, n_above, k.n_above, 1, n))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    uint64_t found = 0;                                                     // (a plane's rows come from many lanes: the host counts the planes that have one)
+    for (uint64_t i = 0; i < n; ++i) found += n_cut[i] != 0u;
+    item_info(info, found, c->planes_count.state.h);
+    return CD_OK;
+}
+int cd_plane_tri_points(const double *planes, const double *tri, uint64_t n, uint8_t *cls, double *seg, uint8_t *edge, double *t, uint8_t *on)
+{
+    if (n == 0) return CD_OK;
+    if (!planes || !tri || !cls) return CD_ERR_ARG;
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_p = dev.in(planes, 4 * n), *d_t = dev.in(tri, 9 * n);
+    uint8_t *d_c = dev.out<uint8_t>(n), *d_e = dev.out<uint8_t>(2 * n), *d_on = dev.out<uint8_t>(n);
+    double *d_s = dev.out<double>(6 * n), *d_tt = dev.out<double>(2 * n);
+    if (dev.e == hipSuccess) {
+        k_plane_tri_points<<<strided_grid(n, 256), 256>>>(d_p, d_t, n, d_c, d_s, d_e, d_tt, d_on);
+        dev.e = hipGetLastError();
+    }
+    dev.back(cls, d_c, n);
+    dev.back(seg, d_s, 6 * n);
+    dev.back(edge, d_e, 2 * n);
+    dev.back(t, d_tt, 2 * n);
+    dev.back(on, d_on, n);
     return dev.rc();
 }
 }  // extern "C"

@@ -184,6 +184,34 @@ class _BoxRowArrays:
         return tuple(a[:got].copy() for a in (self.ids, self.inside))
 
 
+class CdPlaneInfo(C.Structure):
+    _fields_ = [("n_found", C.c_uint64), ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64)]
+
+
+class CdPlaneRows(C.Structure):
+    _fields_ = [("ids", C.c_void_p), ("seg", C.c_void_p), ("edge", C.c_void_p), ("t", C.c_void_p), ("on", C.c_void_p)]
+
+
+CD_PLANE_ABOVE, CD_PLANE_BELOW, CD_PLANE_CUT = 0, 1, 2
+CD_PLANE_SLAB = 256                 # mi355cd.h: leaves of the tree a lane of the plane queries walks (tests/test_planes_abi.py compares)
+
+
+class _PlaneRowArrays:
+    """The arrays of a planes_cut_all call with room for cap rows, and the cd_plane_rows that points at them."""
+
+    def __init__(self, cap):
+        n = max(cap, 1)
+        self.ids = np.empty(n, dtype=np.uint32)
+        self.seg = np.empty((n, 2, 3), dtype=np.float64)
+        self.edge = np.empty((n, 2), dtype=np.uint8)
+        self.t = np.empty((n, 2), dtype=np.float64)
+        self.on = np.empty(n, dtype=np.uint8)
+        self.out = CdPlaneRows(self.ids.ctypes.data, self.seg.ctypes.data, self.edge.ctypes.data, self.t.ctypes.data, self.on.ctypes.data)
+
+    def take(self, got):
+        return tuple(a[:got].copy() for a in (self.ids, self.seg, self.edge, self.t, self.on))
+
+
 class Nearest(collections.namedtuple("Nearest", "faces ids dist witness info")):
     """cd_nearest_between's rows: faces u32[n, 2] (face of self, face of other; NEAREST_NONE twice when nothing is within rmax),
     ids u32[n, 2], dist f64[n] (+inf then), witness (a Witness over the same rows, or None), info (CdNearestInfo)."""
@@ -291,6 +319,7 @@ EXPORTS = [
     "cd_sweep_points_all", "cd_sweep_points", "cd_pt_advance_points",
     "cd_points_inside", "cd_signed_distance", "cd_column_tri_points",
     "cd_boxes_overlap_all", "cd_boxes_count", "cd_box_tri_points",
+    "cd_planes_cut_all", "cd_planes_count", "cd_plane_tri_points",
 ]
 
 _lib = None
@@ -396,6 +425,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_boxes_overlap_all.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(CdBoxRows)]
     lib.cd_boxes_count.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, vp, C.POINTER(CdBoxInfo)]
     lib.cd_box_tri_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+    lib.cd_planes_cut_all.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(CdPlaneRows)]
+    lib.cd_planes_count.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.POINTER(CdPlaneInfo)]
+    lib.cd_plane_tri_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -881,6 +913,31 @@ class CollisionDetector:
         self._chk("cd_boxes_count", rc)
         return count, n_inside, info
 
+    # ---- plane queries against this mesh (cd_planes_cut_all, cd_planes_count)
+    def planes_cut_all(self, normals, d, cap: int = 1 << 20):
+        """cd_planes_cut_all on the tree that is there.  normals: [n, 3], d: [n], the planes normal . x = d.  -> (rows[m, 2] (plane
+        index, face index), ids[m], seg[m, 2, 3] (a, b), edge[m, 2], t[m, 2], on[m], m, rc): one row for EVERY (plane, triangle) that
+        plane_tri classes CUT -- some but not all of its vertices lie below the plane -- with the segment a -> b along which the plane
+        cuts it.  On a closed outward mesh the segments of a plane are closed loops, counter-clockwise seen from the normal's tip, and
+        the a are the b bit for bit.  m may exceed cap (rc = CD_OVERFLOW, cap rows are returned).  The rows come in no order.
+        self.planes_tested: plane_tri evaluations made.  One plane is walked by many lanes (CD_PLANE_SLAB leaves each)."""
+        planes = pack_planes(normals, d)
+        self.planes_tested, (rows, n, rc, vals) = self._pair_query("cd_planes_cut_all", (self._ctx, _ptr(planes), planes.shape[0]), cap, extra=_PlaneRowArrays(cap))
+        return (rows, *vals, n, rc)
+
+    def planes_count(self, normals, d):
+        """cd_planes_count on the tree that is there.  -> (n_cut[n], n_below[n], n_above[n], info): per plane the number of rows it has
+        in planes_cut_all, the faces wholly below it and the faces with no vertex below it; the three add up to the number of faces.
+        info: CdPlaneInfo (planes with n_cut > 0, boxes tested, plane_tri evaluations).  A subtree on one side of the plane is
+        counted without being walked."""
+        planes = pack_planes(normals, d)
+        n = planes.shape[0]
+        n_cut, n_below, n_above = (np.empty(n, dtype=np.uint32) for _ in range(3))
+        info = CdPlaneInfo()
+        rc = self.lib.cd_planes_count(self._ctx, _ptr(planes), n, _ptr(n_cut), _ptr(n_below), _ptr(n_above), C.byref(info))
+        self._chk("cd_planes_count", rc)
+        return n_cut, n_below, n_above, info
+
     def find_collisions(self, cap: int = 1 << 20):
         return self._pairs_call(self.lib.cd_find_collisions, "cd_find_collisions", cap)
 
@@ -1249,6 +1306,32 @@ def box_tri_points(boxes, tris):
     if rc != CD_OK:
         raise CdError("cd_box_tri_points", rc)
     return hit.astype(bool), inside.astype(bool), code
+
+
+def pack_planes(normals, d) -> np.ndarray:
+    """[n, 4] doubles {nx, ny, nz, d}, the layout cd_planes_cut_all, cd_planes_count and cd_plane_tri_points take."""
+    a = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+    b = np.asarray(d, dtype=np.float64).reshape(-1)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"{a.shape[0]} normals against {b.shape[0]} offsets")
+    return np.ascontiguousarray(np.concatenate([a, b[:, None]], axis=1))
+
+
+def plane_tri_points(planes, tris):
+    """plane_tri (the per-pair predicate of the plane queries) on explicit operands, on the device (cd_plane_tri_points): planes
+    [n, 4] {nx, ny, nz, d}, tris [n, 3, 3] -> (cls[n] (uint8: CD_PLANE_ABOVE / BELOW / CUT), seg[n, 2, 3] (a, b), edge[n, 2], t[n, 2],
+    on[n] (bit i: vertex i lies in the plane))."""
+    b = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 4))
+    p = np.ascontiguousarray(np.asarray(tris, dtype=np.float64).reshape(-1, 9))
+    if b.shape[0] != p.shape[0]:
+        raise ValueError(f"{b.shape[0]} planes against {p.shape[0]} triangles")
+    n = b.shape[0]
+    cls, on = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+    seg, edge, t = np.zeros((n, 2, 3)), np.zeros((n, 2), dtype=np.uint8), np.zeros((n, 2))
+    rc = load_library().cd_plane_tri_points(_ptr(b), _ptr(p), n, _ptr(cls), _ptr(seg), _ptr(edge), _ptr(t), _ptr(on))
+    if rc != CD_OK:
+        raise CdError("cd_plane_tri_points", rc)
+    return cls, seg, edge, t, on
 
 
 def pack_sweeps(p0, p1, dist) -> np.ndarray:

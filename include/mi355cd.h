@@ -982,6 +982,73 @@ int cd_boxes_count(cd_ctx *ctx, const double *boxes /* n x 6 */, uint64_t n, int
  * pin of the device function. */
 int cd_box_tri_points(const double *boxes, const double *tri, uint64_t n, uint8_t *hit, uint8_t *inside, uint8_t *code);
 
+/* ---- plane queries: where a plane cuts the mesh, and what lies on each side (not reference behaviour) ----
+ * A floor or a wall (is anything under it, and how much), a clip plane, the cross-section of a garment for a debug view, the layers
+ * of a slicer, splitting a mesh in two.  A plane is four doubles {nx, ny, nz, d}: the points with n . x = d.  n need not be a unit
+ * vector; "below" is the side n points away from.
+ * plane_tri(plane; triangle p0 p1 p2) -> (class, a, b, edge_a, edge_b, t_a, t_b, on), FP64 with a fixed operation order and no
+ * contraction, every product, sum, difference and quotient rounded on its own (csrc/cd_math.h):
+ *   vertex: s_i = ((nx p_i.x + ny p_i.y) + nz p_i.z) - d.  Vertex i is BELOW iff s_i < 0; s_i > 0, +-0 and a NaN are "not below".
+ *   class:  CD_PLANE_BELOW: all three vertices below.  CD_PLANE_ABOVE: none below -- a face lying in the plane, or touching it from
+ *           above, is ABOVE.  CD_PLANE_CUT: otherwise.
+ *   points: a CUT face has exactly two boundary edges, of e = 0 (p0 -> p1), 1 (p1 -> p2), 2 (p2 -> p0), whose ends differ in "below".
+ *           For such an edge L is its below vertex and U the other, whichever way the face runs through it.  s_U == 0: the point is
+ *           U itself, t = 1.  Otherwise t = s_L / (s_L - s_U) and the point is L + t (U - L) per component (difference, product, sum).
+ *           a is the point on the edge through which the boundary leaves "not below", b the point on the edge it comes back through.
+ *   on:     bit i set iff s_i == 0.
+ * A face that is not CUT has a = b = 0, edges 0, t = 0.  Consequences (proved in DESIGN.md section 24):
+ *   - the point of a shared edge is the same bits in both faces: it depends on the edge's two vertices and the plane alone;
+ *   - on a closed, consistently oriented mesh the multiset of a equals the multiset of b: the segments a -> b are closed loops with
+ *     no epsilon anywhere, counter-clockwise seen from the tip of n for an outward mesh, and sum n . (a x b) / (2 |n|) is the
+ *     enclosed area;
+ *   - an edge lying in the plane is reported once, by the face below it;
+ *   - a face below that touches the plane with one vertex is a row with a == b;
+ *   - n_above + n_below + n_cut == the number of faces, always.
+ * Scaling mesh and d by 2^k changes nothing but the scale of a and b while no nonzero intermediate (products n_a x_a and their sums)
+ * leaves the normal FP64 range: ray_tri's band, |k| <= 300 for coordinates and |n| of order 1 .. 16.
+ *
+ * cd_planes_cut_all: one row for every (plane k, face f) of this context whose class is CD_PLANE_CUT.  rows[2 r] = k,
+ * rows[2 r + 1] = f, the index in cd_create's face list; out->ids[r]: the face's ID; out->seg[6 r ..]: a then b; out->edge[2 r ..]:
+ * edge_a, edge_b; out->t[2 r ..]: t_a, t_b; out->on[r].  out and each array in it may be NULL.  Everything else is
+ * cd_boxes_overlap_all's contract: the order of the rows is free and each (k, f) appears once; *n_rows is the true number of rows,
+ * CD_OVERFLOW when it exceeds cap_rows, and nothing is written at or past cap_rows in any array; cap_rows = 0 counts only; n_tested
+ * (may be NULL): plane_tri evaluations, a number of this tree.
+ *
+ * cd_planes_count, by definition: n_cut[k] is the number of rows plane k has in cd_planes_cut_all; n_below[k] and n_above[k] (each
+ * may be NULL) the faces of class BELOW and ABOVE.  info (may be NULL): planes with n_cut > 0, boxes tested, plane_tri evaluations
+ * -- numbers of this tree.  One kernel with integer sums: no candidate buffer, nothing that can overflow.  A subtree whose stored
+ * box lies on one side of the plane is counted without being walked, the whole tree included.
+ *
+ * One plane, many lanes.  A plane's work is cut into slabs of CD_PLANE_SLAB consecutive leaves of the tree, a lane each, so ONE plane
+ * through a large mesh fills the device; no item of these calls is walked by a single lane.  The box filter of the walk is exact and
+ * needs no pad: a subtree is skipped only when the rounded vertex formula at two corners of its box proves every vertex on one side.
+ * Guarantee: the result depends on the mesh and the planes only -- not on the Morton frame, CD_OPT_TRAVERSAL, CD_OPT_CELL_TABLE, the
+ * build variant, CD_PLANE_SLAB or the order of the planes.
+ * Needs a tree built from the current vertices (CD_ERR_ORDER otherwise, including after cd_update_vertices without a rebuild).
+ * CD_ERR_ARG: a NULL context; NULL planes with n > 0; n > 2^32 - 1, or n times the slabs of this tree above 2^36; NULL n_rows, or NULL
+ * rows with cap_rows > 0 (cd_planes_cut_all); NULL n_cut with n > 0 (cd_planes_count); a plane with a member that is not finite or
+ * with n = (0, 0, 0) -- checked on the host before anything is launched, and nothing is written then.  n = 0 returns CD_OK.  The calls
+ * leave cd_stats, the last pair list, the order hint, a captured CD_OPT_GRAPH step and every other query's buffers as they were;
+ * they keep device buffers of their own (grown on demand; cd_destroy frees them) and run on the context's stream.
+ * Not built: rows for the faces wholly below (a half-space selection is a count here or a box query), oriented boxes, frustums,
+ * forms between two meshes. */
+#ifndef CD_PLANE_SLAB
+#define CD_PLANE_SLAB 256           /* leaves a lane; a power of two (tools/planes_time.py: DESIGN.md section 24) */
+#endif
+enum { CD_PLANE_ABOVE = 0, CD_PLANE_BELOW = 1, CD_PLANE_CUT = 2 };
+typedef struct cd_plane_rows { uint32_t *ids; double *seg; uint8_t *edge; double *t; uint8_t *on; } cd_plane_rows;
+typedef struct cd_plane_info { uint64_t n_found, node_visits, tri_tests; } cd_plane_info;
+int cd_planes_cut_all(cd_ctx *ctx, const double *planes /* n x 4 */, uint64_t n, uint32_t *rows, uint64_t cap_rows,
+                      uint64_t *n_rows, uint64_t *n_tested, const cd_plane_rows *out);
+int cd_planes_count(cd_ctx *ctx, const double *planes /* n x 4 */, uint64_t n, uint32_t *n_cut, uint32_t *n_below,
+                    uint32_t *n_above, cd_plane_info *info);
+/* plane_tri on explicit operands (host pointers; no context): planes is n x 4 doubles, tri n x 9 (p0, p1, p2).  cls[k]: CD_PLANE_*;
+ * seg[6 k ..]: a, b; edge[2 k ..]; t[2 k ..]; on[k].  cls is required, the others may be NULL.  CD_ERR_ARG: NULL planes, tri or cls
+ * with n > 0; n = 0 returns CD_OK and writes nothing.  No argument is checked for finiteness: the arithmetic decides.  The pin of
+ * the device function. */
+int cd_plane_tri_points(const double *planes, const double *tri, uint64_t n, uint8_t *cls, double *seg, uint8_t *edge,
+                        double *t, uint8_t *on);
+
 /* Library / build identification: "mi355cd <version> gfx950". */
 const char *cd_version(void);
 
