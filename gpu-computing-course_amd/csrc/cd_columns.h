@@ -65,6 +65,10 @@ struct BoxCountCols : Columns {                 // cd_boxes_count: the box, coun
 struct PlaneCountCols : Columns {               // cd_planes_count: the plane, n_cut, n_below, n_above
     double *planes = col<double>(4); uint32_t *n_cut = col<uint32_t>(1), *n_below = col<uint32_t>(1), *n_above = col<uint32_t>(1);
 };
+struct SegmentCols : Columns {                  // cd_segments_closest: the segment with its r, dist, s, on_seg, on_tri, uv, face, ID, feature, end, cross, side
+    double *segs = col<double>(7), *dist = col<double>(1), *s = col<double>(1), *on_seg = col<double>(3), *on_tri = col<double>(3), *uv = col<double>(2);
+    uint32_t *face = col<uint32_t>(1), *ids = col<uint32_t>(1); uint8_t *feature = col<uint8_t>(1), *end = col<uint8_t>(1), *cross = col<uint8_t>(1), *side = col<uint8_t>(1);
+};
 
 // ---- blocks of cap_rows rows (ItemRowsBuf::vals): what a row has besides (item, face) and its dist / t, which are the pair record's ----
 struct WithinRowCols : Columns {                // cd_points_within: closest, uv, ID, feature, side
@@ -82,10 +86,14 @@ struct BoxRowCols : Columns {                   // cd_boxes_overlap_all (no dist
 struct PlaneRowCols : Columns {                 // cd_planes_cut_all (no dist): the segment a b, t of each, ID, edge of each, on
     double *seg = col<double>(6), *t = col<double>(2); uint32_t *ids = col<uint32_t>(1); uint8_t *edge = col<uint8_t>(2), *on = col<uint8_t>(1);
 };
+struct SegmentRowCols : Columns {               // cd_segments_within: s, on_seg, on_tri, uv, ID, feature, end, cross, side
+    double *s = col<double>(1), *on_seg = col<double>(3), *on_tri = col<double>(3), *uv = col<double>(2); uint32_t *ids = col<uint32_t>(1);
+    uint8_t *feature = col<uint8_t>(1), *end = col<uint8_t>(1), *cross = col<uint8_t>(1), *side = col<uint8_t>(1);
+};
 
 // every list is walked at compile time: one whose columns widen calls the function above, which is no constant expression
 static_assert(column_bytes<RayCols>() + column_bytes<PointCols>() + column_bytes<SweepFirstCols>() + column_bytes<NearestCols<>>(false) + column_bytes<NearestCols<>>(true) +
               column_bytes<InsideCols>() + column_bytes<BoxCountCols>() + column_bytes<PlaneCountCols>() + column_bytes<WithinRowCols>() + column_bytes<RayRowCols>() + column_bytes<SweepRowCols>() +
-              column_bytes<BoxRowCols>() + column_bytes<PlaneRowCols>() > 0, "a column's elements are larger than those of the column before it");
+              column_bytes<BoxRowCols>() + column_bytes<PlaneRowCols>() + column_bytes<SegmentCols>() + column_bytes<SegmentRowCols>() > 0, "a column's elements are larger than those of the column before it");
 
 }  // namespace cd

@@ -531,6 +531,100 @@ __device__ __forceinline__ PtTri pt_tri(const d3 p, const d3 p0, const d3 p1, co
     return r;
 }
 
+// ---------------------------------------------------------------- segment against triangle (not reference behaviour)
+// seg_tri(a, b; p0, p1, p2): the distance from the segment a + s (b - a), s in [0, 1], to the triangle, the two closest points and where
+// on the segment and on the triangle they lie.  FP64 with this operation order, IEEE divide and sqrt, no contraction.
+//   d = b - a per coordinate (one rounding).
+//   1. Crossing: h = ray_tri(a, d, 1.0, p0, p1, p2), the call tri_isect makes for an edge.  On a hit cross = 1, dist = 0, s = h.t,
+//      (u, v) = (h.u, h.v), feature = 0, side = h.side, qs = a + s d per coordinate (the product rounded, then the sum: the P of
+//      ray_tri's gate), qt = bary_point(u, v, p0, p1, p2).  An all-zero d has det == 0 and misses by ray_tri's own arithmetic.
+//   2. Otherwise cross = 0, in tri_distance's frame translated to a:  B = b - a (= d), T_i = p_i - a;  m = the largest |component| of
+//      B, T0, T1, T2;  m == 0 (five coincident points): pt_tri's all-coincident result -- dist 0, s = u = v = 0, feature 4, end 1,
+//      side 0, qs = a, qt = p0;  else m = f 2^ex (f in [0.5, 1), |ex| clamped at TRI_DIST_EXP_MAX), B and T_i times 2^-ex (exact),
+//      A = O the origin, and the minimum of 14 squared distances taken in this order, a later term replacing the running minimum only
+//      when it is STRICTLY smaller (an earlier term keeps a tie):
+//        k = 0          pt_face2_vw(A; T)                          s = 0               the face, (u, v) = (fv, fw), feature 0
+//        k = 1, 2, 3    pt_seg2_t(A; T's edges 01, 12, 20)         s = 0               edge_bary(k - 1, t)
+//        k = 4          pt_face2_vw(B; T)                          s = 1               the face
+//        k = 5, 6, 7    pt_seg2_t(B; edges)                        s = 1               edge_bary(k - 5, t)
+//        k = 8, 9, 10   pt_seg2_t(T_(k-8); A, B)                   s = its clamped t   vertex_bary(k - 8)
+//        k = 11, 12, 13 seg_seg2_st(A, B; edge k - 11)             s = its s           edge_bary(k - 11, its t)
+//      When d is all-zero ONLY terms 0..3 are taken: they are pt_tri(a)'s four terms in pt_tri's order and frame (B = 0 adds nothing
+//      to m), so a segment with a == b is pt_tri(a) bit for bit -- dist, (u, v), feature, side, qt -- by construction.
+//      dist = sqrt(best) 2^ex;  side = (O - T0) . ((T1 - T0) x (T2 - T0)) > 0 on the scaled operands: pt_tri's side of endpoint a;
+//      qs = a for s == 0, b for s == 1, else a + s d;  qt = bary_point(u, v, p0, p1, p2) on the ORIGINAL vertices.
+//   end = 1 when s == 0, 2 when s == 1, else 0 (both branches; a clamped s may be -0.0: it compares equal to 0).
+// As in tri_witness only WHICH term won is kept; the winner is evaluated once more for its parameters (the same call on the same
+// operands: the same bits), and the term loop stays rolled (tri_distance's comment: unrolled, every term's operands are live at once).
+// The 14 terms are complete.  A closest pair (x on the segment, y on the triangle) without a crossing: if x is a segment end, terms
+// 0..7 hold it (the end against the face's interior projection and the three edges, which cover the closed triangle); if y lies on the
+// triangle's boundary and x inside the segment, y is on an edge and the pair is that edge's against the segment -- its interior
+// critical point (11..13) or an end of one of the two, which is a vertex against the segment (8..10) or a segment end again; if x is
+// inside the segment AND y inside the face, x - y is normal to the plane and to d, so the segment is parallel to the plane there and
+// the pair slides along d, at the same distance, until x reaches a segment end or y the boundary: a case above.
+// Band: ray_tri's (about 2^-300 .. 2^300), because the crossing term is ray_tri.  Finite input gives no NaN: a hit has passed ray_tri's
+// comparisons, every division of the distance terms has a denominator > 0 and the scaled operands lie in [-1, 1].  A triangle of no
+// area (ray_tri: det == 0, a miss; pt_face2: +inf) gets the distance of the segment or point it is, from its edges' terms.  A crossing's
+// two points are ray_tri's: within rounding of the face's plane, or through a sliver, they carry its noise.
+// dist is never above the true distance by more than rounding and never below it by more than a few 2^-52 M (every term is |P - Q|^2
+// of two points on the two sets up to the rounding of forming them).  Restated in tests/segment_ref.py bit for bit.
+struct SegTri { double dist, s, u, v; d3 qs, qt; uint32_t feature, end, cross, side; };
+// term k on the scaled operands (A = O): the squared distance and the term's one or two parameters
+__device__ __forceinline__ double seg_tri_term(int k, const d3 B, const d3 t0, const d3 t1, const d3 t2, double &p, double &q)
+{
+    const d3 O = d3{0.0, 0.0, 0.0};
+    p = 0.0; q = 0.0;
+    if (k >= 11) { const int e = k - 11; return seg_seg2_st(O, B, sel3(e, t0, t1, t2), sel3(e, t1, t2, t0), p, q); }
+    const bool ends = k < 8;
+    if (ends && (k & 3) == 0) return pt_face2_vw(k == 0 ? O : B, t0, t1, t2, p, q);
+    const int e = ends ? (k & 3) - 1 : k - 8;
+    const d3 te = sel3(e, t0, t1, t2);
+    return pt_seg2_t(ends ? (k < 4 ? O : B) : te, ends ? te : O, ends ? sel3(e, t1, t2, t0) : B, p);
+}
+__device__ inline SegTri seg_tri(const d3 a, const d3 b, const d3 p0, const d3 p1, const d3 p2)
+{
+    const d3 zero = d3{0.0, 0.0, 0.0};
+    SegTri r{0.0, 0.0, 0.0, 0.0, a, p0, 4u, 1u, 0u, 0u};
+    const d3 d = sub(b, a);
+    const RayHit h = ray_tri(a, d, 1.0, p0, p1, p2);
+    if (h.hit) {
+        r.s = h.t; r.u = h.u; r.v = h.v; r.feature = 0u; r.cross = 1u; r.side = h.side;
+        r.end = h.t == 0.0 ? 1u : (h.t == 1.0 ? 2u : 0u);
+        r.qs = d3{a.x + h.t * d.x, a.y + h.t * d.y, a.z + h.t * d.z};
+        r.qt = bary_point(h.u, h.v, p0, p1, p2);
+        return r;
+    }
+    d3 B = d, t0 = sub(p0, a), t1 = sub(p1, a), t2 = sub(p2, a);
+    double m = 0.0;
+    m = dmax_abs3(m, B); m = dmax_abs3(m, t0); m = dmax_abs3(m, t1); m = dmax_abs3(m, t2);
+    if (!(m > 0.0)) return r;                                             // five coincident points
+    int ex = (int)((__double_as_longlong(m) >> 52) & 0x7ff) - 1022;     // m = f 2^ex, f in [0.5, 1) (as tri_distance)
+    ex = ex < -TRI_DIST_EXP_MAX ? -TRI_DIST_EXP_MAX : (ex > TRI_DIST_EXP_MAX ? TRI_DIST_EXP_MAX : ex);
+    const double sc = pow2(-ex);
+    B = dscale(B, sc); t0 = dscale(t0, sc); t1 = dscale(t1, sc); t2 = dscale(t2, sc);
+    const int nterms = (d.x == 0.0 && d.y == 0.0 && d.z == 0.0) ? 4 : 14;
+    double best = __builtin_inf(), p, q;
+    int win = 0;
+#pragma unroll 1
+    for (int k = 0; k < nterms; ++k) {
+        const double x = seg_tri_term(k, B, t0, t1, t2, p, q);
+        if (x < best) { best = x; win = k; }
+    }
+    seg_tri_term(win, B, t0, t1, t2, p, q);                               // the winning term once more, for its parameters
+    double s = win < 4 ? 0.0 : 1.0;
+    if (win >= 11) { s = p; edge_bary(win - 11, q, r.u, r.v, r.feature); }
+    else if (win >= 8) { s = p; vertex_bary(win - 8, r.u, r.v, r.feature); }
+    else if ((win & 3) == 0) { r.u = p; r.v = q; r.feature = 0u; }
+    else edge_bary((win & 3) - 1, p, r.u, r.v, r.feature);
+    r.s = s;
+    r.end = s == 0.0 ? 1u : (s == 1.0 ? 2u : 0u);
+    r.side = dot(sub(zero, t0), cross(sub(t1, t0), sub(t2, t0))) > 0.0 ? 1u : 0u;
+    r.dist = __builtin_sqrt(best) * pow2(ex);
+    r.qs = r.end == 1u ? a : (r.end == 2u ? b : d3{a.x + s * d.x, a.y + s * d.y, a.z + s * d.z});
+    r.qt = bary_point(r.u, r.v, p0, p1, p2);
+    return r;
+}
+
 // ---------------------------------------------------------------- column against triangle (not reference behaviour)
 // column_tri(p, c; v0, v1, v2): does the line through p parallel to axis c (the COLUMN) cross the triangle, with which orientation, and
 // above or below p?  FP64 with this operation order, no contraction; every difference, product and sum is rounded on its own.

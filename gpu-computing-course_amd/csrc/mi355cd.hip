@@ -20,6 +20,7 @@
 #include "cd_inside.h"
 #include "cd_boxes.h"
 #include "cd_planes.h"
+#include "cd_segments.h"
 #include "cd_columns.h"
 
 #include <hip/hip_runtime.h>
@@ -455,6 +456,10 @@ struct cd_ctx {
     // planes_all.items: planes [4 n], planes_all.vals: PlaneRowCols;   planes_count.block: PlaneCountCols
     ItemRowsBuf planes_all;
     ItemBuf<PointState> planes_count;
+    // segment queries (cd_segments_within, cd_segments_closest, cd_segments.h).
+    // segments_all.items: segments [7 n], segments_all.vals: SegmentRowCols;   segments.block: SegmentCols
+    ItemRowsBuf segments_all;
+    ItemBuf<PointState> segments;
 };
 
 namespace {
@@ -485,6 +490,7 @@ void free_all(cd_ctx *c)
     for (SweptBuf &sw : c->swept) sw.release();
     c->rays.release(); c->points.release(); c->nearest.release(); c->nearest_self.release(); c->within.release(); c->rays_all.release(); c->sweep.release();
     c->inside.release(); c->sdist.release(); c->sdist_in.release(); c->boxes_all.release(); c->boxes_count.release(); c->planes_all.release(); c->planes_count.release();
+    c->segments_all.release(); c->segments.release();
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -500,13 +506,13 @@ inline bool have_device() { int ndev = 0; return hipGetDeviceCount(&ndev) == hip
 // error; every operation after it does nothing and hands out nullptr, so the caller launches only while e == hipSuccess.
 struct OneShot {
     hipError_t e = hipSuccess;
-    void *owned[8] = {}; int n_owned = 0;
+    void *owned[12] = {}; int n_owned = 0;
     OneShot() = default; OneShot(const OneShot &) = delete;
     ~OneShot() { for (int i = 0; i < n_owned; ++i) hipFree(owned[i]); }
     template <typename T> T *out(uint64_t count)                             // an output of `count` elements
     {
         void *p = nullptr;
-        if (e == hipSuccess && n_owned == 8) e = hipErrorOutOfMemory;
+        if (e == hipSuccess && n_owned == 12) e = hipErrorOutOfMemory;
         if (e == hipSuccess && (e = hipMalloc(&p, sizeof(T) * count)) == hipSuccess) owned[n_owned++] = p;
         return e == hipSuccess ? static_cast<T *>(p) : nullptr;
     }
@@ -3297,6 +3303,100 @@ int cd_plane_tri_points(const double *planes, const double *tri, uint64_t n, uin
     dev.back(edge, d_e, 2 * n);
     dev.back(t, d_tt, 2 * n);
     dev.back(on, d_on, n);
+    return dev.rc();
+}
+// ---- segment queries (cd_segments.h) --------------------------------------------------------------------------------------------------
+// Own buffers (items, candidates, rows, counters): nothing any other call keeps is touched.  The rows call is the all-results item
+// queries' pass; the single-answer call is one kernel.
+// every coordinate is finite and r >= 0 (a NaN r fails the comparison)
+static bool segments_ok(const double *segs, uint64_t n)
+{
+    for (uint64_t i = 0; i < n; ++i) {
+        const double *r = segs + 7 * i;
+        for (int k = 0; k < 6; ++k) if (!std::isfinite(r[k])) return false;
+        if (!(r[6] >= 0.0)) return false;
+    }
+    return true;
+}
+int cd_segments_within(cd_ctx *c, const double *segs, uint64_t n, uint32_t *rows, uint64_t cap_rows, uint64_t *n_rows, uint64_t *n_tested, const cd_segment_rows *out)
+{
+    int rc = item_rows_args(c, segs, n, rows, cap_rows, n_rows);
+    if (rc) return rc;
+    if (!segments_ok(segs, n)) return CD_ERR_ARG;                           // before anything is launched: nothing is written for a bad segment
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { *n_rows = 0; if (n_tested) *n_tested = 0; return CD_OK; }
+    ItemRowsBuf &b = c->segments_all;
+    if ((rc = b.ensure<SegmentRowCols>(n, 7, cap_rows))) return rc;
+    const cd_segment_rows want = out ? *out : cd_segment_rows{};
+    const SegmentRowCols k = b.cols<SegmentRowCols>();
+    const SegOut o{wanted(want.ids, k.ids), wanted(want.dist, b.q.d_dists), wanted(want.s, k.s), wanted(want.on_seg, k.on_seg), wanted(want.on_tri, k.on_tri),
+                   wanted(want.uv, k.uv), wanted(want.feature, k.feature), wanted(want.end, k.end), wanted(want.cross, k.cross), wanted(want.side, k.side)};
+    rc = item_rows_pass(c, b, segs, 7, n, [&] {
+        k_segments_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, c->stream>>>(c->d_recs32, c->d_root, c->d_boxes, (int)c->nt, c->d_os_ticket + 8, b.items.d, n,
+                                                                                           b.q.state.d, b.q.d_cand, b.q.shard_cap);
+        k_segments_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, c->stream>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, b.items.d,
+                                                                                                     b.q.state.d, cap_rows, b.q.d_pairs, o);
+    });
+    if (rc) return rc;
+    const uint64_t take = std::min<uint64_t>(b.q.state.h->n_pairs, cap_rows);
+    if ((rc = row_values(want.ids, k.ids, 1, take)) || (rc = row_values(want.s, k.s, 1, take)) || (rc = row_values(want.on_seg, k.on_seg, 3, take)) ||
+        (rc = row_values(want.on_tri, k.on_tri, 3, take)) || (rc = row_values(want.uv, k.uv, 2, take)) || (rc = row_values(want.feature, k.feature, 1, take)) ||
+        (rc = row_values(want.end, k.end, 1, take)) || (rc = row_values(want.cross, k.cross, 1, take)) || (rc = row_values(want.side, k.side, 1, take))) return rc;
+    if (n_tested) *n_tested = b.q.state.h->n_tested;
+    return b.q.results(rows, nullptr, want.dist, cap_rows, n_rows);
+}
+int cd_segments_closest(cd_ctx *c, const double *segs, uint64_t n, int flags, uint32_t *face, const cd_segment_rows *out, cd_segment_info *info)
+{
+    const bool any = flags == CD_SEGMENT_ANY;
+    if (!c || (flags != 0 && !any) || (n && (!segs || !face)) || (any && out) || n > 0xffffffffull) return CD_ERR_ARG;
+    if (!segments_ok(segs, n)) return CD_ERR_ARG;                           // before anything is launched: nothing is written for a bad segment
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { if (info) *info = cd_segment_info{0, 0, 0}; return CD_OK; }
+    int rc = c->segments.ensure<SegmentCols>(n);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const SegmentCols k = c->segments.cols<SegmentCols>();
+    const cd_segment_rows want = out ? *out : cd_segment_rows{};
+    if ((rc = c->segments.upload(s, k.segs, segs, 7, n))) return rc;
+    const uint32_t grid = cdiv(n, SEGMENT_THREADS);
+    if (any) k_segments_closest<true><<<grid, SEGMENT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, k.segs, n,
+                                                                      c->segments.state.d, k.face, SegOut{});
+    else k_segments_closest<false><<<grid, SEGMENT_THREADS, 0, s>>>(c->d_recs32, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, c->d_boxes, (int)c->nt, k.segs, n,
+                                                                   c->segments.state.d, k.face,
+                                                                   SegOut{wanted(want.ids, k.ids), wanted(want.dist, k.dist), wanted(want.s, k.s), wanted(want.on_seg, k.on_seg),
+                                                                          wanted(want.on_tri, k.on_tri), wanted(want.uv, k.uv), wanted(want.feature, k.feature),
+                                                                          wanted(want.end, k.end), wanted(want.cross, k.cross), wanted(want.side, k.side)});
+    if ((rc = c->segments.launched(s)) || (rc = fetch(s, face, k.face, 1, n)) || (rc = fetch(s, want.ids, k.ids, 1, n)) || (rc = fetch(s, want.dist, k.dist, 1, n)) ||
+        (rc = fetch(s, want.s, k.s, 1, n)) || (rc = fetch(s, want.on_seg, k.on_seg, 3, n)) || (rc = fetch(s, want.on_tri, k.on_tri, 3, n)) ||
+        (rc = fetch(s, want.uv, k.uv, 2, n)) || (rc = fetch(s, want.feature, k.feature, 1, n)) || (rc = fetch(s, want.end, k.end, 1, n)) ||
+        (rc = fetch(s, want.cross, k.cross, 1, n)) || (rc = fetch(s, want.side, k.side, 1, n))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    item_info(info, c->segments.state.h->n_found, c->segments.state.h);
+    return CD_OK;
+}
+int cd_seg_tri_points(const double *segs, const double *tri, uint64_t n, double *dist, double *s, double *on_seg, double *on_tri, double *uv, uint8_t *feature, uint8_t *end,
+                      uint8_t *cross, uint8_t *side)
+{
+    if (n == 0) return CD_OK;
+    if (!segs || !tri || !dist) return CD_ERR_ARG;
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_a = dev.in(segs, 6 * n), *d_t = dev.in(tri, 9 * n);
+    double *d_d = dev.out<double>(n), *d_s = dev.out<double>(n), *d_qs = dev.out<double>(3 * n), *d_qt = dev.out<double>(3 * n), *d_uv = dev.out<double>(2 * n);
+    uint8_t *d_f = dev.out<uint8_t>(n), *d_e = dev.out<uint8_t>(n), *d_c = dev.out<uint8_t>(n), *d_sd = dev.out<uint8_t>(n);
+    if (dev.e == hipSuccess) {
+        k_seg_tri_points<<<strided_grid(n, 256), 256>>>(d_a, d_t, n, SegOut{nullptr, d_d, d_s, d_qs, d_qt, d_uv, d_f, d_e, d_c, d_sd});
+        dev.e = hipGetLastError();
+    }
+    dev.back(dist, d_d, n);
+    dev.back(s, d_s, n);
+    dev.back(on_seg, d_qs, 3 * n);
+    dev.back(on_tri, d_qt, 3 * n);
+    dev.back(uv, d_uv, 2 * n);
+    dev.back(feature, d_f, n);
+    dev.back(end, d_e, n);
+    dev.back(cross, d_c, n);
+    dev.back(side, d_sd, n);
     return dev.rc();
 }
 }  // extern "C"

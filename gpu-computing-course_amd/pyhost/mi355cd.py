@@ -212,6 +212,40 @@ class _PlaneRowArrays:
         return tuple(a[:got].copy() for a in (self.ids, self.seg, self.edge, self.t, self.on))
 
 
+class CdSegmentInfo(C.Structure):
+    _fields_ = [("n_found", C.c_uint64), ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64)]
+
+
+class CdSegmentRows(C.Structure):
+    _fields_ = [("ids", C.c_void_p), ("dist", C.c_void_p), ("s", C.c_void_p), ("on_seg", C.c_void_p), ("on_tri", C.c_void_p), ("uv", C.c_void_p),
+                ("feature", C.c_void_p), ("end", C.c_void_p), ("cross", C.c_void_p), ("side", C.c_void_p)]
+
+
+CD_SEGMENT_ANY = 1
+SEGMENT_NONE = 0xFFFFFFFF
+
+
+class _SegmentRowArrays:
+    """The arrays of a segments_within / segments_closest call with room for cap rows, and the cd_segment_rows that points at them."""
+
+    def __init__(self, cap):
+        n = max(cap, 1)
+        self.ids = np.empty(n, dtype=np.uint32)
+        self.dist = np.empty(n, dtype=np.float64)
+        self.s = np.empty(n, dtype=np.float64)
+        self.on_seg = np.empty((n, 3), dtype=np.float64)
+        self.on_tri = np.empty((n, 3), dtype=np.float64)
+        self.uv = np.empty((n, 2), dtype=np.float64)
+        self.feature, self.end, self.cross, self.side = (np.empty(n, dtype=np.uint8) for _ in range(4))
+        self.out = CdSegmentRows(*(a.ctypes.data for a in self._all()))
+
+    def _all(self):
+        return (self.ids, self.dist, self.s, self.on_seg, self.on_tri, self.uv, self.feature, self.end, self.cross, self.side)
+
+    def take(self, got):
+        return tuple(a[:got].copy() for a in self._all())
+
+
 class Nearest(collections.namedtuple("Nearest", "faces ids dist witness info")):
     """cd_nearest_between's rows: faces u32[n, 2] (face of self, face of other; NEAREST_NONE twice when nothing is within rmax),
     ids u32[n, 2], dist f64[n] (+inf then), witness (a Witness over the same rows, or None), info (CdNearestInfo)."""
@@ -320,6 +354,7 @@ EXPORTS = [
     "cd_points_inside", "cd_signed_distance", "cd_column_tri_points",
     "cd_boxes_overlap_all", "cd_boxes_count", "cd_box_tri_points",
     "cd_planes_cut_all", "cd_planes_count", "cd_plane_tri_points",
+    "cd_segments_within", "cd_segments_closest", "cd_seg_tri_points",
 ]
 
 _lib = None
@@ -428,6 +463,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_planes_cut_all.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(CdPlaneRows)]
     lib.cd_planes_count.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.POINTER(CdPlaneInfo)]
     lib.cd_plane_tri_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, vp]
+    lib.cd_segments_within.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(CdSegmentRows)]
+    lib.cd_segments_closest.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, C.POINTER(CdSegmentRows), C.POINTER(CdSegmentInfo)]
+    lib.cd_seg_tri_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -938,6 +976,41 @@ class CollisionDetector:
         self._chk("cd_planes_count", rc)
         return n_cut, n_below, n_above, info
 
+    # ---- segment queries against this mesh (cd_segments_within, cd_segments_closest)
+    def segments_within(self, a, b, r, cap: int = 1 << 20):
+        """cd_segments_within on the tree that is there.  a, b: [n, 3], the segments' ends (a == b: a point); r: a scalar or [n], the
+        radius.  -> (rows[m, 2] (segment index, face index), ids[m], dist[m], s[m], on_seg[m, 3], on_tri[m, 3], uv[m, 2], feature[m],
+        end[m], cross[m], side[m], m, rc): one row for EVERY (segment, triangle) with seg_tri's dist <= r, with seg_tri's values --
+        the closest points on the segment (at parameter s; end 1 / 2: it is a / b) and on the triangle (uv, feature as pt_tri's);
+        cross = 1: the segment crosses the face (dist 0, the points are the crossing).  m may exceed cap (rc = CD_OVERFLOW, cap rows
+        are returned).  The edge-edge and edge-face pairs of a repulsion pass are  b.segments_within(a_verts[e[:, 0]], a_verts[e[:, 1]],
+        thickness).  The rows come in no order; grouped by segment, nearest first:
+            o = np.lexsort((rows[:, 1], ids, dist, rows[:, 0]))
+        whose first row a segment is segments_closest's answer.  self.segments_tested: seg_tri evaluations made.  Segments are walked
+        in the order given: keep spatially coherent ones next to each other; one with r = +inf walks the whole tree in one lane."""
+        segs = pack_segments(a, b, r)
+        self.segments_tested, (rows, n, rc, vals) = self._pair_query("cd_segments_within", (self._ctx, _ptr(segs), segs.shape[0]), cap, extra=_SegmentRowArrays(cap))
+        return (rows, *vals, n, rc)
+
+    def segments_closest(self, a, b, rmax=np.inf, any_within: bool = False):
+        """cd_segments_closest on the tree that is there.  a, b: [n, 3]; rmax: a scalar or [n], the search radius.  -> (face[n]
+        (SEGMENT_NONE = 0xFFFFFFFF when nothing is within rmax), ids[n], dist[n] (+inf then), s[n], on_seg[n, 3], on_tri[n, 3],
+        uv[n, 2], feature[n], end[n], cross[n], side[n], info): of the triangles with seg_tri's dist <= rmax the smallest (dist, ID,
+        face index) -- the smallest row of segments_within, bit for bit.  any_within: (face[n], info); face is SEGMENT_NONE or SOME
+        triangle within rmax -- which one is not defined, whether there is one is."""
+        segs = pack_segments(a, b, rmax)
+        n = segs.shape[0]
+        face = np.empty(n, dtype=np.uint32)
+        info = CdSegmentInfo()
+        if any_within:
+            rc = self.lib.cd_segments_closest(self._ctx, _ptr(segs), n, CD_SEGMENT_ANY, _ptr(face), None, C.byref(info))
+            self._chk("cd_segments_closest", rc)
+            return face, info
+        arrays = _SegmentRowArrays(n)
+        rc = self.lib.cd_segments_closest(self._ctx, _ptr(segs), n, 0, _ptr(face), C.byref(arrays.out), C.byref(info))
+        self._chk("cd_segments_closest", rc)
+        return (face, *arrays.take(n), info)
+
     def find_collisions(self, cap: int = 1 << 20):
         return self._pairs_call(self.lib.cd_find_collisions, "cd_find_collisions", cap)
 
@@ -1332,6 +1405,36 @@ def plane_tri_points(planes, tris):
     if rc != CD_OK:
         raise CdError("cd_plane_tri_points", rc)
     return cls, seg, edge, t, on
+
+
+def pack_segments(a, b, r=np.inf) -> np.ndarray:
+    """[n, 7] doubles (a, b, r), the layout cd_segments_within and cd_segments_closest take."""
+    p = np.asarray(a, dtype=np.float64).reshape(-1, 3)
+    q = np.asarray(b, dtype=np.float64).reshape(-1, 3)
+    if p.shape != q.shape:
+        raise ValueError(f"{p.shape[0]} first ends against {q.shape[0]} second ends")
+    segs = np.empty((p.shape[0], 7), dtype=np.float64)
+    segs[:, 0:3] = p
+    segs[:, 3:6] = q
+    segs[:, 6] = r
+    return segs
+
+
+def seg_tri_points(segs, tris):
+    """seg_tri (the per-pair predicate of the segment queries) on explicit operands, on the device (cd_seg_tri_points): segs [n, 6]
+    (a, b), tris [n, 3, 3] -> (dist[n], s[n], on_seg[n, 3], on_tri[n, 3], uv[n, 2], feature[n], end[n], cross[n], side[n])."""
+    q = np.ascontiguousarray(np.asarray(segs, dtype=np.float64).reshape(-1, 6))
+    p = np.ascontiguousarray(np.asarray(tris, dtype=np.float64).reshape(-1, 9))
+    if q.shape[0] != p.shape[0]:
+        raise ValueError(f"{q.shape[0]} segments against {p.shape[0]} triangles")
+    n = q.shape[0]
+    dist, s, on_seg, on_tri, uv = np.zeros(n), np.zeros(n), np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 2))
+    feature, end, cross, side = (np.zeros(n, dtype=np.uint8) for _ in range(4))
+    rc = load_library().cd_seg_tri_points(_ptr(q), _ptr(p), n, _ptr(dist), _ptr(s), _ptr(on_seg), _ptr(on_tri), _ptr(uv), _ptr(feature), _ptr(end), _ptr(cross),
+                                          _ptr(side))
+    if rc != CD_OK:
+        raise CdError("cd_seg_tri_points", rc)
+    return dist, s, on_seg, on_tri, uv, feature, end, cross, side
 
 
 def pack_sweeps(p0, p1, dist) -> np.ndarray:

@@ -656,7 +656,7 @@ int cd_tri_isect_points(const double *tri, uint64_t n, uint8_t *code, double *pa
  * CD_ERR_ARG: a NULL context; NULL rays or face with n > 0; flags other than 0 / CD_RAY_ANY; with CD_RAY_ANY an output other than
  * face; a non-finite origin or direction, an all-zero direction, a tmax that is NaN or negative -- checked on the host before
  * anything is launched, and nothing is written then.  n = 0 returns CD_OK.  The call leaves cd_stats, the last pair list, the order
- * hint, a captured CD_OPT_GRAPH step and the proximity, CCD and between-mesh buffers as they were; it keeps device buffers of its
+ * hint, a captured CD_OPT_GRAPH step and every other query's buffers as they were; it keeps device buffers of its
  * own (grown on demand; cd_destroy frees them) and runs on the context's stream with one host synchronisation. */
 typedef struct cd_ray_info { uint64_t n_hits, node_visits, tri_tests; } cd_ray_info;
 enum { CD_RAY_ANY = 1 };
@@ -708,7 +708,7 @@ int cd_ray_tri_points(const double *ray, const double *tri, uint64_t n, uint8_t 
  * CD_ERR_ARG: a NULL context; NULL points or face with n > 0; flags other than 0 / CD_POINT_ANY; with CD_POINT_ANY an output other
  * than face; a non-finite coordinate, an rmax that is NaN or negative -- checked on the host before anything is launched, and nothing
  * is written then.  n = 0 returns CD_OK.  The call leaves cd_stats, the last pair list, the order hint, a captured CD_OPT_GRAPH step and
- * the proximity, CCD, between-mesh and ray buffers as they were; it keeps device buffers of its own (grown on demand; cd_destroy frees
+ * every other query's buffers as they were; it keeps device buffers of its own (grown on demand; cd_destroy frees
  * them) and runs on the context's stream with one host synchronisation. */
 typedef struct cd_point_info { uint64_t n_found, node_visits, tri_tests; } cd_point_info;
 enum { CD_POINT_ANY = 1 };
@@ -1048,6 +1048,89 @@ int cd_planes_count(cd_ctx *ctx, const double *planes /* n x 4 */, uint64_t n, u
  * the device function. */
 int cd_plane_tri_points(const double *planes, const double *tri, uint64_t n, uint8_t *cls, double *seg, uint8_t *edge,
                         double *t, uint8_t *on);
+
+/* ---- segment queries: every triangle within a radius of a segment, and the nearest (not reference behaviour) ----
+ * The segment with a thickness -- the capsule: a strand or rod element against a body, the edges of one garment against another (the
+ * edge-edge half of a repulsion pass, beside cd_points_within's vertex-face half), a bone or tool capsule against a mesh, a thick pick
+ * ray of finite length.  segs is n x 7 doubles (ax, ay, az, bx, by, bz, r): the segment a + s (b - a), s in [0, 1], and a radius;
+ * coordinates finite, 0 <= r <= +inf; a == b is allowed (a point).
+ *
+ * The per-pair predicate seg_tri(a, b; p0, p1, p2) -> (dist, s, u, v, feature, end, cross, side, qs, qt), FP64 with a fixed operation
+ * order, no contraction, IEEE divide and sqrt:  s: the parameter of the closest point on the segment;  (u, v), feature: the closest
+ * point on the triangle in pt_tri's coding (0 face, 1 / 2 / 3 edge 01 / 12 / 20, 4 / 5 / 6 vertex 0 / 1 / 2);  end: 1 when s == 0, 2 when
+ * s == 1, else 0;  qs, qt: the two closest points.
+ *   d = b - a per coordinate (one rounding).
+ *   1. Crossing.  h = ray_tri(a, d, 1.0, p0, p1, p2), the call the contour makes for an edge.  On a hit: cross = 1, dist = 0, s = h.t,
+ *      (u, v) = (h.u, h.v), feature = 0, side = h.side, qs = a + s d per coordinate (the product rounded, then the sum: the P of ray_tri's
+ *      gate), qt = (w p0 + u p1) + v p2 with w = (1 - u) - v.  An all-zero d has det == 0 and misses by ray_tri's own arithmetic.
+ *   2. Otherwise cross = 0, in pt_tri's frame translated to a: B = b - a, T_i = p_i - a; m = the largest |component| of B, T0, T1, T2;
+ *      m == 0: pt_tri's all-coincident result (dist 0, s = u = v = 0, feature 4, end 1, side 0, qs = a, qt = p0); else m = f 2^ex with f
+ *      in [0.5, 1), |ex| clamped at 1000, B and T_i times 2^-ex (exact), A = O the origin, and the minimum of 14 squared distances taken in
+ *      this order, a later term replacing the running minimum only when STRICTLY smaller (an earlier term keeps a tie) -- the blocks are
+ *      pt_tri's face and edge terms (above) and cd_find_proximity's edge-edge term:
+ *        k = 0          face term of A against T                   s = 0               (u, v) = (fv, fw), feature 0
+ *        k = 1, 2, 3    A against T's edges 01, 12, 20             s = 0               the edge's (u, v, feature) at its t, as pt_tri's table
+ *        k = 4          face term of B against T                   s = 1
+ *        k = 5, 6, 7    B against T's edges                        s = 1
+ *        k = 8, 9, 10   T_(k-8) against the segment (A, B)         s = the clamped t   vertex k - 8: (u, v) = (0, 0), (1, 0), (0, 1)
+ *        k = 11, 12, 13 the segment (A, B) against edge k - 11 at their interior critical point (+inf unless den > 0 and both parameters
+ *                       lie in [0, 1])                             s = its s           the edge's (u, v, feature) at its t
+ *      When d is all-zero ONLY terms 0..3 are taken: pt_tri(a)'s four terms in pt_tri's order and frame, so a segment with a == b is
+ *      pt_tri(a) bit for bit -- dist, (u, v), feature, side, qt -- by construction.
+ *      dist = sqrt(best) 2^ex;  side = 1 when (O - T0) . ((T1 - T0) x (T2 - T0)) > 0 on the scaled operands: pt_tri's side of endpoint a;
+ *      qs = a for s == 0, b for s == 1, else a + s d;  qt = (w p0 + u p1) + v p2 on the ORIGINAL vertices.
+ * The 14 terms are complete: without a crossing a closest pair involves a segment end (terms 0..7) or the triangle's boundary
+ * (8..13); a pair in the interiors of both the segment and the face has the segment parallel to the plane there and slides, at the same
+ * distance, to a segment end or to the boundary.  Band: ray_tri's (largest |coordinate| about 2^-300 .. 2^300), because the crossing
+ * term is ray_tri; scaling segment and triangle by 2^k inside it scales dist, qs, qt exactly and changes nothing else.  Finite input
+ * gives no NaN.  A triangle of no area (det == 0) is never crossed and gets the distance of the segment or point it is.
+ * | |qs - qt| - dist | <= 2^-50 M on cross = 0 rows, M the pair's largest |coordinate|; on cross = 1 rows |qs - qt| <= 2^-46 M unless
+ * the segment lies within rounding of the face's plane or the face is a sliver: there ray_tri's det is rounding noise, its gate admits
+ * the hit, and the two points -- ray_tri's P and the point of its (u, v) -- can be as far apart as the triangle is large (conditions
+ * on the inputs, as the witness's and the contour's bounds; measured: DESIGN.md section 25).
+ *
+ * cd_segments_within: one row for every (segment k, face f) of this context with seg_tri(a_k, b_k; f).dist <= r_k (closed).
+ * rows[2 r] = k, rows[2 r + 1] = f, the index in cd_create's face list.  out (may be NULL, and so may each of its members), per row:
+ * ids[r] the face's ID; dist[r], s[r], on_seg[3 r ..] (qs), on_tri[3 r ..] (qt), uv[2 r], uv[2 r + 1], feature[r], end[r], cross[r],
+ * side[r]: seg_tri's values for (k, f).  Everything else is cd_points_within's contract, word for word: the order of the rows is free and
+ * each (k, f) appears exactly once; *n_rows is the size of the set; when it exceeds cap_rows the call returns CD_OVERFLOW with the true
+ * *n_rows, nothing is written at or past cap_rows in any array, and the rows that are written are distinct rows of the true set; rows
+ * may be NULL with cap_rows 0: the count-only call; n_tested (may be NULL): seg_tri evaluations made -- a number of this tree.
+ *
+ * cd_segments_closest, flags = 0: for segment k, of the triangles with seg_tri's dist <= r_k (r is a search radius), the one with the
+ * smallest (dist, triangle ID, face index).  face[k]: its index in the face list, 0xFFFFFFFF when nothing is within r; out (may be NULL,
+ * and so may each member), per item: cd_segment_rows' values for it; when nothing is within r dist[k] = +inf and the other outputs are
+ * 0.  By definition the smallest row of item k in cd_segments_within is this call's answer bit for bit, and the items with no row are
+ * its 0xFFFFFFFF items.  flags = CD_SEGMENT_ANY: face[k] = 0xFFFFFFFF when nothing is within r and SOME triangle within r otherwise;
+ * whether there is one is defined, which one is not; out must be NULL.  info (may be NULL): segments that found a triangle, boxes
+ * tested, seg_tri evaluations -- numbers of this tree.
+ *
+ * Guarantee: the rows, the answers and every value in them depend on the mesh and the items only -- not on the Morton frame,
+ * CD_OPT_TRAVERSAL, CD_OPT_CELL_TABLE, the build variant or the order of the items.  The box filter of both calls is the ray queries'
+ * slab test over s in [0, 1] against the box inflated by the bound plus the point queries' pad; it only filters (the proof: DESIGN.md
+ * section 25).  Items are walked in the order given, one lane each, neighbours in one wave: coherent items should be neighbours.  An
+ * item of cd_segments_within whose bound meets every box (r = +inf) walks the whole tree in one lane: correct, bounded, and slow.
+ * Needs a tree built from the current vertices (CD_ERR_ORDER otherwise, including after cd_update_vertices without a rebuild).
+ * CD_ERR_ARG: a NULL context; n > 0xFFFFFFFF (checked before the items are read); NULL segs with n > 0; NULL n_rows, or NULL rows with
+ * cap_rows > 0 (cd_segments_within); NULL face with n > 0, flags other than 0 / CD_SEGMENT_ANY, out given with CD_SEGMENT_ANY
+ * (cd_segments_closest); a non-finite coordinate, an r that is NaN or negative -- checked on the host before anything is launched, and
+ * nothing is written then.  n = 0 returns CD_OK.  The calls leave cd_stats, the last pair list, the order hint, a captured CD_OPT_GRAPH
+ * step and every other query's buffers as they were; they keep device buffers of their own (grown on demand, the candidate buffer by
+ * running the pass again; cd_destroy frees them) and run on the context's stream.
+ * Not built: swept segments (edge-edge CCD is cd_find_ccd's), capsules against capsules, forms between two meshes. */
+enum { CD_SEGMENT_ANY = 1 };
+typedef struct cd_segment_rows { uint32_t *ids; double *dist; double *s; double *on_seg; double *on_tri; double *uv; uint8_t *feature; uint8_t *end; uint8_t *cross; uint8_t *side; } cd_segment_rows;
+typedef struct cd_segment_info { uint64_t n_found, node_visits, tri_tests; } cd_segment_info;
+int cd_segments_within(cd_ctx *ctx, const double *segs /* n x 7 */, uint64_t n, uint32_t *rows, uint64_t cap_rows,
+                       uint64_t *n_rows, uint64_t *n_tested, const cd_segment_rows *out);
+int cd_segments_closest(cd_ctx *ctx, const double *segs /* n x 7 */, uint64_t n, int flags, uint32_t *face,
+                        const cd_segment_rows *out, cd_segment_info *info);
+/* seg_tri on explicit operands (host pointers; no context): segs is n x 6 doubles (a, b; no radius), tri n x 9 (p0, p1, p2).  dist[k],
+ * s[k], on_seg[3 k ..], on_tri[3 k ..], uv[2 k ..], feature[k], end[k], cross[k], side[k]: seg_tri's values; every output except dist
+ * may be NULL.  CD_ERR_ARG: NULL segs, tri or dist with n > 0; n = 0 returns CD_OK and writes nothing.  No argument is checked for
+ * finiteness: the arithmetic decides.  The pin of the device function. */
+int cd_seg_tri_points(const double *segs, const double *tri, uint64_t n, double *dist, double *s, double *on_seg, double *on_tri,
+                      double *uv, uint8_t *feature, uint8_t *end, uint8_t *cross, uint8_t *side);
 
 /* Library / build identification: "mi355cd <version> gfx950". */
 const char *cd_version(void);
