@@ -69,6 +69,10 @@ struct SegmentCols : Columns {                  // cd_segments_closest: the segm
     double *segs = col<double>(7), *dist = col<double>(1), *s = col<double>(1), *on_seg = col<double>(3), *on_tri = col<double>(3), *uv = col<double>(2);
     uint32_t *face = col<uint32_t>(1), *ids = col<uint32_t>(1); uint8_t *feature = col<uint8_t>(1), *end = col<uint8_t>(1), *cross = col<uint8_t>(1), *side = col<uint8_t>(1);
 };
+struct SweepSegmentCols : Columns {             // cd_sweep_segments: the item, toi, dist, s, on_seg, on_tri, uv, face, ID, feature, end, cross, side
+    double *items = col<double>(13), *toi = col<double>(1), *dist = col<double>(1), *s = col<double>(1), *on_seg = col<double>(3), *on_tri = col<double>(3), *uv = col<double>(2);
+    uint32_t *face = col<uint32_t>(1), *ids = col<uint32_t>(1); uint8_t *feature = col<uint8_t>(1), *end = col<uint8_t>(1), *cross = col<uint8_t>(1), *side = col<uint8_t>(1);
+};
 
 // ---- blocks of cap_rows rows (ItemRowsBuf::vals): what a row has besides (item, face) and its dist / t, which are the pair record's ----
 struct WithinRowCols : Columns {                // cd_points_within: closest, uv, ID, feature, side
@@ -90,10 +94,15 @@ struct SegmentRowCols : Columns {               // cd_segments_within: s, on_seg
     double *s = col<double>(1), *on_seg = col<double>(3), *on_tri = col<double>(3), *uv = col<double>(2); uint32_t *ids = col<uint32_t>(1);
     uint8_t *feature = col<uint8_t>(1), *end = col<uint8_t>(1), *cross = col<uint8_t>(1), *side = col<uint8_t>(1);
 };
+struct SweepSegmentRowCols : Columns {          // cd_sweep_segments_all: toi, s, on_seg, on_tri, uv, ID, feature, end, cross, side
+    double *toi = col<double>(1), *s = col<double>(1), *on_seg = col<double>(3), *on_tri = col<double>(3), *uv = col<double>(2); uint32_t *ids = col<uint32_t>(1);
+    uint8_t *feature = col<uint8_t>(1), *end = col<uint8_t>(1), *cross = col<uint8_t>(1), *side = col<uint8_t>(1);
+};
 
 // every list is walked at compile time: one whose columns widen calls the function above, which is no constant expression
 static_assert(column_bytes<RayCols>() + column_bytes<PointCols>() + column_bytes<SweepFirstCols>() + column_bytes<NearestCols<>>(false) + column_bytes<NearestCols<>>(true) +
               column_bytes<InsideCols>() + column_bytes<BoxCountCols>() + column_bytes<PlaneCountCols>() + column_bytes<WithinRowCols>() + column_bytes<RayRowCols>() + column_bytes<SweepRowCols>() +
-              column_bytes<BoxRowCols>() + column_bytes<PlaneRowCols>() + column_bytes<SegmentCols>() + column_bytes<SegmentRowCols>() > 0, "a column's elements are larger than those of the column before it");
+              column_bytes<BoxRowCols>() + column_bytes<PlaneRowCols>() + column_bytes<SegmentCols>() + column_bytes<SegmentRowCols>() +
+              column_bytes<SweepSegmentCols>() + column_bytes<SweepSegmentRowCols>() > 0, "a column's elements are larger than those of the column before it");
 
 }  // namespace cd

@@ -21,6 +21,7 @@
 #include "cd_boxes.h"
 #include "cd_planes.h"
 #include "cd_segments.h"
+#include "cd_sweep_segments.h"
 #include "cd_columns.h"
 
 #include <hip/hip_runtime.h>
@@ -299,6 +300,16 @@ struct SweepBuf {
     void release() { rows.release(); cst.release(); swept.release(); x1.release(); skip.release(); first.release(); }
 };
 
+// What the swept-segment queries (cd_sweep_segments_all, cd_sweep_segments, cd_sweep_segments.h) own besides what they share with the
+// swept-point queries (SweepBuf's cst, swept and x1): the rows call's record, the items' skip_vertices (2 an item) and the
+// first-contact call's counters and block
+struct SweepSegBuf {
+    ItemRowsBuf rows;
+    DevArray<uint32_t> skip;
+    ItemBuf<PointState> first;
+    void release() { rows.release(); skip.release(); first.release(); }
+};
+
 struct cd_multi;
 struct cd_ctx {
     uint32_t nv = 0, nt = 0;
@@ -460,6 +471,9 @@ struct cd_ctx {
     // segments_all.items: segments [7 n], segments_all.vals: SegmentRowCols;   segments.block: SegmentCols
     ItemRowsBuf segments_all;
     ItemBuf<PointState> segments;
+    // swept-segment queries (cd_sweep_segments_all, cd_sweep_segments, cd_sweep_segments.h); the swept records, their counters and x1 are `sweep`'s.
+    // sweep_segments.rows.items: items [13 n], sweep_segments.rows.vals: SweepSegmentRowCols;   sweep_segments.first.block: SweepSegmentCols
+    SweepSegBuf sweep_segments;
 };
 
 namespace {
@@ -490,7 +504,7 @@ void free_all(cd_ctx *c)
     for (SweptBuf &sw : c->swept) sw.release();
     c->rays.release(); c->points.release(); c->nearest.release(); c->nearest_self.release(); c->within.release(); c->rays_all.release(); c->sweep.release();
     c->inside.release(); c->sdist.release(); c->sdist_in.release(); c->boxes_all.release(); c->boxes_count.release(); c->planes_all.release(); c->planes_count.release();
-    c->segments_all.release(); c->segments.release();
+    c->segments_all.release(); c->segments.release(); c->sweep_segments.release();
     if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
     if (c->graph) hipGraphDestroy(c->graph);
     for (int i = 0; i < EV_COUNT; ++i) if (c->ev[i]) hipEventDestroy(c->ev[i]);
@@ -3397,6 +3411,137 @@ int cd_seg_tri_points(const double *segs, const double *tri, uint64_t n, double 
     dev.back(end, d_e, n);
     dev.back(cross, d_c, n);
     dev.back(side, d_sd, n);
+    return dev.rc();
+}
+// ---- swept-segment queries (cd_sweep_segments.h) ------------------------------------------------------------------------------------------
+// The swept-point queries' calls with 13 doubles an item, two skip indices an item and seg_tri's values a row.  The swept records, their
+// counters and x1 are the swept-point queries' (c->sweep: every call refits them for itself); the items, the skip indices, the
+// candidates, the rows and the first-contact block are this section's own.  swept[0] / swept[1] stay the last CCD pass's.
+// every item has twelve finite coordinates and a dist that is finite and > 0 (ccd_dist_ok: a NaN fails)
+static bool sweep_segments_ok(const double *items, uint64_t n)
+{
+    for (uint64_t i = 0; i < n; ++i) {
+        const double *r = items + 13 * i;
+        for (int k = 0; k < 12; ++k) if (!std::isfinite(r[k])) return false;
+        if (!ccd_dist_ok(r[12])) return false;
+    }
+    return true;
+}
+// sweep_inputs for x1; skip_vertices (NULL: none), 2 an item, into this section's own array
+static int sweep_segment_inputs(cd_ctx *c, const double *verts_end, const uint32_t *skip_vertices, uint64_t n, const double *&x1, const uint32_t *&skip)
+{
+    const uint32_t *none = nullptr;
+    int rc = sweep_inputs(c, verts_end, nullptr, n, x1, none);
+    if (!rc && skip_vertices) rc = c->sweep_segments.skip.ensure(n, 2);
+    if (rc) return rc;
+    skip = nullptr;
+    if (skip_vertices) {
+        HIPCHK(hipMemcpyAsync(c->sweep_segments.skip.d, skip_vertices, sizeof(uint32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
+        skip = c->sweep_segments.skip.d;
+    }
+    return CD_OK;
+}
+int cd_sweep_segments_all(cd_ctx *c, const double *verts_end, const double *items, uint64_t n, const uint32_t *skip_vertices, uint32_t *rows, uint64_t cap_rows,
+                          uint64_t *n_rows, const cd_sweep_segment_rows *out, cd_ccd_info *info)
+{
+    int rc = item_rows_args(c, items, n, rows, cap_rows, n_rows);
+    if (rc) return rc;
+    if (!sweep_segments_ok(items, n)) return CD_ERR_ARG;                    // before anything is launched: nothing is written for a bad item
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { *n_rows = 0; if (info) *info = cd_ccd_info{0, 0, 0, 0}; return CD_OK; }
+    SweepBuf &sb = c->sweep;
+    ItemRowsBuf &b = c->sweep_segments.rows;
+    if ((rc = b.ensure<SweepSegmentRowCols>(n, 13, cap_rows))) return rc;
+    const double *x1 = nullptr; const uint32_t *d_skip = nullptr;
+    if ((rc = sweep_segment_inputs(c, verts_end, skip_vertices, n, x1, d_skip))) return rc;
+    const cd_sweep_segment_rows want = out ? *out : cd_sweep_segment_rows{};
+    const SweepSegmentRowCols k = b.cols<SweepSegmentRowCols>();
+    const SweepSegOut o{SegOut{wanted(want.ids, k.ids), wanted(want.dist, b.q.d_dists), wanted(want.s, k.s), wanted(want.on_seg, k.on_seg), wanted(want.on_tri, k.on_tri),
+                               wanted(want.uv, k.uv), wanted(want.feature, k.feature), wanted(want.end, k.end), wanted(want.cross, k.cross), wanted(want.side, k.side)},
+                        wanted(want.toi, k.toi)};
+    int erc = CD_OK;                                                        // the first error of a pass's own enqueues
+    rc = item_rows_pass(c, b, items, 13, n, [&] {
+        hipStream_t s = c->stream;
+        if ((erc = sweep_refit(c, x1))) return;
+        k_sweep_segments_descend<<<cdiv(n, PROX_DESC_THREADS), PROX_DESC_THREADS, 0, s>>>(sb.swept.d_recs, c->d_root, (int)c->nt, c->d_os_ticket + 8, b.items.d, n, sb.cst.d,
+                                                                                          b.q.state.d, b.q.d_cand, b.q.shard_cap);
+        k_sweep_segments_exact<<<dim3(item_rows_blocks(c, n), NSHARD), PROX_EXACT_THREADS, 0, s>>>(b.q.d_cand, b.q.shard_cap, c->d_leaf, c->d_perm[0], c->d_verts, x1, b.items.d,
+                                                                                                   d_skip, b.q.state.d, sb.cst.d, cap_rows, b.q.d_pairs, o);
+        const hipError_t e = hipMemcpyAsync(sb.cst.h, sb.cst.d, sizeof(CcdState), hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) erc = -(int)e;
+    });
+    if (rc || (rc = erc)) return rc;
+    const uint64_t take = std::min<uint64_t>(b.q.state.h->n_pairs, cap_rows);
+    if ((rc = row_values(want.ids, k.ids, 1, take)) || (rc = row_values(want.toi, k.toi, 1, take)) || (rc = row_values(want.s, k.s, 1, take)) ||
+        (rc = row_values(want.on_seg, k.on_seg, 3, take)) || (rc = row_values(want.on_tri, k.on_tri, 3, take)) || (rc = row_values(want.uv, k.uv, 2, take)) ||
+        (rc = row_values(want.feature, k.feature, 1, take)) || (rc = row_values(want.end, k.end, 1, take)) || (rc = row_values(want.cross, k.cross, 1, take)) ||
+        (rc = row_values(want.side, k.side, 1, take))) return rc;
+    if (info) {
+        uint64_t cand = 0;
+        for (int i = 0; i < NSHARD; ++i) cand += b.q.state.h->shard[i * PROX_SHARD_STRIDE];
+        *info = cd_ccd_info{cand, b.q.state.h->n_tested, sb.cst.h->n_evals, sb.cst.h->n_unresolved};
+    }
+    return b.q.results(rows, nullptr, want.dist, cap_rows, n_rows);
+}
+int cd_sweep_segments(cd_ctx *c, const double *verts_end, const double *items, uint64_t n, const uint32_t *skip_vertices, int flags, uint32_t *face,
+                      const cd_sweep_segment_rows *out, cd_point_info *info)
+{
+    if (!c || flags != 0 || (n && (!items || !face)) || n > 0xffffffffull) return CD_ERR_ARG;
+    if (!sweep_segments_ok(items, n)) return CD_ERR_ARG;                    // before anything is launched: nothing is written for a bad item
+    if (c->stage < ST_REFIT) return CD_ERR_ORDER;
+    if (n == 0) { if (info) *info = cd_point_info{0, 0, 0}; return CD_OK; }
+    SweepBuf &sb = c->sweep;
+    ItemBuf<PointState> &fb = c->sweep_segments.first;
+    int rc = fb.ensure<SweepSegmentCols>(n);
+    if (rc) return rc;
+    const double *x1 = nullptr; const uint32_t *d_skip = nullptr;
+    if ((rc = sweep_segment_inputs(c, verts_end, skip_vertices, n, x1, d_skip))) return rc;
+    hipStream_t s = c->stream;
+    const SweepSegmentCols k = fb.cols<SweepSegmentCols>();
+    const cd_sweep_segment_rows want = out ? *out : cd_sweep_segment_rows{};
+    if ((rc = fb.upload(s, k.items, items, 13, n)) || (rc = sweep_refit(c, x1))) return rc;
+    k_sweep_segments_first<<<cdiv(n, SWEEP_SEGMENT_THREADS), SWEEP_SEGMENT_THREADS, 0, s>>>(
+        sb.swept.d_recs, c->d_root, c->d_leaf, c->d_perm[0], c->d_verts, x1, (int)c->nt, c->d_os_ticket + 8, k.items, d_skip, n, sb.cst.d, fb.state.d, k.face,
+        SweepSegOut{SegOut{wanted(want.ids, k.ids), wanted(want.dist, k.dist), wanted(want.s, k.s), wanted(want.on_seg, k.on_seg), wanted(want.on_tri, k.on_tri),
+                           wanted(want.uv, k.uv), wanted(want.feature, k.feature), wanted(want.end, k.end), wanted(want.cross, k.cross), wanted(want.side, k.side)},
+                    wanted(want.toi, k.toi)});
+    if ((rc = fb.launched(s)) || (rc = fetch(s, face, k.face, 1, n)) || (rc = fetch(s, want.ids, k.ids, 1, n)) || (rc = fetch(s, want.toi, k.toi, 1, n)) ||
+        (rc = fetch(s, want.dist, k.dist, 1, n)) || (rc = fetch(s, want.s, k.s, 1, n)) || (rc = fetch(s, want.on_seg, k.on_seg, 3, n)) ||
+        (rc = fetch(s, want.on_tri, k.on_tri, 3, n)) || (rc = fetch(s, want.uv, k.uv, 2, n)) || (rc = fetch(s, want.feature, k.feature, 1, n)) ||
+        (rc = fetch(s, want.end, k.end, 1, n)) || (rc = fetch(s, want.cross, k.cross, 1, n)) || (rc = fetch(s, want.side, k.side, 1, n))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    item_info(info, fb.state.h->n_found, fb.state.h);
+    return CD_OK;
+}
+int cd_seg_advance_points(const double *items, const double *tri, uint64_t n, double *toi, double *dist, double *s, double *on_seg, double *on_tri, double *uv,
+                          uint8_t *feature, uint8_t *end, uint8_t *cross, uint8_t *side, uint32_t *evals)
+{
+    if (!items || !tri || !toi) return CD_ERR_ARG;
+    if (!sweep_segments_ok(items, n)) return CD_ERR_ARG;
+    if (n == 0) return CD_OK;
+    if (!have_device()) return CD_ERR_NO_DEVICE;
+    OneShot dev;
+    const double *d_i = dev.in(items, 13 * n), *d_t = dev.in(tri, 18 * n);
+    double *d_toi = dev.out<double>(n), *d_d = dev.out<double>(n), *d_s = dev.out<double>(n), *d_qs = dev.out<double>(3 * n), *d_qt = dev.out<double>(3 * n);
+    double *d_uv = dev.out<double>(2 * n);
+    uint8_t *d_b = dev.out<uint8_t>(4 * n);                                 // feature, end, cross, side
+    uint32_t *d_e = dev.out<uint32_t>(n);
+    if (dev.e == hipSuccess) {
+        k_seg_advance_points<<<strided_grid(n, CCD_THREADS), CCD_THREADS>>>(d_i, d_t, n, SweepSegOut{SegOut{nullptr, d_d, d_s, d_qs, d_qt, d_uv, d_b, d_b + n, d_b + 2 * n, d_b + 3 * n}, d_toi},
+                                                                            d_e);
+        dev.e = hipGetLastError();
+    }
+    dev.back(toi, d_toi, n);
+    dev.back(dist, d_d, n);
+    dev.back(s, d_s, n);
+    dev.back(on_seg, d_qs, 3 * n);
+    dev.back(on_tri, d_qt, 3 * n);
+    dev.back(uv, d_uv, 2 * n);
+    dev.back(feature, d_b, n);
+    dev.back(end, d_b + n, n);
+    dev.back(cross, d_b + 2 * n, n);
+    dev.back(side, d_b + 3 * n, n);
+    dev.back(evals, d_e, n);
     return dev.rc();
 }
 }  // extern "C"

@@ -246,6 +246,33 @@ class _SegmentRowArrays:
         return tuple(a[:got].copy() for a in self._all())
 
 
+class CdSweepSegmentRows(C.Structure):
+    _fields_ = [("ids", C.c_void_p), ("toi", C.c_void_p), ("dist", C.c_void_p), ("s", C.c_void_p), ("on_seg", C.c_void_p), ("on_tri", C.c_void_p),
+                ("uv", C.c_void_p), ("feature", C.c_void_p), ("end", C.c_void_p), ("cross", C.c_void_p), ("side", C.c_void_p)]
+
+
+class _SweepSegmentRowArrays:
+    """The arrays of a sweep_segments_all / sweep_segments call with room for cap rows, and the cd_sweep_segment_rows that points at them."""
+
+    def __init__(self, cap):
+        n = max(cap, 1)
+        self.ids = np.empty(n, dtype=np.uint32)
+        self.toi = np.empty(n, dtype=np.float64)
+        self.dist = np.empty(n, dtype=np.float64)
+        self.s = np.empty(n, dtype=np.float64)
+        self.on_seg = np.empty((n, 3), dtype=np.float64)
+        self.on_tri = np.empty((n, 3), dtype=np.float64)
+        self.uv = np.empty((n, 2), dtype=np.float64)
+        self.feature, self.end, self.cross, self.side = (np.empty(n, dtype=np.uint8) for _ in range(4))
+        self.out = CdSweepSegmentRows(*(a.ctypes.data for a in self._all()))
+
+    def _all(self):
+        return (self.ids, self.toi, self.dist, self.s, self.on_seg, self.on_tri, self.uv, self.feature, self.end, self.cross, self.side)
+
+    def take(self, got):
+        return tuple(a[:got].copy() for a in self._all())
+
+
 class Nearest(collections.namedtuple("Nearest", "faces ids dist witness info")):
     """cd_nearest_between's rows: faces u32[n, 2] (face of self, face of other; NEAREST_NONE twice when nothing is within rmax),
     ids u32[n, 2], dist f64[n] (+inf then), witness (a Witness over the same rows, or None), info (CdNearestInfo)."""
@@ -355,6 +382,7 @@ EXPORTS = [
     "cd_boxes_overlap_all", "cd_boxes_count", "cd_box_tri_points",
     "cd_planes_cut_all", "cd_planes_count", "cd_plane_tri_points",
     "cd_segments_within", "cd_segments_closest", "cd_seg_tri_points",
+    "cd_sweep_segments_all", "cd_sweep_segments", "cd_seg_advance_points",
 ]
 
 _lib = None
@@ -466,6 +494,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.cd_segments_within.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p, C.POINTER(CdSegmentRows)]
     lib.cd_segments_closest.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, C.POINTER(CdSegmentRows), C.POINTER(CdSegmentInfo)]
     lib.cd_seg_tri_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cd_sweep_segments_all.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p, C.POINTER(CdSweepSegmentRows), C.POINTER(CdCcdInfo)]
+    lib.cd_sweep_segments.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_int, vp, C.POINTER(CdSweepSegmentRows), C.POINTER(CdPointInfo)]
+    lib.cd_seg_advance_points.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cd_multi_unique_id.argtypes = [vp]
     lib.cd_multi_create.argtypes = [C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_int]
     lib.cd_multi_create_from_comm.argtypes = [C.POINTER(vp), vp, vp, C.c_uint64, C.c_int]
@@ -1011,6 +1042,52 @@ class CollisionDetector:
         self._chk("cd_segments_closest", rc)
         return (face, *arrays.take(n), info)
 
+    # ---- swept-segment queries against this mesh as it moves (cd_sweep_segments_all, cd_sweep_segments)
+    def _sweep_segments_pre(self, a0, b0, a1, b1, dist, verts_end, skip_vertices):
+        items = pack_swept_segments(a0, b0, a1, b1, dist)
+        n = items.shape[0]
+        x1 = _verts_end(verts_end, self.nv, "verts_end", optional=True)
+        skip = None
+        if skip_vertices is not None:
+            skip = np.ascontiguousarray(skip_vertices, dtype=np.uint32)
+            if skip.shape != (n, 2):
+                raise ValueError(f"skip_vertices must be [{n}, 2], got {skip.shape}")
+        return items, n, x1, skip
+
+    def sweep_segments_all(self, a0, b0, a1, b1, dist, verts_end=None, skip_vertices=None, cap: int = 1 << 20):
+        """cd_sweep_segments_all on the tree that is there.  a0, b0, a1, b1: [n, 3], the segments' two ends at the start and at the end
+        of the step (a0 == b0 and a1 == b1: a moving point); dist: a scalar or [n], finite and > 0; verts_end: [nv, 3], the mesh at
+        the end of the step (None: it does not move); skip_vertices: [n, 2] vertex indices (SWEEP_NONE = 0xFFFFFFFF: none) whose
+        triangles are not tested for that item.  -> (rows[m, 2] (item index, face index), ids[m], toi[m], dist[m], s[m], on_seg[m, 3],
+        on_tri[m, 3], uv[m, 2], feature[m], end[m], cross[m], side[m], m, rc): one row for EVERY (item, triangle) the advancement
+        reports, with toi and seg_tri's values of the reporting evaluation; m may exceed cap (rc = CD_OVERFLOW, cap rows are
+        returned).  A row with dist > the item's dist is unresolved.  self.sweep_segments_info (CdCcdInfo): candidates, pairs through
+        the gate, seg_tri evaluations, unresolved rows.  The edge-edge half of a cloth's own CCD pass, e its [ne, 2] edges, is
+            cd.sweep_segments_all(x0[e[:, 0]], x0[e[:, 1]], x1[e[:, 0]], x1[e[:, 1]], thickness, verts_end=x1, skip_vertices=e)."""
+        items, n, x1, skip = self._sweep_segments_pre(a0, b0, a1, b1, dist, verts_end, skip_vertices)
+        rows = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        arrays = _SweepSegmentRowArrays(cap)
+        nrows, info = C.c_uint64(0), CdCcdInfo()
+        rc = self.lib.cd_sweep_segments_all(self._ctx, _ptr(x1), _ptr(items), n, _ptr(skip), _ptr(rows) if cap else None, cap, C.byref(nrows), C.byref(arrays.out),
+                                            C.byref(info))
+        self._chk("cd_sweep_segments_all", rc, allow=(CD_OK, CD_OVERFLOW))
+        self.sweep_segments_info = info
+        got = min(nrows.value, cap)
+        return (rows[:got].copy(), *arrays.take(got), nrows.value, rc)
+
+    def sweep_segments(self, a0, b0, a1, b1, dist, verts_end=None, skip_vertices=None):
+        """cd_sweep_segments on the tree that is there; arguments as sweep_segments_all takes them.  -> (face[n] (SWEEP_NONE =
+        0xFFFFFFFF: the segment comes within dist of no triangle), ids[n], toi[n] (+inf then), dist[n], s[n], on_seg[n, 3],
+        on_tri[n, 3], uv[n, 2], feature[n], end[n], cross[n], side[n], info): per item the row of sweep_segments_all with the smallest
+        (toi, ID, face index), bit for bit."""
+        items, n, x1, skip = self._sweep_segments_pre(a0, b0, a1, b1, dist, verts_end, skip_vertices)
+        face = np.empty(n, dtype=np.uint32)
+        arrays = _SweepSegmentRowArrays(n)
+        info = CdPointInfo()
+        rc = self.lib.cd_sweep_segments(self._ctx, _ptr(x1), _ptr(items), n, _ptr(skip), 0, _ptr(face), C.byref(arrays.out), C.byref(info))
+        self._chk("cd_sweep_segments", rc)
+        return (face, *arrays.take(n), info)
+
     def find_collisions(self, cap: int = 1 << 20):
         return self._pairs_call(self.lib.cd_find_collisions, "cd_find_collisions", cap)
 
@@ -1435,6 +1512,38 @@ def seg_tri_points(segs, tris):
     if rc != CD_OK:
         raise CdError("cd_seg_tri_points", rc)
     return dist, s, on_seg, on_tri, uv, feature, end, cross, side
+
+
+def pack_swept_segments(a0, b0, a1, b1, dist) -> np.ndarray:
+    """[n, 13] doubles (a0, b0, a1, b1, dist), the layout cd_sweep_segments_all, cd_sweep_segments and cd_seg_advance_points take."""
+    pts = [np.asarray(x, dtype=np.float64).reshape(-1, 3) for x in (a0, b0, a1, b1)]
+    if any(x.shape != pts[0].shape for x in pts):
+        raise ValueError(f"a0, b0, a1, b1 differ in shape: {[x.shape for x in pts]}")
+    items = np.empty((pts[0].shape[0], 13), dtype=np.float64)
+    for k, x in enumerate(pts):
+        items[:, 3 * k:3 * k + 3] = x
+    items[:, 12] = dist
+    return items
+
+
+def seg_advance_points(items, tris):
+    """seg_advance (the per-pair function of the swept-segment queries) on explicit operands, on the device (cd_seg_advance_points):
+    items [n, 13] (a0, b0, a1, b1, dist), tris [n, 6, 3] (the triangle's vertices at the start, then at the end) -> (toi[n] (+inf: not
+    reported), dist[n], s[n], on_seg[n, 3], on_tri[n, 3], uv[n, 2], feature[n], end[n], cross[n], side[n], evals[n]), the values those
+    of the last evaluation made."""
+    it = np.ascontiguousarray(np.asarray(items, dtype=np.float64).reshape(-1, 13))
+    t = np.ascontiguousarray(np.asarray(tris, dtype=np.float64).reshape(-1, 18))
+    if it.shape[0] != t.shape[0]:
+        raise ValueError(f"{it.shape[0]} items against {t.shape[0]} triangles")
+    n = it.shape[0]
+    toi, dist, s, on_seg, on_tri, uv = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 2))
+    feature, end, cross, side = (np.zeros(n, dtype=np.uint8) for _ in range(4))
+    ev = np.zeros(n, dtype=np.uint32)
+    rc = load_library().cd_seg_advance_points(_ptr(it), _ptr(t), n, _ptr(toi), _ptr(dist), _ptr(s), _ptr(on_seg), _ptr(on_tri), _ptr(uv), _ptr(feature), _ptr(end),
+                                              _ptr(cross), _ptr(side), _ptr(ev))
+    if rc != CD_OK:
+        raise CdError("cd_seg_advance_points", rc)
+    return toi, dist, s, on_seg, on_tri, uv, feature, end, cross, side, ev
 
 
 def pack_sweeps(p0, p1, dist) -> np.ndarray:

@@ -1117,7 +1117,7 @@ int cd_plane_tri_points(const double *planes, const double *tri, uint64_t n, uin
  * nothing is written then.  n = 0 returns CD_OK.  The calls leave cd_stats, the last pair list, the order hint, a captured CD_OPT_GRAPH
  * step and every other query's buffers as they were; they keep device buffers of their own (grown on demand, the candidate buffer by
  * running the pass again; cd_destroy frees them) and run on the context's stream.
- * Not built: swept segments (edge-edge CCD is cd_find_ccd's), capsules against capsules, forms between two meshes. */
+ * Not built: capsules against capsules, forms between two meshes.  The moving question is cd_sweep_segments_all's (below). */
 enum { CD_SEGMENT_ANY = 1 };
 typedef struct cd_segment_rows { uint32_t *ids; double *dist; double *s; double *on_seg; double *on_tri; double *uv; uint8_t *feature; uint8_t *end; uint8_t *cross; uint8_t *side; } cd_segment_rows;
 typedef struct cd_segment_info { uint64_t n_found, node_visits, tri_tests; } cd_segment_info;
@@ -1131,6 +1131,70 @@ int cd_segments_closest(cd_ctx *ctx, const double *segs /* n x 7 */, uint64_t n,
  * finiteness: the arithmetic decides.  The pin of the device function. */
 int cd_seg_tri_points(const double *segs, const double *tri, uint64_t n, double *dist, double *s, double *on_seg, double *on_tri,
                       double *uv, uint8_t *feature, uint8_t *end, uint8_t *cross, uint8_t *side);
+
+/* ---- swept-segment queries: moving segments against the moving mesh (not reference behaviour) ----
+ * The moving question for a segment: a strand or rod element, a bone or tool capsule, the edges of a garment against a body that
+ * deforms in the same step, the edge-edge half of a cloth's own CCD pass.  items is n x 13 doubles: a0, b0, a1, b1 (end a of the
+ * segment moves linearly from a0 to a1 during the step, end b from b0 to b1) and the item's own dist, finite and > 0; all twelve
+ * coordinates finite.  A segment of zero length at both ends of the step (a0 == b0, a1 == b1) is a moving point.  The mesh moves
+ * linearly from the context's vertices x0 (the tree's) to verts_end = x1, as for cd_sweep_points_all; NULL: the mesh does not move.
+ * skip_vertices (may be NULL): n x 2 vertex indices, 0xFFFFFFFF for none; the triangles with either index among their three are not
+ * tested for item k, before the gate -- what an edge of the mesh itself passes (its two ends).
+ *
+ * seg_advance, the per-pair function (FP64, fixed operation order, no contraction; tests/swept_segment_ref.py restates it), is
+ * pt_advance (above) with seg_tri in place of pt_tri: every coordinate of the five points moves as x + t (y - x), the difference,
+ * the product and the sum each rounded; the evaluation at t = 0 is on the start positions themselves and the one at t = 1 on the end
+ * positions themselves.  L = max over the ends j in {a, b} and the vertices i of |(x1_i - x0_i) - (j1 - j0)| (1 + 2^-20), six norms,
+ * |v| = sqrt((x x + y y) + z z); h = dist / 2.  r = seg_tri at t.  r.dist <= dist: reported at this t (a crossing, cross = 1 and
+ * dist = 0, like any other evaluation).  Else, with the evaluation on the end positions done or L == 0: not reported.  Else, after
+ * 1024 evaluations: reported UNRESOLVED at this t, with r.dist > dist.  Else t' = t + (r.dist - h) / L; t' >= 1: one evaluation on the
+ * end positions, reported at toi = 1 when within dist; otherwise t = t' and again.  A reported pair returns toi, the whole of seg_tri's
+ * result of the reporting evaluation (dist, s, qs, qt, u, v, feature, end, cross, side; qs and qt on the segment and the triangle as
+ * they stand at toi) and the evaluation count.
+ * The gate decides which pairs are evaluated at all: the box of {a0, b0, a1, b1} and the box of the triangle's six points, each widened
+ * by dist (lo - dist, hi + dist), overlap (closed).
+ * By construction an item with a0 == b0 and a1 == b1 is pt_advance of (a0, a1, dist) bit for bit and passes pt_gate's gate: its rows
+ * are cd_sweep_points_all's.  With nothing moving there is one evaluation a pair and the rows are cd_segments_within's at r = dist.
+ * Guarantee: with M the largest |coordinate| of the segment and the triangle over both ends and
+ * delta = 2^-38 M, (1) a segment that comes closer than h - delta to the exactly moving triangle at some t* is reported with
+ * toi <= t*, and stays at least h - delta away before toi; (2) a reported, resolved pair is within dist + delta at toi -- except a
+ * cross = 1 report of a segment within rounding of the face's plane or through a sliver, where ray_tri's hit is noise: such a report
+ * is early, never late.
+ *
+ * cd_sweep_segments_all: cd_sweep_points_all's contract word for word.  One row for every (item k, face f) that passes the filter and
+ * the gate and that seg_advance reports.  Row r: rows[2 r] = k, rows[2 r + 1] = f, the index in cd_create's face list; each (k, f)
+ * once, in free order.  out (may be NULL, and so may each member), per row: the face's ID, toi, and seg_tri's values of the reporting
+ * evaluation: dist[r], s[r], on_seg[3 r ..] (qs), on_tri[3 r ..] (qt), uv[2 r ..], feature[r], end[r], cross[r], side[r].
+ * CD_OVERFLOW with the true *n_rows when it exceeds cap_rows; nothing is written at or past cap_rows; cap_rows = 0 (rows may be NULL)
+ * counts only.  info (may be NULL): candidates of the walk (a number of this tree), pairs through the gate, seg_tri evaluations,
+ * unresolved rows.
+ * cd_sweep_segments: per item the row of cd_sweep_segments_all with the smallest (toi, ID, face index), bit for bit, by definition;
+ * without one face[k] = 0xFFFFFFFF, toi[k] = +inf and zeros elsewhere.  face is required; out and its members may be NULL.  flags
+ * must be 0.  info (may be NULL): items with a row, records visited, seg_tri evaluations of the walk -- numbers of this tree and this
+ * run's item order.
+ * The rows and every value in them depend on the mesh, x1 and the items only -- not on the Morton frame, CD_OPT_TRAVERSAL,
+ * CD_OPT_CELL_TABLE, the build variant or the order of the items.  Items are walked in the order given, one lane each.
+ * Needs a tree built from the current vertices (CD_ERR_ORDER otherwise, including after cd_update_vertices without a rebuild).
+ * CD_ERR_ARG: a NULL context; NULL n_rows / face; n > 0xFFFFFFFF; NULL items with n > 0; NULL rows with cap_rows > 0; a non-finite
+ * coordinate; a dist that is not finite and > 0; flags other than 0 -- checked on the host before anything is launched, and nothing
+ * is written then.  n = 0 returns CD_OK.  The calls leave cd_stats, the last pair list, the order hint, a captured CD_OPT_GRAPH step,
+ * cd_debug_swept's view of the last CCD pass and every other query's results as they were; they refit the swept-point queries' swept
+ * records for themselves (as those calls do on every call) and keep device buffers of their own (cd_destroy frees them).
+ * Not built: a slab or capsule filter tighter than the four-point box, an ANY form, a form between two meshes.
+ *
+ * cd_seg_advance_points: seg_advance on explicit operands, host pointers, no context and no gate: items n x 13, tri n x 18 (the three
+ * vertices at x0, then at x1).  toi = +inf: not reported; the other outputs (each may be NULL) are those of the last evaluation made.
+ * The pin of the device function. */
+typedef struct cd_sweep_segment_rows { uint32_t *ids; double *toi; double *dist; double *s; double *on_seg; double *on_tri; double *uv; uint8_t *feature; uint8_t *end; uint8_t *cross; uint8_t *side; } cd_sweep_segment_rows;
+int cd_sweep_segments_all(cd_ctx *ctx, const double *verts_end, const double *items /* n x 13 */, uint64_t n,
+                          const uint32_t *skip_vertices /* n x 2 */, uint32_t *rows, uint64_t cap_rows, uint64_t *n_rows,
+                          const cd_sweep_segment_rows *out, cd_ccd_info *info);
+int cd_sweep_segments(cd_ctx *ctx, const double *verts_end, const double *items /* n x 13 */, uint64_t n,
+                      const uint32_t *skip_vertices /* n x 2 */, int flags, uint32_t *face, const cd_sweep_segment_rows *out,
+                      cd_point_info *info);
+int cd_seg_advance_points(const double *items /* n x 13 */, const double *tri /* n x 18 */, uint64_t n, double *toi, double *dist,
+                          double *s, double *on_seg, double *on_tri, double *uv, uint8_t *feature, uint8_t *end, uint8_t *cross,
+                          uint8_t *side, uint32_t *evals);
 
 /* Library / build identification: "mi355cd <version> gfx950". */
 const char *cd_version(void);
