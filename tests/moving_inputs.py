@@ -14,6 +14,7 @@ import functools
 import numpy as np
 
 import between_ref as br
+import box_ref as bx
 import ccd_ref as cr
 import column_ref as cref
 import isect_ref as ir
@@ -22,11 +23,14 @@ import mi355cd
 import nearest_ref as nr
 import nearest_self_ref as ns
 import oracle
+import plane_ref as plr
 import point_ref as ptr
 import proximity_ref as pr
 import ray_ref as rr
+import segment_ref as sg
 import sweep_ref as sw
 import swept_ref as sr
+import swept_segment_ref as ssr
 import within_ref as wn
 import witness_ref as wr
 from test_between_gpu import _same_ccd as same_between_ccd, _same_contact as same_between_contact, _same_prox as same_between_prox  # noqa: F401
@@ -434,6 +438,164 @@ def want_self_sweep(name, f):
     return sw.sweep_rows_ref(s.frames[f], x1(name, f), s.vidx, None, items, skip=skip, counts=True)
 
 
+# ---------------------------------------------------------------- boxes, planes, segments and swept segments, frame by frame
+NI = 250                        # segments and swept segments a frame: three full waves and a ragged one of 58
+NBOX = 258                      # boxes of box_ref.make_boxes a frame: 32 of them are its `miss` kind (250 have 31; test_moving_inputs.py asks for 32 without a row)
+POINT_BOXES = 16                # point boxes on vertices of the frame behind the root box, which is item NBOX of the boxes
+NEAR_BOXES = 32                 # small boxes beside the surface behind those: whether they meet a face depends on the frame, not on their kind
+NPLANES = 24
+SEG_INF = (0, 128)              # the segments with r = +inf: every triangle is a row of them
+SEG_POINT_EVERY = 8             # every eighth segment has b == a
+SEG_GROWTH_AT = 256             # the growth block of the segments and swept segments: items 256 .. 319, one whole block of the descent
+SWEPT_SEGMENT_SEED = 3          # (2 gives collapse's sparse frame 0 only 31 items with several rows, 3 gives 43; test_moving_inputs.py asks for 32)
+EDGE_EVERY = 5                  # on SELF_SWEEP sequences every fifth edge of the mesh is swept against it
+
+
+def _far(name, f, n):
+    """n points a hundred edges and more beyond the mesh: the items between NI and the growth block (no rows)."""
+    s, e = seq(name), edge_at(name, f)
+    return s.frames[f].max(axis=0) + 100.0 * e * (1.0 + np.arange(n))[:, None]
+
+
+@functools.lru_cache(maxsize=None)
+def box_items(name, f):
+    """The boxes [n, 6] of cd_boxes_overlap_all / cd_boxes_count on frame f: NBOX of box_ref.make_boxes on the frame's vertices (seed by
+    frame), the frame's root box exactly (item NBOX: every triangle is a row, and inside), POINT_BOXES point boxes on vertices of
+    the frame, where the closed comparison decides, and NEAR_BOXES boxes of half-width a tenth of an edge centred 0.05 to 0.5 edge beside
+    a vertex of the frame.  Every kind of make_boxes meets the mesh or misses it by construction, in every frame alike; whether a
+    near box does is a matter of where the faces of THIS frame lie, so CD_BOX_ANY's answer changes from frame to frame and differs
+    on the previous frame's tree (tests/test_moving_inputs.py)."""
+    s, e = seq(name), edge_at(name, f)
+    v = s.frames[f]
+    used = v[s.vidx.astype(np.int64)].reshape(-1, 3)
+    at = used[np.random.default_rng(s.seed + 31 * f).integers(0, used.shape[0], POINT_BOXES)]
+    g = np.random.default_rng(s.seed + 37 * f + 5)
+    u = g.normal(size=(NEAR_BOXES, 3))
+    c = used[g.integers(0, used.shape[0], NEAR_BOXES)] + u / np.linalg.norm(u, axis=1, keepdims=True) * (e * g.uniform(0.05, 0.5, NEAR_BOXES))[:, None]
+    boxes = bx.make_boxes(v, s.vidx, e, NBOX, seed=s.seed + f)
+    return np.ascontiguousarray(np.concatenate([boxes, bx.root_box(v, s.vidx)[None], np.stack([at, at], axis=2).reshape(-1, 6),
+                                                np.stack([c - 0.1 * e, c + 0.1 * e], axis=2).reshape(-1, 6)]))
+
+
+@functools.lru_cache(maxsize=None)
+def stale_boxes(name, f) -> bx.BoxRows:
+    """What a device that kept frame f - 1's tree would answer for frame f's boxes: the restatement on the previous frame's vertices."""
+    s = seq(name)
+    return bx.boxes_overlap_all_ref(s.frames[f - 1], s.vidx, None, box_items(name, f))
+
+
+@functools.lru_cache(maxsize=None)
+def want_boxes(name, f) -> bx.BoxRows:
+    s = seq(name)
+    return bx.boxes_overlap_all_ref(s.frames[f], s.vidx, None, box_items(name, f))
+
+
+@functools.lru_cache(maxsize=None)
+def plane_items(name, f):
+    """The planes [NPLANES, 4] of cd_planes_cut_all / cd_planes_count on frame f: plane_ref.make_planes on the frame's vertices."""
+    s = seq(name)
+    return plr.make_planes(s.frames[f], s.vidx, NPLANES, seed=s.seed + f)
+
+
+@functools.lru_cache(maxsize=None)
+def want_plane_classes(name, f):
+    """plane_ref.classes_ref: the class of every (plane, face) of frame f, uint8 [NPLANES, nt]."""
+    s = seq(name)
+    return plr.classes_ref(s.frames[f], s.vidx, plane_items(name, f))
+
+
+@functools.lru_cache(maxsize=None)
+def want_planes(name, f) -> plr.PlaneRows:
+    s = seq(name)
+    return plr.rows_of(s.frames[f], s.vidx, None, plane_items(name, f), want_plane_classes(name, f))
+
+
+@functools.lru_cache(maxsize=None)
+def segment_items(name, f):
+    """The segments [n, 7] (a, b, r) of cd_segments_within / cd_segments_closest on frame f: a the frame's first NI points,
+    b = a + N(0, 1 edge) a coordinate, r a quarter edge, one edge or two by i % 3; every SEG_POINT_EVERY-th is a point (b == a) and
+    items SEG_INF have r = +inf.  On jitter's dense frame the filler and the growth block (a, b = the block's two positions, r =
+    GROWTH_EDGES edges) behind them, as items SEG_GROWTH_AT .. SEG_GROWTH_AT + 63."""
+    s, e = seq(name), edge_at(name, f)
+    a = points(name, f)[:NI]
+    b = a + np.random.default_rng(s.seed + 7 * f + 1).normal(size=a.shape) * e
+    b[::SEG_POINT_EVERY] = a[::SEG_POINT_EVERY]
+    r = np.array([e / 4, e, 2 * e])[np.arange(NI) % 3]
+    r[list(SEG_INF)] = np.inf
+    blk = _growth_block(name, f)
+    if blk is not None:
+        pad = _far(name, f, SEG_GROWTH_AT - NI)
+        a, b = np.concatenate([a, pad, blk[0]]), np.concatenate([b, pad, blk[1]])
+        r = np.concatenate([r, np.full(SEG_GROWTH_AT - NI, e), np.full(GROWTH_ITEMS, GROWTH_EDGES * e)])
+    return mi355cd.pack_segments(a, b, r)
+
+
+@functools.lru_cache(maxsize=None)
+def want_segments(name, f) -> sg.SegRows:
+    s = seq(name)
+    return sg.segments_within_ref(s.frames[f], s.vidx, None, segment_items(name, f))
+
+
+@functools.lru_cache(maxsize=None)
+def swept_segment_items(name, f):
+    """The items [n, 13] (a0, b0, a1, b1, dist) of the swept-segment queries on frame f: NI free segments at the frame's points, about
+    one edge long, both ends moving by a common N(0, 0.6 edge) and N(0, 0.2 edge) of their own, dist a quarter edge; on jitter's dense
+    frame the filler (at rest) and the growth block behind them.  The mesh moves to x1(name, f)."""
+    s, e = seq(name), edge_at(name, f)
+    g = np.random.default_rng(s.seed + 11 * f + SWEPT_SEGMENT_SEED)
+    a0 = points(name, f)[:NI]
+    b0 = a0 + g.normal(size=a0.shape) * 0.6 * e
+    common = g.normal(size=a0.shape) * 0.6 * e
+    a1, b1 = a0 + common + g.normal(size=a0.shape) * 0.2 * e, b0 + common + g.normal(size=a0.shape) * 0.2 * e
+    dist = np.full(NI, e / 4)
+    blk = _growth_block(name, f)
+    if blk is not None:
+        pad = _far(name, f, SEG_GROWTH_AT - NI)
+        off = np.random.default_rng(3).normal(size=blk[0].shape) * 0.6 * e
+        a0, b0 = np.concatenate([a0, pad, blk[0]]), np.concatenate([b0, pad, blk[0] + off])
+        a1, b1 = np.concatenate([a1, pad, blk[1]]), np.concatenate([b1, pad, blk[1] + off])
+        dist = np.concatenate([dist, np.full(SEG_GROWTH_AT - NI, e / 4), np.full(GROWTH_ITEMS, GROWTH_EDGES * e)])
+    return np.ascontiguousarray(ssr.pack(a0, b0, a1, b1, dist))
+
+
+@functools.lru_cache(maxsize=None)
+def want_swept_segments(name, f):
+    """(swept_segment_ref's SweepSegRows, (pairs through the gate, evaluations, unresolved rows)) of swept_segment_items(name, f) against
+    frame f moving to x1(name, f)."""
+    s = seq(name)
+    return ssr.sweep_segment_rows_ref(s.frames[f], x1(name, f), s.vidx, None, swept_segment_items(name, f), counts=True)
+
+
+@functools.lru_cache(maxsize=None)
+def want_swept_segments_still(name, f):
+    """The same items against frame f at rest (verts_end = None)."""
+    s = seq(name)
+    return ssr.sweep_segment_rows_ref(s.frames[f], None, s.vidx, None, swept_segment_items(name, f), counts=True)
+
+
+@functools.lru_cache(maxsize=None)
+def mesh_edges(name):
+    """Every EDGE_EVERY-th edge [ne, 2] of a SELF_SWEEP sequence's mesh (test_sweep_segments_gpu.py's on `slide`)."""
+    assert name in SELF_SWEEP
+    t = np.asarray(seq(name).vidx)
+    e = np.unique(np.sort(np.concatenate([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]]).astype(np.int64), axis=1), axis=0)
+    return np.ascontiguousarray(e[::EDGE_EVERY].astype(np.uint32))
+
+
+@functools.lru_cache(maxsize=None)
+def self_swept_segment_items(name, f):
+    """The edge-edge half of the mesh's own CCD pass: mesh_edges moving to x1, dist a quarter edge -> (items, skip_vertices)."""
+    v, w, e = seq(name).frames[f], x1(name, f), mesh_edges(name)
+    return np.ascontiguousarray(ssr.pack(v[e[:, 0]], v[e[:, 1]], w[e[:, 0]], w[e[:, 1]], edge_at(name, f) / 4)), e
+
+
+@functools.lru_cache(maxsize=None)
+def want_self_swept_segments(name, f):
+    s = seq(name)
+    items, skip = self_swept_segment_items(name, f)
+    return ssr.sweep_segment_rows_ref(s.frames[f], x1(name, f), s.vidx, None, items, skip=skip, counts=True)
+
+
 # ---------------------------------------------------------------- the mesh against itself and points inside it, frame by frame
 NEAREST_SELF_EDGES = 1.0        # cd_nearest_self's radius in edges of the frame: at least half of a frame's rows have a partner within it
 NEAREST_SELF_INF = {"scale_walk": (2, SCALE_WALK_OFFSET_FRAME), "collapse": (COLLAPSE_FRAMES[0], COLLAPSE_FRAMES[0] + 1)}
@@ -726,12 +888,17 @@ def same_contour(got, want: ir.Rows, what="", tested=None):
 
 
 def item_rows(got):
-    """The tuple of cd_points_within / cd_cast_rays_all / cd_sweep_points_all -- (rows, values ..., n, rc) -- as within_ref's PointRows /
-    RayRows or sweep_ref's SweepRows (told apart by their number of columns), sorted by (item, face); the call fitted its capacity."""
+    """The tuple of cd_points_within / cd_cast_rays_all / cd_sweep_points_all / cd_boxes_overlap_all / cd_planes_cut_all /
+    cd_segments_within / cd_sweep_segments_all -- (rows, values ..., n, rc) -- as within_ref's PointRows / RayRows, sweep_ref's SweepRows,
+    box_ref's BoxRows, plane_ref's PlaneRows, segment_ref's SegRows or swept_segment_ref's SweepSegRows (told apart by their number of
+    columns), sorted by (item, face); the call fitted its capacity."""
     *cols, n, rc = got
     assert rc == 0 and n == cols[0].shape[0], (rc, n, cols[0].shape[0])
-    kind = {len(t._fields): t for t in (wn.PointRows, wn.RayRows, sw.SweepRows)}[len(cols)]
-    return kind(*wn.sort_rows(*cols))
+    return ROW_KINDS[len(cols)](*wn.sort_rows(*cols))
+
+
+ROW_KINDS = {len(t._fields): t for t in (wn.PointRows, wn.RayRows, sw.SweepRows, bx.BoxRows, plr.PlaneRows, sg.SegRows, ssr.SweepSegRows)}
+assert len(ROW_KINDS) == 7
 
 
 def item_call(rows, rc=0):
@@ -762,6 +929,81 @@ def same_first_contact(got, rows: sw.SweepRows, n, what=""):
         _same_bytes(a, b, (what, "first contact, output", k))
     found = int(np.unique(rows.rows[:, 0]).size)
     assert got[8].n_found == found, (what, got[8].n_found, found)
+
+
+def box_count_call(rows: bx.BoxRows, n, any=False):
+    """What cd_boxes_count (with any: CD_BOX_ANY) returns on n boxes whose rows are `rows`."""
+    c, ci = bx.counts_of(rows, n)
+    info = mi355cd.CdBoxInfo(int((c > 0).sum()), 0, 0)
+    return ((c > 0).astype(np.uint32), None, info) if any else (c, ci, info)
+
+
+def same_box_counts(got, rows: bx.BoxRows, n, what="", any=False):
+    """got: cd_boxes_count's (count, n_inside, info); rows: the rows of the same n boxes.  count and n_inside are the per-item sums of
+    the rows (with any: count is "has a row" and n_inside None), n_found the boxes with a row.  node_visits and tri_tests: not compared."""
+    c, ci = bx.counts_of(rows, n)
+    if any:
+        assert got[1] is None, what
+        _same_bytes(got[0], (c > 0).astype(np.uint32), (what, "any"))
+    else:
+        _same_bytes(got[0], c, (what, "count"))
+        _same_bytes(got[1], ci, (what, "n_inside"))
+    assert got[2].n_found == int((c > 0).sum()), (what, got[2].n_found, int((c > 0).sum()))
+
+
+def plane_count_call(cls):
+    """What cd_planes_count returns on planes whose classes are `cls`."""
+    c = plr.counts_of_classes(cls)
+    return c + (mi355cd.CdPlaneInfo(int((c[0] > 0).sum()), 0, 0),)
+
+
+def same_plane_counts(got, cls, what=""):
+    """got: cd_planes_count's (n_cut, n_below, n_above, info); cls: plane_ref.classes_ref of the same planes.  The three counts are
+    counts_of_classes, they add up to the number of faces, n_found is the planes that cut a face."""
+    want = plr.counts_of_classes(cls)
+    for k, a, b in zip(("n_cut", "n_below", "n_above"), got[:3], want):
+        _same_bytes(a, b, (what, k))
+    assert (got[0].astype(np.int64) + got[1] + got[2] == cls.shape[1]).all(), what
+    assert got[3].n_found == int((want[0] > 0).sum()), (what, got[3].n_found)
+
+
+def segment_closest_call(rows: sg.SegRows, n):
+    """What cd_segments_closest returns on n segments whose rows are `rows`."""
+    first = sg.closest_of(rows, n)
+    return first + (mi355cd.CdSegmentInfo(int((first[0] != sg.NONE).sum()), 0, 0),)
+
+
+def same_segment_closest(got, rows: sg.SegRows, n, what=""):
+    """got: cd_segments_closest's (face, ids, dist, s, on_seg, on_tri, uv, feature, end, cross, side, info); rows: rows of the same n
+    segments.  All eleven outputs are segment_ref.closest_of of the rows, by their bytes; n_found is the segments with a row."""
+    for k, (a, b) in enumerate(zip(got[:11], sg.closest_of(rows, n))):
+        _same_bytes(a, b, (what, "closest, output", k))
+    found = int(np.unique(rows.rows[:, 0]).size)
+    assert got[11].n_found == found, (what, got[11].n_found, found)
+
+
+def same_segment_any(face, info, rows: sg.SegRows, n, what=""):
+    """CD_SEGMENT_ANY: WHETHER a segment has a row is defined, and the face returned is one of its rows'."""
+    has = wn.rows_per_item(rows, n) > 0
+    assert np.array_equal(face != sg.NONE, has) and info.n_found == int(has.sum()), (what, info.n_found, int(has.sum()))
+    key = lambda r: (r[:, 0].astype(np.uint64) << np.uint64(32)) | r[:, 1].astype(np.uint64)
+    k = np.flatnonzero(has)
+    assert np.isin(key(np.stack([k.astype(np.uint32), face[k]], axis=1)), key(rows.rows)).all(), what
+
+
+def sweep_segments_call(rows: ssr.SweepSegRows, n):
+    """What cd_sweep_segments returns on n items whose rows are `rows`."""
+    first = ssr.first_of(rows, n)
+    return first + (mi355cd.CdPointInfo(int((first[0] != ssr.NONE).sum()), 0, 0),)
+
+
+def same_sweep_segments(got, rows: ssr.SweepSegRows, n, what=""):
+    """got: cd_sweep_segments' (face, ids, toi, dist, s, on_seg, on_tri, uv, feature, end, cross, side, info); rows: rows of the same n
+    items.  All twelve outputs are swept_segment_ref.first_of of the rows, by their bytes; n_found is the items with a row."""
+    for k, (a, b) in enumerate(zip(got[:12], ssr.first_of(rows, n))):
+        _same_bytes(a, b, (what, "first contact, output", k))
+    found = int(np.unique(rows.rows[:, 0]).size)
+    assert got[12].n_found == found, (what, got[12].n_found, found)
 
 
 def unordered_pairs(pairs):

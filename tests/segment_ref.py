@@ -316,3 +316,38 @@ def input_conditions(name):
         assert nt > 1 or c.max() <= 1
     if nt >= 1000:
         assert all(g > 0 for g in groups), (name, groups)
+
+
+# ---------------------------------------------------------------- the case of the range tests (tests/test_segments_gpu.py section 10, tests/test_segment_ref.py)
+SCALE_MESHES = ("cloth", "centred")         # of tests/scale_inputs.py: a cloth pair away from the origin, a soup with both signs on every axis
+NSCALE = 512
+
+
+@functools.lru_cache(maxsize=None)
+def scale_case(name, off=0.0):
+    """(verts, vidx, items [NSCALE, 7], the restatement's rows) at k = 0: segments at the mesh (a as point_ref.mesh_points places
+    points, b = a + N(0, 1 edge) a coordinate), radius a quarter edge or one edge by i % 2; with `off` the mesh and both ends are
+    translated by it.  Another scale takes scale_inputs.scaled() of these, never items of its own."""
+    import scale_inputs as si
+    v, vidx, edge = si.meshes()[name]
+    vv = np.asarray(v, dtype=np.float64).reshape(-1, 3)
+    a = ptr.mesh_points(vv, vidx, NSCALE, seed=3, edge=edge)
+    b = a + np.random.default_rng(21).normal(size=a.shape) * edge
+    r = np.where(np.arange(NSCALE) % 2 == 0, 0.25 * edge, edge)
+    items = np.ascontiguousarray(np.concatenate([a, b, r[:, None]], axis=1))
+    if off:
+        vv = vv + off
+        items[:, 0:6] += off
+    return vv, vidx, items, segments_within_ref(vv, vidx, None, items)
+
+
+def scale_conditions(w: SegRows):
+    """What the range tests need of the case: at least 32 items without a row, at least 32 with several, a crossing row."""
+    per = wr.rows_per_item(w, NSCALE)
+    assert (per == 0).sum() >= 32 and (per >= 2).sum() >= 32 and (w.cross == 1).any(), (int((per == 0).sum()), int((per >= 2).sum()), int(w.cross.sum()))
+    return per
+
+
+def scaled_rows(w: SegRows, k) -> SegRows:
+    """The rows of the case at 2^k, from the k = 0 rows: dist and the two points times 2^k, everything else unchanged."""
+    return w._replace(dist=np.ldexp(w.dist, k), on_seg=np.ldexp(w.on_seg, k), on_tri=np.ldexp(w.on_tri, k))

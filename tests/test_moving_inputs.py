@@ -5,18 +5,25 @@ comparisons of the witness, contour, nearest-triangle, all-within, every-hit and
 right frame's result is changed.  The conditions the all-results and swept-point queries need of their items -- items without a row,
 items with several, contacts strictly inside the step, a block that overflows its shard -- are asserted here too.  So are those of
 the self-nearest and inside references: rows with a partner, points with a face over them, points inside, covers the tie rule decided;
-and the two routes to the self-nearest rows (the reduced proximity restatement, all pairs cut to the radius) agree column by column."""
+and the two routes to the self-nearest rows (the reduced proximity restatement, all pairs cut to the radius) agree column by column.
+The box, plane, segment and swept-segment comparisons are held to the same three things at the end of the file: the previous frame's
+result fails each of them, one changed value of any column, count or output fails them, and in every frame of the large sequences the
+items include some without a row, some with several, planes with faces on both sides and planes that cut nothing, contacts strictly
+inside the step, and on jitter's dense frame a block that overflows its shard in a frame with more than twice the rows of the last."""
 from __future__ import annotations
 
 import numpy as np
 import pytest
 
+import box_ref as bx
 import moving_inputs as mi
 import nearest_ref as nr
 import nearest_self_ref as ns
 import oracle
+import plane_ref as plr
 import proximity_ref as pr
 import scale_inputs as si
+import segment_ref as sg
 import sweep_ref as sw
 import swept_ref as sr
 import within_ref as wn
@@ -639,3 +646,230 @@ def test_the_two_routes_to_the_nearest_rows_agree_on_a_frame_of_the_apart_schedu
     f0 = mi.APART_INF_FRAMES[1]
     with pytest.raises(AssertionError):                                         # the rows at +inf of one frame against another's
         mi.same_nearest(mi.nearest_call(nr.within(rows, mi.NEAREST_R)), mi.want_between(mi.APART, f0)["near"], "apart")
+
+
+# ---------------------------------------------------------------- boxes, planes, segments and swept segments
+def _tuple_differs(a, b):
+    return any(x.shape != y.shape or x.tobytes() != y.tobytes() for x, y in zip(a, b))
+
+
+def _new_row_sets(name, f):
+    """(label, rows of frame f - 1, rows of frame f) of the four new all-results calls as test_moving_mesh_gpu.py makes them."""
+    sets = [("boxes", mi.want_boxes(name, f - 1), mi.want_boxes(name, f)), ("planes", mi.want_planes(name, f - 1), mi.want_planes(name, f)),
+            ("segments", mi.want_segments(name, f - 1), mi.want_segments(name, f)),
+            ("swept segments", mi.want_swept_segments(name, f - 1)[0], mi.want_swept_segments(name, f)[0]),
+            ("swept segments, the mesh at rest", mi.want_swept_segments_still(name, f - 1)[0], mi.want_swept_segments_still(name, f)[0])]
+    if name in mi.SELF_SWEEP:
+        sets.append(("the mesh's own edges", mi.want_self_swept_segments(name, f - 1)[0], mi.want_self_swept_segments(name, f)[0]))
+    return sets
+
+
+@pytest.mark.parametrize("name", mi.NAMES)
+def test_box_plane_segment_and_swept_segment_comparisons_raise_on_the_previous_frames_result(name):
+    """cd_boxes_overlap_all / cd_boxes_count, cd_planes_cut_all / cd_planes_count, cd_segments_within / cd_segments_closest and
+    cd_sweep_segments_all / cd_sweep_segments: every comparison test_moving_mesh_gpu.py makes passes on the frame's own restatement and
+    raises on the one of the frame before it, in every frame of every sequence -- the count calls included, plain and CD_BOX_ANY:
+    the kinds of box_ref.make_boxes meet the mesh or miss it by construction, but whether a near box of moving_inputs.box_items does
+    depends on the frame.  The box counts also raise on what a device that kept the previous frame's TREE would answer for this
+    frame's boxes (moving_inputs.stale_boxes), ANY included.  (On a tiny mesh two frames' PLANE counts can be the same numbers: that
+    comparison must raise whenever the expected counts differ, and they do differ in some frame of every sequence.)"""
+    s = mi.seq(name)
+    large = name in mi.LARGE
+    planes_changed = 0
+    for f in range(1, len(s)):
+        what = f"{name} frame {f}"
+        for label, w0, w1 in _new_row_sets(name, f):
+            w = f"{what} {label}"
+            mi.same_item_rows(mi.item_call(w1), w1, w)
+            mi.same_item_rows(mi.item_call(w1), mi.item_rows(mi.item_call(w1)), w)      # (the form the fresh context's result is compared in)
+            if w0.rows.shape[0] or w1.rows.shape[0]:
+                with pytest.raises(AssertionError):
+                    mi.same_item_rows(mi.item_call(w0), w1, w)
+            with pytest.raises(AssertionError):                                 # the return code
+                mi.same_item_rows(mi.item_call(w1, rc=1), w1, w)
+        nb0, nb = mi.box_items(name, f - 1).shape[0], mi.box_items(name, f).shape[0]
+        b0, b1 = mi.want_boxes(name, f - 1), mi.want_boxes(name, f)
+        for any_ in (False, True):
+            mi.same_box_counts(mi.box_count_call(b1, nb, any_), b1, nb, what, any_)
+            with pytest.raises(AssertionError):                                 # the previous frame's expected counts
+                mi.same_box_counts(mi.box_count_call(b0, nb0, any_), b1, nb, what, any_)
+            with pytest.raises(AssertionError):                                 # this frame's boxes on the previous frame's tree
+                mi.same_box_counts(mi.box_count_call(mi.stale_boxes(name, f), nb, any_), b1, nb, what, any_)
+        with pytest.raises(AssertionError):
+            mi.same_item_rows(mi.item_call(mi.stale_boxes(name, f)), b1, what + " boxes on the previous frame's tree")
+        c0, c1 = mi.want_plane_classes(name, f - 1), mi.want_plane_classes(name, f)
+        mi.same_plane_counts(mi.plane_count_call(c1), c1, what)
+        if large or _tuple_differs(mi.plane_count_call(c0)[:3], mi.plane_count_call(c1)[:3]):
+            planes_changed += 1
+            with pytest.raises(AssertionError):
+                mi.same_plane_counts(mi.plane_count_call(c0), c1, what)
+        g0, g1 = mi.want_segments(name, f - 1), mi.want_segments(name, f)
+        n0, n1 = mi.segment_items(name, f - 1).shape[0], mi.segment_items(name, f).shape[0]
+        mi.same_segment_closest(mi.segment_closest_call(g1, n1), g1, n1, what)
+        with pytest.raises(AssertionError):                                     # (the segments with r = +inf have a row in every frame)
+            mi.same_segment_closest(mi.segment_closest_call(g0, n0), g1, n1, what)
+        face = mi.segment_closest_call(g1, n1)
+        mi.same_segment_any(face[0], face[11], g1, n1, what)
+        with pytest.raises(AssertionError):                                     # the previous frame's faces against this frame's rows
+            stale = mi.segment_closest_call(g0, n0)
+            mi.same_segment_any(stale[0], stale[11], g1, n1, what)
+        firsts = [("swept segments", mi.want_swept_segments, mi.swept_segment_items),
+                  ("swept segments, the mesh at rest", mi.want_swept_segments_still, mi.swept_segment_items)]
+        if name in mi.SELF_SWEEP:
+            firsts.append(("the mesh's own edges", mi.want_self_swept_segments, lambda n_, k: mi.self_swept_segment_items(n_, k)[0]))
+        for label, want, items in firsts:
+            w0, w1 = want(name, f - 1)[0], want(name, f)[0]
+            m0, m1 = items(name, f - 1).shape[0], items(name, f).shape[0]
+            mi.same_sweep_segments(mi.sweep_segments_call(w1, m1), w1, m1, f"{what} {label}")
+            if w0.rows.shape[0] or w1.rows.shape[0]:
+                with pytest.raises(AssertionError):
+                    mi.same_sweep_segments(mi.sweep_segments_call(w0, m0), w1, m1, f"{what} {label}")
+        assert mi.want_swept_segments(name, f - 1)[1] != mi.want_swept_segments(name, f)[1], what     # ... and so do the counts compared beside the rows
+    assert planes_changed > 0, name
+    # the swept rows depend on the end positions: the same items against the mesh at rest are another row set
+    assert any(mi.want_swept_segments(name, f)[0].rows.shape != mi.want_swept_segments_still(name, f)[0].rows.shape
+               or not np.array_equal(mi.want_swept_segments(name, f)[0].toi, mi.want_swept_segments_still(name, f)[0].toi) for f in range(len(s))), name
+
+
+def _corrupt(a, k):
+    """One value of row k of a column changed: the lowest bit of a double, bit 0 of anything else."""
+    if a.dtype == np.float64:
+        _flip_lowest_bit(a.reshape(a.shape[0], -1), (k, 0))
+    else:
+        a.reshape(a.shape[0], -1)[k, 0] ^= 1
+
+
+def test_one_corrupted_field_of_a_box_plane_segment_or_swept_segment_result_raises():
+    """The right frame's result with ONE value changed: every column of every new row type, one face, one row dropped; every count
+    array of cd_boxes_count (plain and ANY) and cd_planes_count and their n_found; every output of cd_segments_closest and of
+    cd_sweep_segments and their n_found."""
+    name, f = "jitter", 1
+    for rows in (mi.want_boxes(name, f), mi.want_planes(name, f), mi.want_segments(name, f), mi.want_swept_segments(name, f)[0]):
+        k = rows.rows.shape[0] // 2
+        assert k > 0
+        for field in rows._fields[1:]:
+            bad = _copy(rows)
+            _corrupt(getattr(bad, field), k)
+            with pytest.raises(AssertionError):
+                mi.same_item_rows(mi.item_call(bad), rows, (type(rows).__name__, field))
+        bad = _copy(rows)
+        bad.rows[k, 1] ^= 1
+        with pytest.raises(AssertionError):
+            mi.same_item_rows(mi.item_call(bad), rows, "face")
+        with pytest.raises(AssertionError):
+            mi.same_item_rows(mi.item_call(type(rows)(*(np.delete(a, k, axis=0) for a in rows))), rows, "a row less")
+    boxes, nb = mi.want_boxes(name, f), mi.box_items(name, f).shape[0]
+    for any_ in (False, True):
+        good = mi.box_count_call(boxes, nb, any_)
+        for j in range(1 if any_ else 2):
+            bad = [a if a is None else a.copy() for a in good[:2]]
+            bad[j][nb // 2] ^= 1
+            with pytest.raises(AssertionError):
+                mi.same_box_counts((bad[0], bad[1], good[2]), boxes, nb, ("count", j), any_)
+        with pytest.raises(AssertionError):                                     # n_found alone
+            mi.same_box_counts(good[:2] + (mi.mi355cd.CdBoxInfo(good[2].n_found + 1, 0, 0),), boxes, nb, "n_found", any_)
+    cls = mi.want_plane_classes(name, f)
+    good = mi.plane_count_call(cls)
+    for j in range(3):
+        bad = [a.copy() for a in good[:3]]
+        bad[j][mi.NPLANES // 2] += 1
+        with pytest.raises(AssertionError):
+            mi.same_plane_counts(tuple(bad) + (good[3],), cls, ("plane count", j))
+    with pytest.raises(AssertionError):
+        mi.same_plane_counts(good[:3] + (mi.mi355cd.CdPlaneInfo(good[3].n_found + 1, 0, 0),), cls, "n_found")
+    for rows, n, call, same, info in ((mi.want_segments(name, f), mi.segment_items(name, f).shape[0], mi.segment_closest_call, mi.same_segment_closest, mi.mi355cd.CdSegmentInfo),
+                                      (mi.want_swept_segments(name, f)[0], mi.swept_segment_items(name, f).shape[0], mi.sweep_segments_call, mi.same_sweep_segments, mi.mi355cd.CdPointInfo)):
+        good = call(rows, n)
+        item = int(np.flatnonzero(wn.rows_per_item(rows, n) >= 2)[3])
+        for j in range(len(good) - 1):
+            bad = [a.copy() for a in good[:-1]]
+            _corrupt(bad[j], item)
+            with pytest.raises(AssertionError):
+                same(tuple(bad) + (good[-1],), rows, n, ("output", j))
+        with pytest.raises(AssertionError):                                     # n_found alone
+            same(good[:-1] + (info(good[-1].n_found + 1, 0, 0),), rows, n, "n_found")
+        rest = type(rows)(*(a[~((rows.rows[:, 0] == item) & (rows.rows[:, 1] == good[0][item]))] for a in rows))      # the rows without that item's first
+        with pytest.raises(AssertionError):
+            same(call(rest, n), rows, n, "the second row")
+    segs, n = mi.want_segments(name, f), mi.segment_items(name, f).shape[0]
+    good = mi.segment_closest_call(segs, n)
+    none = int(np.flatnonzero(good[0] == sg.NONE)[0])
+    face = good[0].copy(); face[none] = 0
+    with pytest.raises(AssertionError):                                         # ANY: a face for a segment that has no row
+        mi.same_segment_any(face, good[11], segs, n, "any")
+    has = int(np.flatnonzero(good[0] != sg.NONE)[5])
+    face = good[0].copy(); face[has] = np.setdiff1d(np.arange(mi.seq(name).nt), segs.rows[segs.rows[:, 0] == has, 1])[0]
+    with pytest.raises(AssertionError):                                         # ANY: a face that is no row of the segment
+        mi.same_segment_any(face, good[11], segs, n, "any")
+
+
+@pytest.mark.parametrize("name", mi.LARGE)
+def test_new_item_queries_cannot_pass_vacuously(name):
+    """In EVERY frame of the large sequences: at least 32 boxes, segments and swept segments have no row and at least 32 of each have
+    two or more; the root box's rows are every triangle, all inside; every point box has a row; the segments with r = +inf have every
+    triangle; some plane has faces cut, below and above, and some plane cuts nothing; some swept-segment row has 0 < toi < 1; no
+    swept-segment row is unresolved; the segment rows have crossings and rows that are none."""
+    s = mi.seq(name)
+    low = dict(none=1 << 30, several=1 << 30, inside=1 << 30)
+    for f in range(len(s)):
+        what = (name, f)
+        boxes, segs, (swept, counts) = mi.want_boxes(name, f), mi.want_segments(name, f), mi.want_swept_segments(name, f)
+        for rows, n in ((boxes, mi.box_items(name, f).shape[0]), (segs, mi.segment_items(name, f).shape[0]), (swept, mi.swept_segment_items(name, f).shape[0])):
+            c = wn.rows_per_item(rows, n)
+            assert (c == 0).sum() >= 32 and (c >= 2).sum() >= 32, (what, type(rows).__name__, int((c == 0).sum()), int((c >= 2).sum()))
+            low["none"], low["several"] = min(low["none"], int((c == 0).sum())), min(low["several"], int((c >= 2).sum()))
+        c, ci = bx.counts_of(boxes, mi.box_items(name, f).shape[0])
+        assert c[mi.NBOX] == s.nt == ci[mi.NBOX] and (c[mi.NBOX + 1:mi.NBOX + 1 + mi.POINT_BOXES] >= 1).all(), what
+        near = c[mi.NBOX + 1 + mi.POINT_BOXES:] > 0                             # the near boxes: some meet a face and some do not, in every frame
+        assert near.shape[0] == mi.NEAR_BOXES and near.sum() >= 4 and (~near).sum() >= 4, (what, int(near.sum()))
+        assert np.array_equal(mi.box_items(name, f)[mi.NBOX], mi.want_root_box(name, f)), what
+        assert boxes.inside.any() and not boxes.inside.all(), what
+        it = mi.segment_items(name, f)
+        c = wn.rows_per_item(segs, it.shape[0])
+        assert np.isinf(it[list(mi.SEG_INF), 6]).all() and (c[list(mi.SEG_INF)] == s.nt).all() and np.isfinite(np.delete(it[:, 6], mi.SEG_INF)).all(), what
+        assert (it[:mi.NI:mi.SEG_POINT_EVERY, 0:3] == it[:mi.NI:mi.SEG_POINT_EVERY, 3:6]).all() and (segs.cross == 1).any() and (segs.cross == 0).any(), what
+        r = it[:mi.NI, 6][np.isfinite(it[:mi.NI, 6])]
+        assert np.unique(r).size == 3, what                                  # three radii, by i % 3
+        n_cut, n_below, n_above = plr.counts_of_classes(mi.want_plane_classes(name, f))
+        assert ((n_cut > 0) & (n_below > 0) & (n_above > 0)).any() and (n_cut == 0).any() and mi.want_planes(name, f).rows.shape[0] == n_cut.sum(), what
+        inside = int(((swept.toi > 0) & (swept.toi < 1)).sum())
+        assert inside >= 1 and counts[2] == 0 and mi.want_swept_segments_still(name, f)[1][2] == 0, (what, inside, counts)
+        low["inside"] = min(low["inside"], inside)
+        if name in mi.SELF_SWEEP:
+            own, own_counts = mi.want_self_swept_segments(name, f)
+            e = mi.mesh_edges(name)
+            assert own.rows.shape[0] > 100 and own_counts[2] == 0 and ((own.toi > 0) & (own.toi < 1)).any() and e.shape[0] % 64 != 0, what
+            assert not (s.vidx[own.rows[:, 1]][:, :, None] == e[own.rows[:, 0]][:, None, :]).any()       # no face at either end of the edge
+    print(f"{name}: the smallest over its frames and the three item sets: items with no row {low['none']}, with several {low['several']}; swept-segment rows with 0 < toi < 1: {low['inside']}")
+
+
+def test_tiny_sequences_have_box_plane_segment_and_swept_segment_rows_in_some_frame():
+    for n in mi.TINY:
+        name = f"tiny{n}"
+        rows = [(mi.want_boxes(name, f).rows.shape[0], mi.want_planes(name, f).rows.shape[0], mi.want_segments(name, f).rows.shape[0],
+                 mi.want_swept_segments(name, f)[0].rows.shape[0], mi.want_swept_segments_still(name, f)[0].rows.shape[0]) for f in range(len(mi.seq(name)))]
+        print(f"{name}: (boxes, planes, segments, swept segments, swept segments at rest) rows a frame: {rows}")
+        assert all(max(r[k] for r in rows) > 0 for k in range(5)), (name, rows)
+
+
+def test_the_segment_growth_block_overflows_a_shard_and_the_dense_frame_more_than_doubles_the_rows():
+    """Items SEG_GROWTH_AT .. SEG_GROWTH_AT + 63 of jitter's dense frame are ONE block of the descent (one shard), and their rows alone are
+    more than the shard's first WITHIN_SHARD_FIRST slots, for cd_segments_within and for cd_sweep_segments_all moving and at rest: the pass
+    must grow its candidate buffer and run again.  The frame's rows are more than twice the frame's before it, so a row buffer of twice
+    the previous frame's rows does not hold them: the row buffers grow there too, and are oversized on the sparse frames after it."""
+    f = mi.JITTER_DENSE_FRAME
+    assert mi.SEG_GROWTH_AT % 64 == 0 and mi.GROWTH_ITEMS == 64 and mi.SEG_GROWTH_AT >= mi.NI
+    figures = []
+    for items, want in ((mi.segment_items, mi.want_segments), (mi.swept_segment_items, lambda n, k: mi.want_swept_segments(n, k)[0]),
+                        (mi.swept_segment_items, lambda n, k: mi.want_swept_segments_still(n, k)[0])):
+        assert items("jitter", f).shape[0] == mi.SEG_GROWTH_AT + mi.GROWTH_ITEMS
+        rows = want("jitter", f)
+        blk = int((rows.rows[:, 0] >= mi.SEG_GROWTH_AT).sum())
+        fill = int(((rows.rows[:, 0] >= mi.NI) & (rows.rows[:, 0] < mi.SEG_GROWTH_AT)).sum())
+        figures.append((blk, rows.rows.shape[0], want("jitter", f - 1).rows.shape[0]))
+        assert blk > mi.mi355cd.WITHIN_SHARD_FIRST and fill == 0, (blk, fill)
+        assert rows.rows.shape[0] > 2 * want("jitter", f - 1).rows.shape[0] and all(want("jitter", g).rows.shape[0] < rows.rows.shape[0] // 2 for g in range(f + 1, len(mi.seq("jitter"))))
+        for g in range(len(mi.seq("jitter"))):
+            assert (items("jitter", g).shape[0] == mi.NI) == (g != f)
+    print("jitter's growth block: (rows of the block, of the dense frame, of the frame before) for segments, swept segments, swept segments at rest:", figures,
+          "of", mi.mi355cd.WITHIN_SHARD_FIRST, "slots")

@@ -33,6 +33,25 @@ whatever an entry leaves stale of those shows here.  Between cd_update_vertices 
 CD_ERR_ORDER and write nothing.  Their node_visits and tri_tests are compared with nothing (tiny1's node_visits of
 cd_points_inside is 0: there is no record to walk).
 
+And the boxes, planes, segments and swept segments: cd_boxes_overlap_all / cd_boxes_count ("boxes": 258 boxes of box_ref.make_boxes on
+the frame's vertices, the frame's root box exactly -- every triangle a row, all inside -- 16 point boxes on vertices, and 32 small
+boxes beside the surface, which meet a face or not by where this frame's faces lie: CD_BOX_ANY's answer changes with the frame),
+cd_planes_cut_all / cd_planes_count ("planes": 24 of plane_ref.make_planes), cd_segments_within / cd_segments_closest ("segments": 250 at
+the frame's points, three radii by i % 3, every eighth a point, two at +inf) and cd_sweep_segments_all / cd_sweep_segments ("swept
+segments": 250 free segments moving by 0.6 edges, the mesh moving to the CCD queries' end positions, once more at rest behind every
+entry but self_ccd, and on `slide` and `float_double` every fifth edge of the mesh itself with skip_vertices) are in the permuted list,
+against box_ref's, plane_ref's, segment_ref's and swept_segment_ref's all-pairs restatements: the set of (item, face), then every
+column by its bytes, and the same against the fresh context's rows.  Their row buffers get twice the frame's row count; on jitter's
+dense frame the growth block, as items 256 .. 319 of the segments and swept segments, overflows its shard of the candidate buffer, and
+the frame has more than twice the rows of the one before.  What links the calls is held to the DEVICE's own rows: cd_boxes_count (plain
+and ANY) is their per-box sum, cd_planes_count's n_cut their per-plane count (all three counts are counts_of_classes of the
+restatement's classes and add up to nt), cd_segments_closest is closest_of of them, ANY "has a row" with a face that is one, its point
+items cd_closest_points of the same point and radius byte for byte, and cd_sweep_segments is first_of of them.  cd_debug_swept reads the
+same bytes after the swept-segment calls as before them; tiny1's count calls report node_visits == 0; between cd_update_vertices and
+the entry all eight return CD_ERR_ORDER and write nothing.  boxes_tested, planes_tested, segments_tested and the bytes of
+sweep_segments_info are compared with the fresh context's, (n_tested, n_evals, n_unresolved) with swept_segment_ref's counts; node_visits
+and tri_tests of cd_boxes_count, cd_planes_count, cd_segments_closest and cd_sweep_segments with nothing: they count the walk.
+
 Counters that are NOT compared with the fresh context's: node_visits and tri_tests of cd_cast_rays / cd_closest_points /
 cd_sweep_points / cd_nearest_between / cd_nearest_self / cd_points_inside / cd_signed_distance (cd_nearest_between and cd_nearest_self
 also not with a restatement: nearest_ref has no walk), and the collision step's node_visits and
@@ -57,8 +76,12 @@ import nearest_self_ref as ns
 import proximity_ref as pr
 import swept_ref as sr
 import within_ref as wn
+from test_boxes_gpu import _Raw as RawBoxes
 from test_inside_gpu import _raw as raw_inside
 from test_nearest_self_gpu import _raw as raw_nearest_self, _untouched as untouched_nearest_self
+from test_planes_gpu import _Raw as RawPlanes
+from test_segments_gpu import _Raw as RawSegments
+from test_sweep_segments_gpu import _Raw as RawSweepSegments
 
 pytestmark = pytest.mark.gpu
 
@@ -336,10 +359,114 @@ def _queries(cd, fresh, name, f, entry=None):
         assert np.array_equal(np.signbit(sdist), ins & (near[2] > 0)), w
         assert info.n_found == p.shape[0], (w, info.n_found)
 
+    def boxes():
+        b = mi.box_items(name, f)
+        lo, hi, n = b[:, 0::2], b[:, 1::2], b.shape[0]
+        want = mi.want_boxes(name, f)
+        got = cd.boxes_overlap_all(lo, hi, cap=room(want))
+        tested = cd.boxes_tested
+        mi.same_item_rows(got, want, what + " boxes")
+        mi.same_item_rows(got, mi.item_rows(fresh.boxes_overlap_all(lo, hi, cap=room(want))), what + " boxes against the fresh context")
+        assert tested == fresh.boxes_tested and tested >= got[-2], (what, tested, fresh.boxes_tested)
+        own = mi.item_rows(got)                                                 # the count calls are the per-item sums of the DEVICE's rows
+        for any_ in (False, True):
+            c, cf = cd.boxes_count(lo, hi, any=any_), fresh.boxes_count(lo, hi, any=any_)
+            mi.same_box_counts(c, own, n, f"{what} boxes count{', ANY' if any_ else ''}", any_)
+            _equal_bytes(c[:1 if any_ else 2], cf[:1 if any_ else 2], what + " boxes count against the fresh context")
+            assert c[2].n_found == cf[2].n_found, what
+            if s.nt == 1:                                                       # no record to walk
+                assert c[2].node_visits == 0, (what, c[2].node_visits)
+            elif not any_:
+                assert c[0][mi.NBOX] == s.nt == c[1][mi.NBOX], what             # the root box: the whole mesh, all of it inside
+
+    def planes():
+        p = mi.plane_items(name, f)
+        nrm, d = p[:, :3], p[:, 3]
+        want, cls = mi.want_planes(name, f), mi.want_plane_classes(name, f)
+        got = cd.planes_cut_all(nrm, d, cap=room(want))
+        tested = cd.planes_tested
+        mi.same_item_rows(got, want, what + " planes")
+        mi.same_item_rows(got, mi.item_rows(fresh.planes_cut_all(nrm, d, cap=room(want))), what + " planes against the fresh context")
+        assert tested == fresh.planes_tested and tested >= got[-2], (what, tested, fresh.planes_tested)
+        c, cf = cd.planes_count(nrm, d), fresh.planes_count(nrm, d)
+        mi.same_plane_counts(c, cls, what + " planes count")                    # (... and the three add up to nt)
+        assert np.array_equal(c[0], wn.rows_per_item(mi.item_rows(got), p.shape[0])), what + " planes count: n_cut is the device's own rows a plane"
+        _equal_bytes(c[:3], cf[:3], what + " planes count against the fresh context")
+        assert c[3].n_found == cf[3].n_found, what
+        if s.nt == 1:
+            assert c[3].node_visits == 0, (what, c[3].node_visits)
+
+    def segments():
+        it = mi.segment_items(name, f)
+        a, b, r, n = it[:, 0:3], it[:, 3:6], it[:, 6], it.shape[0]
+        want = mi.want_segments(name, f)
+        got = cd.segments_within(a, b, r, cap=room(want))
+        tested = cd.segments_tested
+        mi.same_item_rows(got, want, what + " segments")
+        mi.same_item_rows(got, mi.item_rows(fresh.segments_within(a, b, r, cap=room(want))), what + " segments against the fresh context")
+        assert tested == fresh.segments_tested and tested >= got[-2], (what, tested, fresh.segments_tested)
+        if n > mi.NI:                                                           # the dense frame: the growth block alone overflows its shard
+            assert int((got[0][:, 0] >= mi.SEG_GROWTH_AT).sum()) > mi355cd.WITHIN_SHARD_FIRST, what
+        own = mi.item_rows(got)
+        single = cd.segments_closest(a, b, r)
+        mi.same_segment_closest(single, own, n, what + " segments: the smallest row a segment")
+        sf = fresh.segments_closest(a, b, r)
+        _equal_bytes(single[:11], sf[:11], what + " segments closest against the fresh context")
+        assert single[11].n_found == sf[11].n_found, what
+        face, info = cd.segments_closest(a, b, r, any_within=True)
+        mi.same_segment_any(face, info, own, n, what + " segments, ANY")
+        pt = np.arange(0, mi.NI, mi.SEG_POINT_EVERY)                            # b == a: cd_closest_points (pinned by point_queries) byte for byte
+        assert np.array_equal(a[pt], b[pt])
+        near = cd.closest_points(a[pt], r[pt])
+        _equal_bytes(tuple(single[k][pt] for k in (0, 1, 2, 5, 6, 7, 10)), near[:7], what + " segments: the point items against closest_points")
+
+    def swept_segments():
+        it, e = mi.swept_segment_items(name, f), mi.x1(name, f)
+        n = it.shape[0]
+        want, counts = mi.want_swept_segments(name, f)
+        before = _swept(cd)
+        ends = lambda x: (x[:, 0:3], x[:, 3:6], x[:, 6:9], x[:, 9:12], x[:, 12])
+        sweep = lambda c, items, end, rows, skip=None: c.sweep_segments_all(*ends(items), verts_end=end, skip_vertices=skip, cap=room(rows))
+        tally = lambda i: (i.n_tested, i.n_evals, i.n_unresolved)
+        got = sweep(cd, it, e, want)
+        info = cd.sweep_segments_info
+        mi.same_item_rows(got, want, what + " swept segments")
+        assert tally(info) == counts and info.n_candidates >= info.n_tested, (what, tally(info), counts, info.n_candidates)
+        gf = sweep(fresh, it, e, want)
+        fi = fresh.sweep_segments_info
+        mi.same_item_rows(got, mi.item_rows(gf), what + " swept segments against the fresh context")
+        assert bytes(info) == bytes(fi), (what, [(k, getattr(info, k), getattr(fi, k)) for k, _ in mi355cd.CdCcdInfo._fields_])
+        if n > mi.NI:
+            assert int((got[0][:, 0] >= mi.SEG_GROWTH_AT).sum()) > mi355cd.WITHIN_SHARD_FIRST, what
+        first = cd.sweep_segments(*ends(it), verts_end=e)
+        mi.same_sweep_segments(first, mi.item_rows(got), n, what + " swept segments: the first row an item")
+        ff = fresh.sweep_segments(*ends(it), verts_end=e)
+        _equal_bytes(first[:12], ff[:12], what + " swept segments, first contact against the fresh context")
+        assert first[12].n_found == ff[12].n_found, what
+        if entry != "self_ccd":                                                 # the mesh at rest
+            still, still_counts = mi.want_swept_segments_still(name, f)
+            got = sweep(cd, it, None, still)
+            mi.same_item_rows(got, still, what + " swept segments, the mesh at rest")
+            assert tally(cd.sweep_segments_info) == still_counts, (what, tally(cd.sweep_segments_info), still_counts)
+            mi.same_sweep_segments(cd.sweep_segments(*ends(it)), mi.item_rows(got), n, what + " swept segments, the mesh at rest: the first row an item")
+        if name in mi.SELF_SWEEP:                                               # the mesh's own edges against its own faces
+            (items, skip), (own, own_counts) = mi.self_swept_segment_items(name, f), mi.want_self_swept_segments(name, f)
+            got = sweep(cd, items, e, own, skip)
+            mi.same_item_rows(got, own, what + " swept segments, the mesh's own edges")
+            assert tally(cd.sweep_segments_info) == own_counts, (what, tally(cd.sweep_segments_info), own_counts)
+            mi.same_item_rows(got, mi.item_rows(sweep(fresh, items, e, own, skip)), what + " the mesh's own edges against the fresh context")
+            mi.same_sweep_segments(cd.sweep_segments(*ends(items), verts_end=e, skip_vertices=skip), own, items.shape[0], what + " the mesh's own edges")
+        after = _swept(cd)                                                      # swept[0] is the CCD pass's: no swept segment may touch it
+        assert (before is None) == (after is None), what
+        if before is not None:
+            _equal_bytes(before[:3], after[:3], what + " the CCD pass's swept tree after the swept segments")
+            assert before[3] == after[3] and sr.bits1(before[4]) == sr.bits1(after[4]), what
+
     return [("proximity", proximity), ("ccd", ccd), ("rays", ray_queries), ("points", point_queries), ("root box", box),
             ("proximity witness", proximity_witness), ("ccd witness", ccd_witness), ("contour", contour),
             ("all within", all_within), ("every hit", every_hit), ("swept points", swept_points),
-            ("nearest self", nearest_self), ("inside", inside), ("signed distance", signed_distance)]
+            ("nearest self", nearest_self), ("inside", inside), ("signed distance", signed_distance),
+            ("boxes", boxes), ("planes", planes), ("segments", segments), ("swept segments", swept_segments)]
 
 
 def _swept(cd):
@@ -351,9 +478,44 @@ def _swept(cd):
         return None
 
 
-def _order_errors_self(cd, pts, rmax):
+def _order_errors_items(cd, name, f):
+    """The same for the box, plane, segment and swept-segment calls, all eight, on the frame's own items (the first 64): CD_ERR_ORDER,
+    and nothing written into the canary-filled rows, values, counts, faces and info structs."""
+    lib, E = cd.lib, mi355cd.CD_ERR_ORDER
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    first = lambda items: np.ascontiguousarray(items[:64])
+    canary = lambda: np.full(64, 7, dtype=np.uint32)
+    untouched = lambda arrays, info: all((a == 7).all() for a in arrays) and (info.n_found, info.node_visits, info.tri_tests) == (5, 5, 5)
+    boxes, planes, segs, sweeps = first(mi.box_items(name, f)), first(mi.plane_items(name, f)), first(mi.segment_items(name, f)), first(mi.swept_segment_items(name, f))
+    x1 = np.ascontiguousarray(mi.x1(name, f), dtype=np.float64)
+    r = RawBoxes(cd, 256)
+    assert r.call(boxes, 256) == E and r.nothing_written(), "cd_boxes_overlap_all"
+    for flags in (0, mi355cd.CD_BOX_ANY):
+        count, n_inside, info = canary(), canary(), mi355cd.CdBoxInfo(5, 5, 5)
+        rc = lib.cd_boxes_count(cd._ctx, vp(boxes), boxes.shape[0], flags, vp(count), None if flags else vp(n_inside), C.byref(info))
+        assert rc == E and untouched((count, n_inside), info), ("cd_boxes_count", flags, rc)
+    r = RawPlanes(cd, 256)
+    assert r.call(planes, 256) == E and r.nothing_written(), "cd_planes_cut_all"
+    counts, info = [canary() for _ in range(3)], mi355cd.CdPlaneInfo(5, 5, 5)
+    rc = lib.cd_planes_count(cd._ctx, vp(planes), planes.shape[0], *map(vp, counts), C.byref(info))
+    assert rc == E and untouched(counts, info), ("cd_planes_count", rc)
+    r = RawSegments(cd, 256)
+    assert r.call(segs, 256) == E and r.closest(segs) == E and r.nothing_written(), "cd_segments_within, cd_segments_closest"
+    assert r.closest(segs, flags=mi355cd.CD_SEGMENT_ANY, out=False) == E and r.nothing_written(), "cd_segments_closest, ANY"
+    for end in (x1, None):
+        r = RawSweepSegments(cd, 256)
+        assert r.call(sweeps, 256, end) == E and r.nothing_written(), "cd_sweep_segments_all"
+        assert tuple(getattr(r.info, k) for k, _ in mi355cd.CdCcdInfo._fields_) == (7,) * 4, "cd_sweep_segments_all wrote into its info"
+        face, info = canary(), mi355cd.CdPointInfo(5, 5, 5)
+        rc = lib.cd_sweep_segments(cd._ctx, None if end is None else vp(end), vp(sweeps), sweeps.shape[0], None, 0, vp(face), C.byref(r.out), C.byref(info))
+        assert rc == E and untouched((face,), info) and r.nothing_written(), ("cd_sweep_segments", rc)
+
+
+def _order_errors_self(cd, pts, rmax, name, f):
     """The vertices moved and the tree was not rebuilt: cd_nearest_self (both flags), cd_points_inside and cd_signed_distance return
-    CD_ERR_ORDER and write nothing -- not a row of the canary-filled outputs, not a field of the info structs."""
+    CD_ERR_ORDER and write nothing -- not a row of the canary-filled outputs, not a field of the info structs.  Neither do the eight
+    box, plane, segment and swept-segment calls (_order_errors_items)."""
+    _order_errors_items(cd, name, f)
     lib, E = cd.lib, mi355cd.CD_ERR_ORDER
     info = mi355cd.CdNearestInfo(5, 5, 5)
     for r in (rmax, INF):
@@ -385,7 +547,7 @@ def _run(name, schedule):
                 for _ in range(70):
                     cd.build_tree()
             cd.update_vertices(v)
-            _order_errors_self(cd, mi.inside_points(name, f, 2), mi.nearest_self_r(name, f))
+            _order_errors_self(cd, mi.inside_points(name, f, 2), mi.nearest_self_r(name, f), name, f)
             _rebuild(cd, entry, name, f)
             used.append(entry)
             if name == "frame_exit":

@@ -224,7 +224,8 @@ def test_moving():
 def test_queries_after():
     """The multi step as a rebuild entry: one rank, real RCCL, CD_MULTI_SELF_PEER; per frame of the jitter sequence
     cd_update_vertices, the step, then cd_root_box, cd_find_proximity, cd_closest_points, cd_cast_rays, cd_points_within and
-    cd_sorted_pairs, each against the CPU restatement of that frame and a fresh context.  Expected: the step leaves the tree of the
+    cd_sorted_pairs, each against the CPU restatement of that frame and a fresh context; so are cd_boxes_overlap_all, cd_planes_cut_all,
+    cd_segments_within, cd_sweep_segments_all, cd_boxes_count and cd_planes_count on moving_inputs' items of the frame.  Expected: the step leaves the tree of the
     CURRENT vertices (records, leaves, root box cached from the all-gathered boxes) exactly as cd_build_tree would; its pair list is
     two lists, so cd_sorted_pairs answers CD_OVERFLOW without writing while the step found pairs, and n = 0 with CD_OK when it found none."""
     name = mu.QA_NAME
@@ -267,6 +268,38 @@ def test_queries_after():
                     wr.same_rows(rows, mu.want_within(f), what + " points within")
                     gf = fresh.points_within(pts, rm, cap=cap)
                     wr.same_rows(rows, wr.PointRows(*wr.sort_rows(*gf[:7])), what + " points within (fresh)")
+                    # the box, plane, segment and swept-segment rows and the two count calls, on moving_inputs' items of the frame
+                    room = lambda w: max(1, 2 * w.rows.shape[0])
+                    b, p, sg, sw = mi.box_items(name, f), mi.plane_items(name, f), mi.segment_items(name, f), mi.swept_segment_items(name, f)
+                    want = mi.want_boxes(name, f)
+                    got = cd.boxes_overlap_all(b[:, 0::2], b[:, 1::2], cap=room(want))
+                    mi.same_item_rows(got, want, what + " boxes")
+                    mi.same_item_rows(got, mi.item_rows(fresh.boxes_overlap_all(b[:, 0::2], b[:, 1::2], cap=room(want))), what + " boxes (fresh)")
+                    assert cd.boxes_tested == fresh.boxes_tested, what
+                    got = cd.boxes_count(b[:, 0::2], b[:, 1::2])
+                    mi.same_box_counts(got, want, b.shape[0], what + " boxes count")
+                    assert all(np.array_equal(x, y) for x, y in zip(got[:2], fresh.boxes_count(b[:, 0::2], b[:, 1::2])[:2])), what + " boxes count (fresh)"
+                    want = mi.want_planes(name, f)
+                    got = cd.planes_cut_all(p[:, :3], p[:, 3], cap=room(want))
+                    mi.same_item_rows(got, want, what + " planes")
+                    mi.same_item_rows(got, mi.item_rows(fresh.planes_cut_all(p[:, :3], p[:, 3], cap=room(want))), what + " planes (fresh)")
+                    assert cd.planes_tested == fresh.planes_tested, what
+                    got = cd.planes_count(p[:, :3], p[:, 3])
+                    mi.same_plane_counts(got, mi.want_plane_classes(name, f), what + " planes count")
+                    assert all(np.array_equal(x, y) for x, y in zip(got[:3], fresh.planes_count(p[:, :3], p[:, 3])[:3])), what + " planes count (fresh)"
+                    want = mi.want_segments(name, f)
+                    got = cd.segments_within(sg[:, 0:3], sg[:, 3:6], sg[:, 6], cap=room(want))
+                    mi.same_item_rows(got, want, what + " segments")
+                    mi.same_item_rows(got, mi.item_rows(fresh.segments_within(sg[:, 0:3], sg[:, 3:6], sg[:, 6], cap=room(want))), what + " segments (fresh)")
+                    assert cd.segments_tested == fresh.segments_tested, what
+                    want, counts = mi.want_swept_segments(name, f)
+                    ends = (sw[:, 0:3], sw[:, 3:6], sw[:, 6:9], sw[:, 9:12], sw[:, 12])
+                    got = cd.sweep_segments_all(*ends, verts_end=mi.x1(name, f), cap=room(want))
+                    info = cd.sweep_segments_info
+                    mi.same_item_rows(got, want, what + " swept segments")
+                    assert (info.n_tested, info.n_evals, info.n_unresolved) == counts, (what, counts)
+                    mi.same_item_rows(got, mi.item_rows(fresh.sweep_segments_all(*ends, verts_end=mi.x1(name, f), cap=room(want))), what + " swept segments (fresh)")
+                    assert bytes(info) == bytes(fresh.sweep_segments_info), what
                     sentinel = np.full((4, 2), 0xDEADBEEF, dtype=np.uint32)
                     nn = mi355cd.C.c_uint64(12345)
                     assert cd.lib.cd_sorted_pairs(cd._ctx, sentinel.ctypes.data, 4, mi355cd.C.byref(nn)) == OVERFLOW, what

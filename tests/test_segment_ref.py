@@ -226,3 +226,21 @@ def test_the_shared_items_rows_keep_the_bounds_and_conditions():
         assert (err[w.cross == 0] <= sr.WITNESS_BOUND).all() and (err[w.cross == 1] <= sr.CROSS_WITNESS_BOUND).all(), name
         t, td, ok = _against_tri_distance(segs, tris)
         assert (np.abs(td - t.dist)[ok] <= sr.TRI_DISTANCE_BOUND * M[ok]).all(), name
+
+
+@pytest.mark.parametrize("name", sr.SCALE_MESHES)
+def test_the_row_set_of_the_range_case_is_the_same_at_both_fp32_ends(name):
+    """tests/test_segments_gpu.py expects the k = 0 rows at every scale of its band.  That is the restatement's own property: on mesh,
+    ends and radius scaled by 2^-149 and 2^128 segments_within_ref gives the same set of (item, face), the same IDs, s, u, v, feature,
+    end, cross and side, and dist and the two points times 2^k exactly.  The case has items without a row, items with several and
+    crossings (scale_conditions)."""
+    import scale_inputs as si
+    vv, vidx, items, want = sr.scale_case(name)
+    per = sr.scale_conditions(want)
+    print(f"{name}: {want.rows.shape[0]} rows, {int((per == 0).sum())} of {sr.NSCALE} items with none, {int((per >= 2).sum())} with several, {int(want.cross.sum())} crossings")
+    for k in (-149, 128):
+        got = sr.segments_within_ref(si.scaled(vv, k), vidx, None, si.scaled(items, k))
+        sr.wr.same_rows(got, sr.scaled_rows(want, k), f"{name} 2^{k}")
+    off = sr.scale_case(name, 2.0 ** 20 + 0.37)[3]
+    per = sr.scale_conditions(off)
+    print(f"{name} translated: {off.rows.shape[0]} rows, {int((per == 0).sum())} items with none, {int((per >= 2).sum())} with several")

@@ -12,6 +12,7 @@ import mi355_synth as synth
 import mi355cd
 import oracle
 import proximity_ref as pr
+import scale_inputs as si
 import segment_ref as sr
 import within_ref as wr
 
@@ -399,3 +400,44 @@ def test_edges_of_one_cloth_sheet_against_the_other():
           f"worst {err.max():.3g} M, {cd.segments_tested} seg_tri")
     assert ok.sum() > 1000 and (rows.cross == 1).sum() > 0 and c.max() > 1 and (c == 0).any()
     assert (err <= sr.TRI_DISTANCE_BOUND).all() and (rows.dist <= h).all()
+
+
+# ---------------------------------------------------------------- 10: the scales inside seg_tri's band, and a translated mesh
+SCALE_BAND = tuple(k for k in si.SCALES if abs(k) <= 256)                      # seg_tri's band is ray_tri's, about 2^-300 .. 2^300; -320 lies outside
+
+
+def _check_scale_case(vv, vidx, items, want, what):
+    """The rows of `items` on the mesh are `want`, and segments_closest is closest_of of them.  -> the rows"""
+    with _ctx(vv, vidx) as cd:
+        rows = _within(cd, items[:, 0:6], items[:, 6], what)
+        wr.same_rows(rows, want, what)
+        single = cd.segments_closest(items[:, 0:3], items[:, 3:6], items[:, 6])
+        _same_tuple(single[:11], sr.closest_of(want, sr.NSCALE), what + ", closest")
+        assert single[11].n_found == int((wr.rows_per_item(want, sr.NSCALE) > 0).sum()), what
+    return rows
+
+
+@pytest.mark.parametrize("k", SCALE_BAND)
+@pytest.mark.parametrize("name", sr.SCALE_MESHES)
+def test_scales_in_band(name, k):
+    """Mesh, both ends and the radius scaled by 2^k, past both fp32 ends -- where the stored boxes SegFilter::meets walks hold +-inf, 0
+    and subnormals and the pad 2^-20 max(M, |a|, |b|) overflows or vanishes: the k = 0 rows, with IDs, s, u, v, feature, end, cross and
+    side unchanged and dist, on_seg and on_tri times 2^k exactly (tests/test_segment_ref.py: the restatement's own property); at the
+    scales of scale_inputs.EDGES also the restatement on the scaled inputs themselves; segments_closest: closest_of of those rows."""
+    vv, vidx, items, want = sr.scale_case(name)
+    sr.scale_conditions(want)
+    what = f"{name} 2^{k}"
+    vs, its = si.scaled(vv, k), si.scaled(items, k)
+    rows = _check_scale_case(vs, vidx, its, sr.scaled_rows(want, k), what)
+    if k in si.EDGES:
+        wr.same_rows(rows, sr.segments_within_ref(vs, vidx, None, its), what + ", the restatement on the scaled inputs")
+
+
+@pytest.mark.parametrize("name", sr.SCALE_MESHES)
+def test_translated_mesh_gives_the_restatement(name):
+    """Mesh and both ends translated by 2^20 + 0.37: M is 2^20 while the radius is a fraction of an edge, so the pad's M 2^-20 term
+    (about 1) decides which leaves pass the fp32 filter."""
+    vt, vidx, items, want = sr.scale_case(name, 2.0 ** 20 + 0.37)
+    per = sr.scale_conditions(want)
+    print(f"{name} translated: {want.rows.shape[0]} rows, {int((per == 0).sum())} of {sr.NSCALE} items with none, {int((per >= 2).sum())} with several")
+    _check_scale_case(vt, vidx, items, want, f"{name} translated")
